@@ -305,6 +305,8 @@ def run_gpu(args, reduction, steps, warmup, rank, world, device, breakdown=True)
         res['dom'] = dom
         res['prof_dom'] = res['prof_timed'].get(dom)
         be.prof_enable(False)
+    if getattr(args, 'dump_outputs', None):                  # (before the untimed breakdown pass below moves the state on)
+        dump_outputs(run, args.dump_outputs, rank)
     lsw = be.last_sweeps()
     res['sweeps'], res['sweeps_max'] = float(lsw.mean()), int(lsw.max())
     if extra:
@@ -334,6 +336,30 @@ def run_gpu(args, reduction, steps, warmup, rank, world, device, breakdown=True)
     res['rows_fitted'] = run.row
     res['collective'] = collective_route(run, world, args)
     return res
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(run, out_dir, rank):
+    """--dump-outputs: the state a caller of the timed path holds after its last minibatch, written by rank 0 as float32
+    .npy files of at most DUMP_MAX_BYTES in all - the dictionary (`components`, k x p), the statistics (`C`, k x k;
+    `B`, k x p) and the codes of the last minibatch's rows (`code`, b x k).  When the dictionary and B_ do not fit the
+    budget (a wide --features), both keep the same fixed, seeded sample of feature columns, in increasing order."""
+    est = run.est
+    D, C_, B_ = est.components_, est.C_, est.B_              # (C_ / B_ are collective reads with several ranks)
+    if rank != 0:
+        return
+    r0 = (run.row - BATCH) % CHUNK                           # chunk-local rows of the last minibatch (sample_indices)
+    code = est.code_[r0:r0 + BATCH]
+    k, p = D.shape
+    share = (DUMP_MAX_BYTES - 4 * (C_.size + code.size)) // 2
+    if 4 * k * p > share:
+        cols = np.sort(np.random.RandomState(0).choice(p, share // (4 * k), replace=False))
+        D, B_ = D[:, cols], B_[:, cols]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (('components', D), ('C', C_), ('B', B_), ('code', code)):
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def collective_route(run, world, args):
@@ -711,7 +737,12 @@ def main():
     ap.add_argument('--share-gpu', action='store_true', help='testing only: every rank uses cuda:0 (needs --backend gloo)')
     ap.add_argument('--debug-set', action='append', default=[], metavar='WHAT=VALUE',
                     help='diagnostics: modl_debug_set(WHAT, VALUE) before anything runs (A/B runs of scripts/; see include/modl_hip.h)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy '
+                         '(float32, at most 64 MB in all; see dump_outputs), to compare two builds output for output')
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
     global P_FEAT, CHUNK, BLOCK
     if args.features != P_FEAT:
         # another feature count (C5: p = 200 000): chunks of at most ~8 GB (a power of two of rows, whole minibatches),

@@ -1,4 +1,4 @@
-cd $GRAFT_REPO_ROOT
+cd "$(dirname "$0")/.."
 python - <<'PY'
 import sys, time, json
 sys.path.insert(0, 'scripts'); sys.path.insert(0, '.')

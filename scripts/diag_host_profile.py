@@ -1,5 +1,5 @@
 import sys, os, time, argparse, cProfile, pstats
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 args = argparse.Namespace(torch_collective=False, backend='nccl', force_reduce=False)

@@ -1,6 +1,6 @@
 """Minibatch time at shapes other than the metric's (k not a power of two, wide p): python scripts/diag_shapes.py [lib.so|new] [shape index]"""
 import sys, os, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import modl_amd._lib as L
 if len(sys.argv) > 1 and os.path.exists(sys.argv[1]):     # another build of the library to compare with
     L.LIB_PATH = sys.argv[1]

@@ -3,7 +3,7 @@
 #   bash scripts/make_profiles.sh r06
 # writes gpurun_out/<tag>_*; copy what is to be judged into profiles/.
 TAG=${1:-r06}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out
 mkdir -p $OUT /tmp/w
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # Kernel traces + host profiles of BASELINE configs 2-4 (scripts/bench_configs.py) on the GPU box:
 #   bash scripts/prof_configs.sh r01_n     -> gpurun_out/<tag>_cfg_*.txt
 TAG=${1:-r02}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out
 mkdir -p $OUT /tmp/w
 cd /tmp && export TMPDIR=/tmp

@@ -1,4 +1,4 @@
-import sys; sys.path.insert(0, '/root/repo')
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
 from modl_amd import DictFact
 from oracle import somf_oracle as orc

@@ -2,7 +2,8 @@
 
 Run in the build container only (needs /root/reference, gcc, Cython):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            # every fixture
+    python tests/golden/make_golden.py rk_ref     # only the named ones
 
 It copies the hot-path sources of the reference into a scratch directory
 OUTSIDE the repository ($MODL_REF_SCRATCH or /tmp/modl_refbuild), compiles its
@@ -132,6 +133,46 @@ def gen_rng():
     out['trace_a'] = a
     out['trace_b'] = b2
     save('rng', **out)
+
+
+def gen_rk_ref():
+    """The raw draws of the reference's own randomkit.c + distributions.c, compiled in place into the scratch directory
+    (the recipe of oracle/Makefile `ref`), that tests/test_oracle_golden.py::test_rng_against_compiled_reference replays
+    on the oracle: per seed, in this order, 2000 rk_random, 50 rk_interval per maximum, 50 rk_double, 200 rk_binomial
+    per (n, p)."""
+    import ctypes as C
+    rk = os.path.join(REF, 'utils', 'randomkit')
+    os.makedirs(SCRATCH, exist_ok=True)
+    so = os.path.join(SCRATCH, 'librk_ref.so')
+    subprocess.check_call(['gcc', '-O2', '-fPIC', '-shared', '-I' + rk, '-o', so, os.path.join(rk, 'randomkit.c'),
+                           os.path.join(rk, 'distributions.c'), '-lm'])
+    ref = C.CDLL(so)
+    buf = C.create_string_buffer(8192)      # rk_state is ~5.2 KB
+    ref.rk_seed.argtypes = [C.c_ulong, C.c_void_p]
+    ref.rk_random.restype = C.c_ulong
+    ref.rk_random.argtypes = [C.c_void_p]
+    ref.rk_interval.restype = C.c_ulong
+    ref.rk_interval.argtypes = [C.c_ulong, C.c_void_p]
+    ref.rk_double.restype = C.c_double
+    ref.rk_double.argtypes = [C.c_void_p]
+    ref.rk_binomial.restype = C.c_long
+    ref.rk_binomial.argtypes = [C.c_void_p, C.c_long, C.c_double]
+    seeds = np.array([0, 5, 123456789, 2 ** 40 + 17], dtype=np.uint64)
+    maxes = np.array([1, 7, 1000, 2 ** 33], dtype=np.uint64)
+    binom_n = np.array([10000, 50, 10000, 200000, 10000], dtype=np.int64)
+    binom_p = np.array([0.1, 0.3, 1 / 12., 0.91, 0.1])
+    out = dict(seeds=seeds, interval_max=maxes, binom_n=binom_n, binom_p=binom_p,
+               random=np.zeros((len(seeds), 2000), np.uint64), interval=np.zeros((len(seeds), len(maxes), 50), np.uint64),
+               double=np.zeros((len(seeds), 50)), binomial=np.zeros((len(seeds), len(binom_n), 200), np.int64))
+    for a, seed in enumerate(seeds):
+        ref.rk_seed(int(seed), buf)
+        out['random'][a] = [ref.rk_random(buf) for _ in range(2000)]
+        for b_, mx in enumerate(maxes):
+            out['interval'][a, b_] = [ref.rk_interval(int(mx), buf) for _ in range(50)]
+        out['double'][a] = [ref.rk_double(buf) for _ in range(50)]
+        for b_, (n, p) in enumerate(zip(binom_n, binom_p)):
+            out['binomial'][a, b_] = [ref.rk_binomial(buf, int(n), float(p)) for _ in range(200)]
+    save('rk_ref', **out)
 
 
 def gen_sampler():
@@ -617,16 +658,15 @@ def gen_fmri():
 
 
 if __name__ == '__main__':
-    build_reference()
-    sys.path.insert(0, SCRATCH)
-    gen_rng()
-    gen_sampler()
-    gen_batch_weight()
-    gen_enet()
-    gen_cd()
-    gen_transform()
-    gen_traj()
-    gen_recsys()
-    gen_image()
-    gen_headline()
-    gen_fmri()
+    # `make_golden.py NAME ...` regenerates only the named fixtures (e.g. `rk_ref`); no argument: all of them
+    only = set(sys.argv[1:])
+    gens = [gen_rng, gen_rk_ref, gen_sampler, gen_batch_weight, gen_enet, gen_cd, gen_transform, gen_traj, gen_recsys,
+            gen_image, gen_headline, gen_fmri]
+    if only - {g.__name__[4:] for g in gens}:
+        raise SystemExit('unknown fixture(s): %s' % ' '.join(sorted(only - {g.__name__[4:] for g in gens})))
+    if only != {'rk_ref'}:                  # (rk_ref compiles its two C files itself)
+        build_reference()
+        sys.path.insert(0, SCRATCH)
+    for gen in gens:
+        if not only or gen.__name__[4:] in only:
+            gen()

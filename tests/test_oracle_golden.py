@@ -65,32 +65,44 @@ def test_rng_golden(oracle):
     assert_array_equal(b2, g['trace_b'])
 
 
+def _rk_draws(g, random_u32, interval, double, binomial):
+    """one seed's draws of tests/golden/rk_ref.npz, in the order they were recorded"""
+    return dict(random=[random_u32() for _ in range(g['random'].shape[1])],
+                interval=[[interval(int(mx)) for _ in range(g['interval'].shape[2])] for mx in g['interval_max']],
+                double=[double() for _ in range(g['double'].shape[1])],
+                binomial=[[binomial(int(n), float(p)) for _ in range(g['binomial'].shape[2])]
+                          for n, p in zip(g['binom_n'], g['binom_p'])])
+
+
 def test_rng_against_compiled_reference(oracle):
-    """oracle/_ref/librk_ref.so = the reference's own randomkit.c + distributions.c
-    compiled in place (oracle/Makefile `ref`); only present where it was built."""
+    """tests/golden/rk_ref.npz = the raw draws of the reference's own randomkit.c + distributions.c, compiled
+    (tests/golden/make_golden.py, gen_rk_ref); the oracle must reproduce them bit for bit.  Where oracle/_ref/librk_ref.so
+    was built (oracle/Makefile `ref`), the same draws are also taken from that library live."""
+    g = load_golden('rk_ref')
     so = os.path.join(ROOT, 'oracle', '_ref', 'librk_ref.so')
-    if not os.path.exists(so):
-        pytest.skip('oracle/_ref not built (no /root/reference on this box)')
-    ref = C.CDLL(so)
-    buf = C.create_string_buffer(8192)      # rk_state is ~5.2 KB
-    ref.rk_seed.argtypes = [C.c_ulong, C.c_void_p]
-    ref.rk_random.restype = C.c_ulong
-    ref.rk_random.argtypes = [C.c_void_p]
-    ref.rk_interval.restype = C.c_ulong
-    ref.rk_interval.argtypes = [C.c_ulong, C.c_void_p]
-    ref.rk_double.restype = C.c_double
-    ref.rk_double.argtypes = [C.c_void_p]
-    ref.rk_binomial.restype = C.c_long
-    ref.rk_binomial.argtypes = [C.c_void_p, C.c_long, C.c_double]
-    for seed in (0, 5, 123456789, 2 ** 40 + 17):
-        ref.rk_seed(seed, buf)
-        rs = oracle.OracleRandomState(seed)
-        assert [ref.rk_random(buf) for _ in range(2000)] == [rs.random_u32() for _ in range(2000)]
-        for mx in (1, 7, 1000, 2 ** 33):
-            assert [ref.rk_interval(mx, buf) for _ in range(50)] == [rs.randint(mx) for _ in range(50)]
-        assert [ref.rk_double(buf) for _ in range(50)] == [rs.double() for _ in range(50)]
-        for (n, p) in ((10000, 0.1), (50, 0.3), (10000, 1 / 12.), (200000, 0.91), (10000, 0.1)):
-            assert [ref.rk_binomial(buf, n, p) for _ in range(200)] == [rs.binomial(n, p) for _ in range(200)]
+    ref = None
+    if os.path.exists(so):
+        ref = C.CDLL(so)
+        buf = C.create_string_buffer(8192)      # rk_state is ~5.2 KB
+        ref.rk_seed.argtypes = [C.c_ulong, C.c_void_p]
+        ref.rk_random.restype = C.c_ulong
+        ref.rk_random.argtypes = [C.c_void_p]
+        ref.rk_interval.restype = C.c_ulong
+        ref.rk_interval.argtypes = [C.c_ulong, C.c_void_p]
+        ref.rk_double.restype = C.c_double
+        ref.rk_double.argtypes = [C.c_void_p]
+        ref.rk_binomial.restype = C.c_long
+        ref.rk_binomial.argtypes = [C.c_void_p, C.c_long, C.c_double]
+    for a, seed in enumerate(g['seeds']):
+        rs = oracle.OracleRandomState(int(seed))
+        runs = {'oracle': _rk_draws(g, rs.random_u32, rs.randint, rs.double, rs.binomial)}
+        if ref is not None:
+            ref.rk_seed(int(seed), buf)
+            runs['compiled reference'] = _rk_draws(g, lambda: ref.rk_random(buf), lambda mx: ref.rk_interval(mx, buf),
+                                                   lambda: ref.rk_double(buf), lambda n, p: ref.rk_binomial(buf, n, p))
+        for who, got in runs.items():
+            for key in ('random', 'interval', 'double', 'binomial'):
+                assert_array_equal(np.array(got[key], dtype=g[key].dtype), g[key][a], err_msg='%s %s seed %d' % (who, key, seed))
 
 
 def test_sampler_known_answers(oracle):
