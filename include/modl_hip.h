@@ -511,6 +511,26 @@ int modl_objective_f32(const float *d_X, int64_t ldx, int64_t n, int64_t p, cons
 int modl_objective_f64(const double *d_X, int64_t ldx, int64_t n, int64_t p, const double *d_Dt, int k, const double *d_code,
                        void *d_ws, size_t ws_bytes, double *d_out3, void *stream);
 
+/* Amari discrepancy between dictionaries (modl/decomposition/stability.py:7-31: amari_discrepency,
+ * mean_amari_discrepency).  For the n dictionaries h_d_dicts[i] (device, row-major k_i x p, atoms in rows), every pair
+ * a < b in the reference's generator order (a outer, b inner) gets
+ *   C[i][j] = (D_a[i] . D_b[j]) / ||D_a[i]|| / ||D_b[j]||,
+ *   d_pair[q] = 0.5 * (mean_j (1 - max_i C[i][j]) + mean_i (1 - max_j C[i][j]))     (n (n - 1) / 2 doubles).
+ * The maxima are signed and propagate NaN as ndarray.max does (a zero atom gives NaN).  d_rowmax (may be NULL) receives
+ * max_j C[i][j] of every pair, concatenated in pair order (sum over pairs of k_a values), d_colmax (may be NULL)
+ * max_i C[i][j] (sum of k_b values).  Norms are accumulated in f64, the products run on the matrix cores in the
+ * dtype, the means in f64; no atomics: run-to-run bit-identical.  `launches` (may be NULL) receives the number of
+ * kernels launched (3, or 4 when the products are split along p), independent of n.  The call returns after its
+ * small host tables have reached the device; the kernels are asynchronous.  Arguments are checked before any device
+ * work: n < 2, a k_i <= 0, p <= 0 or a NULL pointer -> MODL_EINVAL; d_ws NULL or smaller than
+ * modl_amari_workspace() -> MODL_ENOMEM; no device -> MODL_ENOGPU.  modl_amari_workspace returns 0 for bad
+ * arguments. */
+size_t modl_amari_workspace(int dtype, int n, const int64_t *h_k, int64_t p);
+int modl_amari_f32(const float *const *h_d_dicts, const int64_t *h_k, int n, int64_t p, double *d_pair, float *d_rowmax,
+                   float *d_colmax, void *d_ws, size_t ws_bytes, void *stream, int *launches);
+int modl_amari_f64(const double *const *h_d_dicts, const int64_t *h_k, int n, int64_t p, double *d_pair, double *d_rowmax,
+                   double *d_colmax, void *d_ws, size_t ws_bytes, void *stream, int *launches);
+
 /* layout helpers: out[c][r] = in[r][c]  (components_ <-> Dt) */
 int modl_transpose_f32(const float *d_in, float *d_out, int64_t rows, int64_t cols, void *stream);
 int modl_transpose_f64(const double *d_in, double *d_out, int64_t rows, int64_t cols, void *stream);

@@ -2,5 +2,6 @@
 (DictFact.partial_fit: code solve, surrogate statistics, block-coordinate
 dictionary update) behind the reference's estimator API."""
 from .dict_fact import DictFact, Coder  # noqa: F401
+from .stability import amari_discrepency, mean_amari_discrepency  # noqa: F401
 
-__all__ = ['DictFact', 'Coder']
+__all__ = ['DictFact', 'Coder', 'amari_discrepency', 'mean_amari_discrepency']
