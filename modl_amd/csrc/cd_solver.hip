@@ -739,6 +739,7 @@ extern "C" int modl_debug_set(int what, int64_t value) {
         return MODL_OK;
     }
     if (what == MODL_DEBUG_RECSYS_FUSED) {
+        if (value != 0 && value != 1) return MODL_EINVAL;
         modl::g_recsys_fused.store((int)value, std::memory_order_relaxed);
         return MODL_OK;
     }

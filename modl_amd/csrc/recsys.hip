@@ -184,44 +184,30 @@ __global__ __launch_bounds__(256) void recsys_predict_kernel(double *out, const 
     }
 }
 
-// ---- the masked minibatch as ONE launch (round 6) -------------------------------------------------------------------------
-// recsys.py:147-213 for a batch of at most 64 rows, at most 64 (f64: 56) atoms: codes, B_, C_ and the dictionary update in one kernel
-// (it was ten launches per minibatch of ten rows: a code launch that lasted as long as the batch's heaviest row, the B_ and C_
-// updates, then the blocked dictionary update as separate launches).
+// ---- the masked minibatch's codes and C_ as ONE launch (round 6) ---------------------------------------------------------
+// recsys.py:159-160 and :176-181 for a batch of at most 64 rows, at most 64 (f64: 56) atoms.
 //   * CHUNK workgroups: a row's ratings are cut into chunks of 128 (the work is balanced by ratings, not by rows); a chunk's
-//     Gram contribution D_S^T D_S and right-hand side are accumulated from the feature-major dictionary rows in 4 x 4 register
-//     tiles (the next 32 rows requested while the current 32 are contracted).  A row of several chunks meets in a scratch
+//     Gram contribution D_S^T D_S and right-hand side are accumulated from the feature-major dictionary rows on the matrix
+//     cores (the next 32 rows requested while the current 32 are contracted).  A row of several chunks meets in a scratch
 //     record per chunk: write-through stores, one ticket per workgroup, the LAST to arrive sums the records in chunk order
-//     (a fixed order: run-to-run identical) - then factors and solves the row's k x k system in LDS (chol_small.hpp) and
-//     writes code_[row].
+//     (a fixed order: run-to-run identical) - then one wavefront factors and solves the row's k x k system in registers
+//     (chol_solve_wave_reg) and writes code_[row].
 //   * the LAST row to finish (a second ticket) goes on alone, 512 threads: C_ = (1 - w) C_ + (w / b) code_[batch]^T code_[batch]
-//     (recsys.py:159-160), the per-item B_ update in batch order (:175, :182-185: a wavefront per touched item), and the
-//     dictionary update on the touched items (:187-213) with ONE ITEM PER THREAD: the item's k dictionary entries stay in
-//     registers in sweep order for the whole sweep; per atom the candidate is (B_j - sum_{i != j} C[i][j] D_i) / C[j][j]
-//     against the registers as they are (the reference's two rank-1 passes per atom over a k x u gradient, evaluated lazily),
-//     its norm and the atom's old norm are ONE workgroup-wide reduction (wave sums, eight partial sums through LDS, one
-//     barrier per atom), the clip to the atom's budget, next atom.  The atom loop is unrolled (the register of atom j is a
-//     compile-time index), KP = 32 or 64 (f64: 56) registers per item.
-// More than 512 touched items: the kernel stops after B_ and the host runs the blocked dictionary update's launches.
+//     (recsys.py:159-160), then it resets the tickets for the next launch.
+// B_ (:175, :182-185) and the blocked dictionary update (:187-213) follow as launches of their own.
 constexpr int kRfMaxChunks = 64, kRfMaxBatch = 64, kRfChunk = 128;
-constexpr int kRfMaxSweep = 4;                          // sweep workgroups of 512 items each
-constexpr long long kRfSentinel = 0x7ff8dead0000beefll; // a NaN no sum produces
 typedef unsigned int rf_u4 __attribute__((ext_vector_type(4)));   // (a native vector: an array of HIP's uint4 structs went to scratch)
 struct RecsysChunk { int32_t pos, beg, cnt, nch, ci, part0; };   // row of the batch, first CSR entry, entries, chunks of the row, index among them, first record
 template <typename T> struct RecsysFusedArgs {
     const int32_t *indptr, *indices;
     const T *data;
-    T *Dt, *Bt, *C, *code, *comp_norm;
-    int64_t *feature_n_iter;
-    const int32_t *order, *subset, *fptr, *esample;      // the staged minibatch (device copy of the pinned slot)
-    const T *eval;
+    const T *Dt;
+    T *C, *code;
     T *part;                                             // [chunks][k * k + k] records of rows with several chunks
     unsigned int *tickets;                               // [kRfMaxBatch + 1], zero between launches (the last workgroup clears them)
-    double *xch;                                         // [(2 KP + KP) x kRfMaxSweep] exchange slots of the sweep workgroups, sentinels between launches
-    double alpha, w, w_n_iter;
+    double alpha, w;
     int64_t p;
-    int k, b, u, n_solve, do_dict, nsweep;
-    int cap2;                                            // items of a sweep workgroup's LDS tier (a multiple of 64, at most 512)
+    int k, b, u, n_solve;                                // (u: touched items, only stamped)
     unsigned long long *dbg;                             // optional: 100 MHz wall-clock stamps of the LAST workgroup (modl_recsys_plan_stamps)
     // the NEXT minibatch's pinned slot -> the other device staging buffer, by one more workgroup at the end of the grid (the
     // run of minibatches of modl_recsys_fit_batches_*: no staging launch between two minibatches); stage_n16 == 0: none
@@ -249,8 +235,9 @@ __device__ __forceinline__ double rf_load(const double *ptr) {
                                                              __HIP_MEMORY_SCOPE_AGENT));
 }
 
-// the widest variant: an item's atoms in registers for the whole sweep, 512 threads = two waves per SIMD = 256 registers per
-// thread: 64 floats, or 56 doubles (64 doubles spill; a masked minibatch with more atoms takes the separate launches)
+// the widest variant: the most atoms a minibatch may have to take this launch, and the registers per lane of the row's system
+// in chol_solve_wave_reg: 64 (f32) / 56 (f64).  (The limits were set by an in-kernel dictionary sweep since removed, DESIGN.md
+// Appendix A; they are kept so that the same minibatches take this path.  More atoms: the separate launches.)
 template <typename T> struct kRfWide { static constexpr int value = sizeof(T) == 4 ? 64 : 56; };
 
 template <int J, int N, typename F> __device__ __forceinline__ void rf_static_for(F &&f) {
@@ -258,32 +245,6 @@ template <int J, int N, typename F> __device__ __forceinline__ void rf_static_fo
         f(std::integral_constant<int, J>{});
         rf_static_for<J + 1, N>(f);
     }
-}
-
-// a workgroup barrier that orders LDS traffic only (global requests stay in flight across it)
-__device__ __forceinline__ void rf_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// D[jj] = v for a wavefront-uniform jj, every register index a compile-time constant: a uniform branch to the group of eight
-// registers, eight selects
-template <typename T, int KP> __device__ __forceinline__ void rf_set(T (&D)[KP], int jj, T v) {
-    static_assert(KP % 8 == 0, "groups of eight registers");
-    const int g = jj >> 3, r = jj & 7;
-    rf_static_for<0, KP / 8>([&](auto G) {
-        constexpr int gg = decltype(G)::value;
-        if (g == gg) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) {
-                D[8 * gg + x] = (r == x) ? v : D[8 * gg + x];
-                // (opaque: the optimiser recognises the chain of selects as an insertion at a variable index and moves the
-                //  whole array to scratch)
-                asm volatile("" : "+v"(D[8 * gg + x]));
-            }
-        }
-    });
 }
 
 // The row's k x k system (k <= KC) factored and solved by ONE wavefront with the matrix in REGISTERS: lane i holds row i, column j
@@ -343,11 +304,10 @@ __device__ __forceinline__ T chol_solve_wave_reg(const T *G, int ld, int k, cons
 }
 
 template <typename T>
-size_t recsys_fused_lds(int k, int b, int KP, int cap2) {
+size_t recsys_fused_lds(int k, int b) {
     const size_t KS = (size_t)((k + 3) & ~3), ld = (size_t)(k | 1);
     const size_t chunk = sizeof(T) * ((size_t)k * ld + 4 + 2 * KS + 768 + 2 * 32 * (size_t)((k + 15) & ~15) + kRfChunk) + sizeof(int) * (kRfChunk + 8);
-    const size_t fin = sizeof(T) * ((size_t)k * KP + (size_t)b * k + 3 * (size_t)KP) + sizeof(double) * (2 * 8 * 2 + 8 * (size_t)KP) +
-                       ((sizeof(int) * ((size_t)KP + 8) + 15) & ~(size_t)15) + sizeof(T) * (size_t)KP * cap2 + 16;
+    const size_t fin = sizeof(T) * (size_t)b * k;                                      // the batch's codes
     return (chunk > fin ? chunk : fin) + 64;
 }
 
@@ -356,7 +316,6 @@ __global__ __launch_bounds__(512) void recsys_fused_kernel(const RecsysFusedArgs
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int k = a.k;
-    int me = 0;                                                 // which of the sweep workgroups this one becomes (0: the last to finish)
     unsigned long long stp[8];                                  // stamps of the chunk phase (kept only by the last workgroup)
     stp[0] = a.dbg ? wall_clock64() : 0;
     if (a.stage_n16 && blockIdx.x == gridDim.x - 1) {           // the rider: the next minibatch's staged arrays
@@ -531,286 +490,27 @@ __global__ __launch_bounds__(512) void recsys_fused_kernel(const RecsysFusedArgs
         if (tid == 0) flag[1] = (int)__hip_atomic_fetch_add(a.tickets + kRfMaxBatch, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         stp[5] = a.dbg ? wall_clock64() : 0;
-        me = a.n_solve - 1 - flag[1];                           // 0: the last row to finish, 1 .. : the ones just before it
-        if (me >= a.nsweep) return;
-        if (me > 0) {
-            // a helper of the sweep: every code is ready when the last row has taken its ticket.  (It WILL: every workgroup of
-            // this launch that has not run yet needs one free compute unit, and the helpers hold at most three.)
-            if (tid == 0) {
-                unsigned spins = 0;
-                while (__hip_atomic_load(a.tickets + kRfMaxBatch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)a.n_solve &&
-                       ++spins < (1u << 20))
-                    __builtin_amdgcn_s_sleep(8);
-            }
-        }
-        __syncthreads();
+        if (flag[1] != a.n_solve - 1) return;                   // only the last row to finish goes on
+        __syncthreads();                                        // (every thread has read flag before the LDS is reused)
     }
-    // ------------------------------------------- the last nsweep workgroups: C_, B_ and the dictionary on 512 items each
-    const int b = a.b, u = a.u, W = a.nsweep;
-    T *Csw = reinterpret_cast<T *>(smem_raw);                   // [k][KP] C in sweep coordinates, zero diagonal, zero padding
-    T *codeb = Csw + (size_t)k * KP;                            // [b][k]
-    T *cdg = codeb + (size_t)b * k;                             // [KP] reciprocals of the diagonal of C (0: frozen), sweep order
-    T *cn = cdg + KP;                                           // [KP] norm budgets, sweep order
-    T *bud = cn + KP;                                           // [KP] budget each atom was clipped to
-    double *red = reinterpret_cast<double *>(bud + KP);         // [2][8][2]
-    double *red2 = red + 32;                                    // [8][KP]
-    int *ord = reinterpret_cast<int *>(red2 + 8 * KP);          // [KP]
-    const bool stamp = a.dbg && me == 0 && tid == 0;
+    // ------------------------------------------- the last row to finish: C_ = (1 - w) C_ + (w / b) code_[batch]^T code_[batch]
+    const int b = a.b;
+    T *codeb = reinterpret_cast<T *>(smem_raw);                 // [b][k]
+    const bool stamp = a.dbg && tid == 0;
     if (stamp) {
         for (int x = 0; x < 6; ++x) a.dbg[x] = stp[x];
         a.dbg[6] = wall_clock64();
     }
     for (int e = tid; e < b * k; e += 512) codeb[e] = rf_load(a.code + a.rows[e / k] * k + e % k);
-    if (tid < KP) ord[tid] = (tid < k) ? a.order[tid] : 0;
     __syncthreads();
-    // C_ = (1 - w) C_ + (w / b) code_[batch]^T code_[batch] (recsys.py:159-160) - formed by every sweep workgroup for itself, in
-    // sweep coordinates, from the C_ in memory, which the first of them replaces only at the very end (below)
-    auto c_new = [&](int oj, int oi) {
+    // (recsys.py:159-160; every element of C_ is read and written by its own thread only)
+    for (int e = tid; e < k * k; e += 512) {
+        const int oj = e / k, oi = e % k;
         T dot = 0;
         for (int rr = 0; rr < b; ++rr) dot = fma(codeb[rr * k + oj], codeb[rr * k + oi], dot);
-        return (T)((1.0 - a.w) * (double)a.C[(int64_t)oj * k + oi]) + (T)(a.w / (double)b) * dot;
-    };
-    for (int e = tid; e < k * KP; e += 512) {
-        const int jj = e / KP, ii = e % KP;
-        T v = 0;
-        if (ii < k) {
-            v = c_new(ord[jj], ord[ii]);
-            if (ii == jj) { cdg[jj] = (v > (T)1e-20) ? (T)1 / v : (T)0; v = 0; }     // (the reciprocal; 0: recsys.py:201 "else do not update")
-        }
-        Csw[e] = v;
+        a.C[e] = (T)((1.0 - a.w) * (double)a.C[e]) + (T)(a.w / (double)b) * dot;
     }
-    if (tid < KP) cn[tid] = (tid < k) ? a.comp_norm[ord[tid]] : (T)0;
-    // B_: ONE ITEM PER THREAD (recsys.py:175, 182-185: the item's entries in batch order), the items of this workgroup's slice -
-    // or, without an in-kernel sweep, all of them in passes.  Every load a thread needs for its item is independent of the other
-    // threads': 512 items in flight per pass (a wavefront per item, as a launch of its own did it, is a chain of three
-    // dependent round trips per item - 94 items per wavefront took 100 us here).
-    if (stamp) a.dbg[7] = wall_clock64();
-    const int per = 512 + a.cap2;                               // items of a sweep workgroup: 512 in registers + cap2 in LDS
-    // (without an in-kernel sweep B_ is not updated here either: one workgroup walking every item's row takes 50 us for the
-    //  thousand items of a MovieLens minibatch, the launch of its own that the host enqueues behind this one - a wavefront per
-    //  item over the whole chip - 6 us)
-    const int it0 = a.do_dict ? per * me : 0, it1 = a.do_dict ? ((u < it0 + per) ? u : it0 + per) : 0;
-    for (int base = it0; base < it1; base += 512) {
-        const int fi = base + tid;
-        const bool on = fi < it1;
-        const int32_t f = a.subset[on ? fi : it0];
-        const int e0 = a.fptr[on ? fi : it0], e1 = on ? a.fptr[fi + 1] : e0;
-        int64_t n = a.feature_n_iter[f];
-        T *brow = a.Bt + (int64_t)f * k;
-        T bv[KP];
-#pragma unroll
-        for (int c = 0; c < KP; ++c) bv[c] = brow[c < k ? c : 0];
-        for (int e = e0; e < e1; ++e) {
-            n += 1;                                             // recsys.py:175
-            double wB = a.w_n_iter / (double)n;                 // :182-183
-            wB = wB < 1.0 ? wB : 1.0;
-            const double xw = (double)a.eval[e] * wB;
-            const T *cr = codeb + a.esample[e] * k;
-#pragma unroll
-            for (int c = 0; c < KP; ++c) {
-                if (c < k) {
-                    T t = (T)((double)bv[c] * (1.0 - wB));      // B_[:, subset] *= 1 - w_B
-                    bv[c] = (T)((double)t + (double)cr[c] * xw); // += outer(code, X_subset * w_B)
-                }
-            }
-        }
-        if (on && e1 > e0) {
-#pragma unroll
-            for (int c = 0; c < KP; ++c)
-                if (c < k) brow[c] = bv[c];
-            a.feature_n_iter[f] = n;
-        }
-    }
-    __syncthreads();
-    if (stamp) a.dbg[8] = wall_clock64();
-    if (a.do_dict) {
-        const int fi = it0 + tid;
-        const bool live = fi < it1;
-        const int64_t fo = (int64_t)a.subset[live ? fi : 0] * k;
-        // the LDS tier: a SECOND item for the first cap2 threads, its atoms in LDS (D2[atom][thread]: a wavefront reads
-        // consecutive words) - a minibatch of ten MovieLens rows touches 700-800 items, more than 512 threads hold in registers
-        const int cap2 = a.cap2;
-        T *D2 = reinterpret_cast<T *>(reinterpret_cast<char *>(ord) + ((sizeof(int) * (KP + 8) + 15) & ~(size_t)15));   // [KP][cap2]
-        const int fi2 = it0 + 512 + tid;
-        const bool live2 = tid < cap2 && fi2 < it1;
-        const bool wave2 = (wid * 64 < cap2) && (it0 + 512 + wid * 64 < it1);     // (wave-uniform: this wave has second items)
-        const int64_t fo2 = (int64_t)a.subset[live2 ? fi2 : 0] * k;
-        T bn2 = 0;
-        if (wave2) {                                                     // (before the first item's registers are live)
-#pragma unroll 8
-            for (int ii = 0; ii < KP; ++ii) {
-                const T v = a.Dt[fo2 + ord[ii]];
-                if (tid < cap2) D2[ii * cap2 + tid] = (live2 && ii < k) ? v : (T)0;
-            }
-            bn2 = a.Bt[fo2 + ord[0]];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        T Dr[KP];
-#pragma unroll
-        for (int ii = 0; ii < KP; ++ii) Dr[ii] = a.Dt[fo + ord[ii]];
-#pragma unroll
-        for (int ii = 0; ii < KP; ++ii) Dr[ii] = (live && ii < k) ? Dr[ii] : (T)0;
-        T bn = a.Bt[fo + ord[0]];
-        // The atom loop is a RUNTIME loop with one shared body.  (Round 6, first version: unrolled by recursion so that the atom's
-        // register was a compile-time index - 56 copies of a 300-instruction body, 134 KB of straight-line code executed once:
-        // the sweep was bound by INSTRUCTION FETCH, 1.8 us per atom whatever the number of items, 89 of a minibatch's 172 us.)
-        // (Measured and not kept: the row of C read with SCALAR loads from a copy in memory - no LDS traffic, but seven dependent
-        //  scalar-memory round trips per wavefront and atom: 88 -> 128 us.)
-        // What needs the atom's index: the dot product does not (C in sweep coordinates has a zero diagonal); the atom's old
-        // value comes from memory with the B_ entry, one atom ahead; the new value goes into its register through a uniform
-        // switch over groups of eight registers (rf_set: a scalar branch + eight selects).
-        // The B_ entry and the old value of an atom are requested TWO atoms ahead, and the barriers inside the loop order LDS
-        // traffic only (rf_lds_barrier): __syncthreads() also waits for every outstanding global load - it drained the requests
-        // it was meant to overlap, a memory round trip per atom (4.5 k cycles per atom, 93 of a minibatch's 175 us, measured).
-        T dn = a.Dt[fo + ord[0]];
-        T dn2 = wave2 ? a.Dt[fo2 + ord[0]] : (T)0;
-        T bm = a.Bt[fo + ord[k > 1 ? 1 : 0]], dm = a.Dt[fo + ord[k > 1 ? 1 : 0]];
-        T bm2 = wave2 ? a.Bt[fo2 + ord[k > 1 ? 1 : 0]] : (T)0, dm2 = wave2 ? a.Dt[fo2 + ord[k > 1 ? 1 : 0]] : (T)0;
-        for (int jj = 0; jj < k; ++jj) {
-            {
-                const int jn = (jj + 2 < k) ? jj + 2 : k - 1;
-                const T bvj = live ? bn : (T)0;
-                const T dold = live ? dn : (T)0;
-                bn = bm; dn = dm;
-                bm = a.Bt[fo + ord[jn]];
-                dm = a.Dt[fo + ord[jn]];
-                // the row of C as explicit 16-byte LDS reads (KP / VW of them: the LDS pipe is what bounds this loop - eight
-                // wavefronts broadcast-read every row)
-                constexpr int VW = 16 / (int)sizeof(T);
-                typedef T rf_vec __attribute__((ext_vector_type(VW)));
-                const rf_vec *crow = reinterpret_cast<const rf_vec *>(Csw + jj * KP);
-                T dot = 0, dot2 = 0;
-                const int t2 = tid < cap2 ? tid : 0;
-                if (!wave2) {
-#pragma unroll
-                    for (int iv = 0; iv < KP / VW; ++iv) {
-                        const rf_vec c = crow[iv];
-#pragma unroll
-                        for (int x = 0; x < VW; ++x) dot = fma(c[x], Dr[iv * VW + x], dot);
-                    }
-                } else {                                         // (both items of the thread on one read of the row of C)
-#pragma unroll
-                    for (int iv = 0; iv < KP / VW; ++iv) {
-                        const rf_vec c = crow[iv];
-#pragma unroll
-                        for (int x = 0; x < VW; ++x) {
-                            dot = fma(c[x], Dr[iv * VW + x], dot);
-                            dot2 = fma(c[x], D2[(iv * VW + x) * cap2 + t2], dot2);
-                        }
-                        if ((iv & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // (a few LDS reads in flight, not all KP: registers)
-                    }
-                }
-                const T icd = cdg[jj];                                   // 1 / C[j][j], or 0: "else do not update"
-                T un = (icd != (T)0) ? (bvj - dot) * icd : dold;       // recsys.py:201-203
-                un = live ? un : (T)0;
-                double o2 = (double)dold * (double)dold, n2 = (double)un * (double)un;
-                T un2 = 0;
-                if (wave2) {
-                    const T bv2 = live2 ? bn2 : (T)0;
-                    const T dold2 = live2 ? dn2 : (T)0;
-                    bn2 = bm2; dn2 = dm2;
-                    bm2 = a.Bt[fo2 + ord[jn]];
-                    dm2 = a.Dt[fo2 + ord[jn]];
-                    un2 = (icd != (T)0) ? (bv2 - dot2) * icd : dold2;
-                    un2 = live2 ? un2 : (T)0;
-                    o2 += (double)dold2 * (double)dold2;
-                    n2 += (double)un2 * (double)un2;
-                }
-                o2 = wave_sum(o2);
-                n2 = wave_sum(n2);
-                double *rd = red + (jj & 1) * 16;
-                if (lane == 0) { rd[2 * wid] = o2; rd[2 * wid + 1] = n2; }
-                rf_lds_barrier();
-                double so = 0, sn = 0;
-#pragma unroll
-                for (int x = 0; x < 8; ++x) { so += rd[2 * x]; sn += rd[2 * x + 1]; }
-                if (W > 1) {
-                    // the other sweep workgroups' sums of this atom: written through, read past the caches, the data is its own
-                    // flag (a NaN no sum can be: the first workgroup restores it at the end of the launch) - one memory round trip
-                    double *slot = a.xch + (size_t)jj * 2 * kRfMaxSweep;
-                    if (tid < 2) rf_store(slot + 2 * me + tid, tid == 0 ? so : sn);
-                    double got = 0.0;
-                    if (tid < 2 * W) {
-                        unsigned spins = 0;
-                        do got = rf_load(slot + tid);
-                        while (__double_as_longlong(got) == kRfSentinel && ++spins < (1u << 18));
-                    }
-                    // (red2 is free until the end of the sweep; it is rewritten behind the NEXT atom's barrier, which every
-                    //  thread reaches only after it has read these)
-                    if (tid < 2 * kRfMaxSweep) red2[tid] = (tid < 2 * W) ? got : 0.0;
-                    rf_lds_barrier();
-                    so = (red2[0] + red2[2]) + (red2[4] + red2[6]);
-                    sn = (red2[1] + red2[3]) + (red2[5] + red2[7]);
-                }
-                const T budget = cn[jj] + (T)so;                         // :197-198 comp_norm_ += subset_norm
-                // :205-208 norm = sqrt(sum), lim = sqrt(budget), "if norm > lim: atom /= norm / lim" as ONE factor
-                // sqrt(budget / sum) (a negative or NaN budget never clips, as there)
-                const bool clip = (T)sn > budget && budget >= (T)0;
-                const T scale = clip ? (T)sqrt((double)budget / sn) : (T)1;
-                un *= scale;
-                rf_set<T, KP>(Dr, jj, un);
-                if (wave2) {
-                    un2 *= scale;
-                    if (tid < cap2) D2[jj * cap2 + tid] = un2;
-                }
-                if (tid == 0) bud[jj] = budget;
-            }
-        }
-        // the projected atoms' norms leave the budgets (:211-212), the rows go back
-        __syncthreads();                                                 // (red2 held the last atom's exchanged sums)
-        if (stamp) a.dbg[9] = wall_clock64();
-#pragma unroll
-        for (int ii = 0; ii < KP; ++ii) {
-            double q2 = (double)Dr[ii] * (double)Dr[ii];
-            if (wave2) {
-                const T d2 = D2[ii * cap2 + (tid < cap2 ? tid : 0)];
-                q2 += live2 ? (double)d2 * (double)d2 : 0.0;
-                if (live2 && ii < k) a.Dt[fo2 + ord[ii]] = d2;
-            }
-            const double s2 = wave_sum(q2);
-            if (lane == 0) red2[wid * KP + ii] = s2;
-        }
-        if (live)
-#pragma unroll
-            for (int ii = 0; ii < KP; ++ii)
-                if (ii < k) a.Dt[fo + ord[ii]] = Dr[ii];
-        __syncthreads();
-        double s2 = 0;
-        if (tid < KP) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) s2 += red2[x * KP + tid];
-        }
-        if (W > 1) {
-            double *slot = a.xch + (size_t)KP * 2 * kRfMaxSweep;           // [kRfMaxSweep][KP] behind the atoms' slots
-            if (me > 0) {
-                if (tid < k) rf_store(slot + (size_t)me * KP + tid, s2);
-                return;                                                  // (a helper is done)
-            }
-            for (int h = 1; h < W; ++h) {
-                double got = 0.0;
-                if (tid < k) {
-                    unsigned spins = 0;
-                    do got = rf_load(slot + (size_t)h * KP + tid);
-                    while (__double_as_longlong(got) == kRfSentinel && ++spins < (1u << 18));
-                }
-                s2 += got;
-            }
-        }
-        if (tid < k) a.comp_norm[ord[tid]] = bud[tid] - (T)s2;
-        if (W > 1) {                                                     // the slots back to sentinels: every helper has left them
-            __syncthreads();                                             // (... once wave 0 has READ the helpers' last ones)
-            long long *xs = reinterpret_cast<long long *>(a.xch);
-            for (int e2 = tid; e2 < (KP * 2 + KP) * kRfMaxSweep; e2 += 512) xs[e2] = kRfSentinel;
-        }
-    }
-    // (only the first sweep workgroup is left) C_ in memory, natural order: the same expression, the same bits as Csw
-    __syncthreads();
-    for (int e = tid; e < k * k; e += 512) {
-        a.part[e] = c_new(e / k, e % k);                                 // (staged: every C_[oj][oi] is still read by other threads' c_new)
-    }
-    __syncthreads();
-    for (int e = tid; e < k * k; e += 512) a.C[e] = a.part[e];
-    if (stamp) { a.dbg[10] = wall_clock64(); a.dbg[11] = (unsigned long long)a.u; a.dbg[12] = (unsigned long long)a.nsweep; }
+    if (stamp) { a.dbg[7] = a.dbg[10] = wall_clock64(); a.dbg[11] = (unsigned long long)a.u; }
     if (tid <= kRfMaxBatch) a.tickets[tid] = 0;                 // for the next launch
 }
 
@@ -857,7 +557,7 @@ template <typename T> struct EpiAxpbyC {
 // and the atom order into a pinned slot, moved to HBM by a kernel reading the device-mapped slot (no copy-engine hop
 // between kernels), then the four launches of the step.  Nothing is synchronised: a ring of slots + events.
 constexpr int kRecsysSlots = 8;
-std::atomic<int> g_recsys_fused{1};        // modl_debug_set(MODL_DEBUG_RECSYS_FUSED, ...): 0 = the separate launches of rounds 2-5
+std::atomic<int> g_recsys_fused{1};        // modl_debug_set(MODL_DEBUG_RECSYS_FUSED, 1 / 0): 0 = the separate launches of rounds 2-5
 
 }  // namespace modl
 
@@ -878,7 +578,6 @@ struct modl_recsys_plan {
     // acknowledgement word the staging kernel writes into the slot itself (its use count; no stream event)
     char *part = nullptr;
     unsigned int *tickets = nullptr;
-    double *xch = nullptr;                     // exchange slots of the sweep workgroups (sentinels between launches)
     unsigned long long *dbg = nullptr;         // modl_recsys_plan_stamps(plan, 1, ...): stamps of the last workgroup of each launch
     unsigned long long uses[modl::kRecsysSlots] = {0};
     size_t ack_off = 0;
@@ -1042,35 +741,10 @@ int recsys_launch(modl_recsys_plan *pl, const RecsysPrep &pr, bool staged, const
         }
         if (fits) {
             fa.indptr = d_indptr; fa.indices = d_indices; fa.data = d_data;
-            fa.Dt = Dt; fa.Bt = Bt; fa.C = C; fa.code = code; fa.comp_norm = comp_norm; fa.feature_n_iter = feature_n_iter;
-            fa.order = d_order; fa.subset = d_subset; fa.fptr = d_fptr; fa.esample = d_es; fa.eval = d_ev;
+            fa.Dt = Dt; fa.C = C; fa.code = code;
             fa.part = reinterpret_cast<T *>(pl->part); fa.tickets = pl->tickets;
-            fa.alpha = alpha; fa.w = w; fa.w_n_iter = w * n_iter; fa.p = pl->p;
+            fa.alpha = alpha; fa.w = w; fa.p = pl->p;
             fa.k = k; fa.b = (int)b; fa.u = (int)u; fa.n_solve = n_solve;
-            constexpr int KPW0 = kRfWide<T>::value;
-            const int KP0 = k <= 32 ? 32 : KPW0;
-            {   // the LDS tier: what 160 KB leave next to the last phase's other arrays, in whole wavefronts
-                const size_t base = recsys_fused_lds<T>(k, (int)b, KP0, 0);
-                const size_t room = base < 156 * 1024 ? 156 * 1024 - base : 0;
-                int cap = (int)(room / (sizeof(T) * KP0)) & ~63;
-                if (cap > 512) cap = 512;
-                if (g_recsys_fused.load(std::memory_order_relaxed) == 3) cap = 0;      // (registers only)
-                fa.cap2 = cap;
-            }
-            const int per = 512 + fa.cap2;
-            fa.nsweep = (int)std::max<int64_t>(1, (u + per - 1) / per);
-            fa.do_dict = (u > 0 && fa.nsweep <= kRfMaxSweep && fa.nsweep <= std::max(n_solve, 1)) ? 1 : 0;
-            // Where B_ and the dictionary update run.  MEASURED (scripts/ab_recsys_fused.sh, MovieLens-10M-shaped rows, k = 50,
-            // b = 10, f64; profiles/r06_ab_recsys_fused.txt): as launches of their own behind this one - a wavefront per item, the
-            // blocked update over the whole chip - 197 us per minibatch at 109 ratings per row, 169 at 36, 130 at 13; inside this
-            // kernel on ONE workgroup (value 2; 3 without the LDS tier) 251-333 / 203 / 172 us - one compute unit walks a thousand
-            // item rows and broadcasts every row of C to eight wavefronts (1.5 us per atom, bound by the LDS pipe) while 255 units
-            // idle; on up to four workgroups that exchange every atom's sums through memory (value 4) 345 us.  So the default (1)
-            // keeps this launch to the codes and C_; the in-kernel variants stay selectable (and tested: they are correct).
-            const int mode = g_recsys_fused.load(std::memory_order_relaxed);
-            if (mode == 1 || (fa.nsweep > 1 && mode != 4)) fa.do_dict = 0;
-            if (!fa.do_dict) fa.nsweep = 1;
-            fa.xch = pl->xch;
             fa.dbg = pl->dbg;
             fa.stage_src = nullptr; fa.stage_dst = nullptr; fa.stage_n16 = 0; fa.stage_ack = nullptr; fa.stage_use = 0;
             if (next) {                                      // the next minibatch's arrays ride along, into the other buffer
@@ -1080,9 +754,9 @@ int recsys_launch(modl_recsys_plan *pl, const RecsysPrep &pr, bool staged, const
                 fa.stage_ack = reinterpret_cast<unsigned long long *>(pl->hdev[next->slot] + pl->ack_off);
                 fa.stage_use = next->use;
             }
-            constexpr int KPW = kRfWide<T>::value;             // registers per item of the wide variant: 64 (f32) / 56 (f64)
+            constexpr int KPW = kRfWide<T>::value;             // registers per lane of the row's system: 64 (f32) / 56 (f64)
             const int KP = k <= 32 ? 32 : KPW;
-            const size_t lds = recsys_fused_lds<T>(k, (int)b, KP, fa.cap2);
+            const size_t lds = recsys_fused_lds<T>(k, (int)b);
             const unsigned grid = (unsigned)(nc > 0 ? nc : 1) + (fa.stage_n16 ? 1u : 0u);
             if (KP == 32) {
                 MODL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&recsys_fused_kernel<T, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1097,8 +771,9 @@ int recsys_launch(modl_recsys_plan *pl, const RecsysPrep &pr, bool staged, const
                 pl->cur ^= 1;
                 if (next_staged) *next_staged = true;
             }
-            if (u > 0 && !fa.do_dict) {                      // more touched items than the sweep's workgroups hold: B_ and the
-                                                             // blocked dictionary update as launches of their own
+            // B_ and the blocked dictionary update as launches of their own: measured faster than inside this launch on one
+            // compute unit
+            if (u > 0) {
                 hipLaunchKernelGGL((recsys_update_B_kernel<T>), dim3((unsigned)cdiv(u, 4)), dim3(256), 0, st, Bt, k, feature_n_iter,
                                    d_subset, d_fptr, d_es, d_ev, (const T *)code, d_rows, w * n_iter, u);
                 MODL_LAUNCH_CHECK();
@@ -1296,11 +971,6 @@ int modl_recsys_plan_create(int dtype, int64_t p, int k, int64_t max_batch, int6
         e = hipMalloc((void **)&pl->part, tsz * (size_t)kRfMaxChunks * ((size_t)k * k + k));
         if (e == hipSuccess) e = hipMalloc((void **)&pl->tickets, sizeof(unsigned int) * (kRfMaxBatch + 1));
         if (e == hipSuccess) e = hipMemset(pl->tickets, 0, sizeof(unsigned int) * (kRfMaxBatch + 1));
-        if (e == hipSuccess) e = hipMalloc((void **)&pl->xch, sizeof(double) * 3 * 64 * kRfMaxSweep);
-        if (e == hipSuccess) {
-            std::vector<long long> fill((size_t)3 * 64 * kRfMaxSweep, kRfSentinel);
-            e = hipMemcpy(pl->xch, fill.data(), sizeof(long long) * fill.size(), hipMemcpyHostToDevice);
-        }
     }
     if (e == hipSuccess) e = hipHostMalloc((void **)&pl->pflags, 64, hipHostMallocMapped);
     if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&pl->pflags_dev, pl->pflags, 0);
@@ -1327,7 +997,6 @@ void modl_recsys_plan_destroy(modl_recsys_plan *pl) {
     if (pl->pflags) (void)hipHostFree(pl->pflags);
     if (pl->part) (void)hipFree(pl->part);
     if (pl->tickets) (void)hipFree(pl->tickets);
-    if (pl->xch) (void)hipFree(pl->xch);
     if (pl->dbg) (void)hipFree(pl->dbg);
     if (pl->dstage) (void)hipFree(pl->dstage);
     if (pl->ws) (void)hipFree(pl->ws);
@@ -1402,8 +1071,8 @@ int modl_recsys_plan_status(modl_recsys_plan *pl, void *stream) {
 }
 
 /* diagnostics: on = 1 allocates 16 words the last workgroup of every one-launch minibatch stamps with the 100 MHz wall clock
- * ([0] entry, [1] ids, [2] Gram chunk, [3] records summed, [4] factor, [5] ticket, [6] last phase, [7] C_, [8] B_, [9] sweep,
- * [10] end, [11] items, [12] sweep workgroups); h_out[16] (may be NULL) receives the last launch's (synchronises the device) */
+ * ([0] entry, [1] ids, [2] Gram chunk, [3] records summed, [4] factor, [5] ticket, [6] last phase, [7] C_, [10] end = [7],
+ * [11] items); h_out[16] (may be NULL) receives the last launch's (synchronises the device) */
 int modl_recsys_plan_stamps(modl_recsys_plan *pl, int on, unsigned long long *h_out) {
     if (!pl) return MODL_EINVAL;
     if (on && !pl->dbg) {

@@ -218,6 +218,7 @@ def test_debug_switch_numbers_match_the_header(lib):
     for name, dflt in defaults.items():
         assert (lib.modl_debug_set(defs[name], dflt) == 0) == (name not in diag_only), name
     assert lib.modl_debug_set(4, 1) != 0
+    assert lib.modl_debug_set(defs['DEBUG_RECSYS_FUSED'], 2) != 0                # (1 / 0 only: the in-kernel sweep is gone)
     dlib = _lib.load_diag()
     assert dlib.modl_is_diag_build() == 1
     for name, dflt in defaults.items():
