@@ -36,6 +36,11 @@ extern "C" {
 
 #define MODL_ABI_VERSION 5
 
+/* The largest dictionary (n_components, k) any entry point takes.  Up to 1024 atoms the tuned solvers keep a sample's
+ * coefficients in registers; 1024 < k <= 4096 runs the wide route (csrc/cd_wide.hip: the solver's four k-vectors in
+ * LDS, 128 KiB in f64 at 4096; csrc/bcd.hip: dict_update_wide).  A larger k is MODL_EINVAL. */
+#define MODL_MAX_COMPONENTS 4096
+
 #define MODL_OK 0
 #define MODL_EINVAL (-1)   /* bad argument */
 #define MODL_ENOMEM (-2)   /* workspace too small / allocation failed */
@@ -60,6 +65,8 @@ extern "C" {
 #define MODL_FLAG_GEMM_STAMPS 2   /* the head statistics product leaves shader-clock stamps (modl_somf_debug_gemm_stamps) */
 
 int modl_abi_version(void);
+/* MODL_MAX_COMPONENTS, for callers that do not read this header */
+int modl_max_components(void);
 /* number of visible HIP devices (0 without a GPU); never fails */
 int modl_device_count(void);
 const char *modl_error_string(int code);
@@ -147,7 +154,7 @@ int modl_batch_weight(int64_t count, int64_t batch_size, double learning_rate, d
  * d_code[n][k] (rows d_indices[ii] are warm starts and results), d_indices[b]
  * int64 (NULL = 0..b-1).  d_sweeps (optional, int32[b]) receives the number of
  * coordinate-descent sweeps per sample.  d_ws / ws_bytes: scratch, see
- * modl_enet_regression_workspace(). */
+ * modl_enet_regression_workspace().  1 <= k <= MODL_MAX_COMPONENTS. */
 size_t modl_enet_regression_workspace(int dtype, int64_t b, int64_t k, int multi_gram);
 int modl_enet_regression_single_gram_f32(const float *d_G, float *d_Dx, const float *d_X, int64_t ldx,
                                          int64_t p, float *d_code, const int64_t *d_indices, int64_t b,
@@ -283,7 +290,8 @@ int modl_gram_axpby_f32(const float *d_rows, int64_t b, int k, float *d_C, float
 int modl_gram_axpby_f64(const double *d_rows, int64_t b, int k, double *d_C, double beta, double alpha, void *stream);
 /* _update_dict on device-resident state (dict_fact.py:650-715, recsys.py:187-213): block-coordinate
  * update of the rows d_subset[s] (int32, NULL = all rows 0..s-1) of d_Dt[p][k].  d_order / h_order: the
- * atom order on the device (int32) and on the host (int64).  Scratch: modl_dict_update_workspace(). */
+ * atom order on the device (int32) and on the host (int64).  Scratch: modl_dict_update_workspace().
+ * k <= MODL_MAX_COMPONENTS; beyond 1024 atoms every optimizer but sgd runs one launch pair per atom. */
 size_t modl_dict_update_workspace(int dtype, int64_t s_max, int k);
 int modl_dict_update_f32(float *d_Dt, const float *d_Bt, const float *d_C, float *d_comp_norm,
                          const int32_t *d_subset, int64_t s, const int32_t *d_order, const int64_t *h_order, int k,
@@ -303,7 +311,7 @@ int modl_dict_update_f64(double *d_Dt, const double *d_Bt, const double *d_C, do
  * ------------------------------------------------------------------------- */
 typedef struct modl_somf_desc {
     int32_t dtype;          /* MODL_F32 / MODL_F64 */
-    int32_t k;              /* n_components */
+    int32_t k;              /* n_components, 1 .. MODL_MAX_COMPONENTS */
     int64_t p;              /* n_features */
     int64_t n_samples;      /* rows of code_ (and of the averages) */
     int32_t G_agg;          /* MODL_AGG_* (dict_fact.py:132-133) */

@@ -97,6 +97,7 @@ def bind(lib):
         return f
 
     _sig('modl_abi_version', C.c_int)
+    _sig('modl_max_components', C.c_int)
     _sig('modl_device_count', C.c_int)
     _sig('modl_error_string', C.c_char_p, C.c_int)
     _sig('modl_debug_set', C.c_int, C.c_int, _i64)

@@ -2651,6 +2651,80 @@ __global__ __launch_bounds__(256) void sgd_project_kernel(T *Dnew, T *Dt, const 
     if (threadIdx.x == 0) comp_norm[j] = (T)(radius - nrm);
 }
 
+// ------------------------------------------------- wide dictionaries (1024 < k <= MODL_MAX_COMPONENTS)
+// The variational loop of dict_fact.py:672-694 one atom at a time, in the host-drawn order: a gradient-row launch over the
+// s sampled features (C's row j in LDS, a wavefront per feature: Dt is [p][k], so the k-long dot of a feature is
+// contiguous), then atom_project_wide_kernel (old-norm partials -> radius, Michelot, write-back).  Every constraint kind: l2,
+// l1 / elastic-net, positive.  Same arithmetic as atom_grad_kernel (f64 dot, f64 update), any k.
+template <typename T>
+__global__ __launch_bounds__(256) void atom_grad_wide_kernel(const T *Dt, const T *Bt, const T *C, const int32_t *subset,
+                                                             int64_t s, int k, int j, int pos, double rho, T *u,
+                                                             double *partial_old) {
+    extern __shared__ __align__(16) unsigned char grad_wide_smem[];
+    T *cj = reinterpret_cast<T *>(grad_wide_smem);                    // row j == column j of C
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    for (int m = threadIdx.x; m < k; m += 256) cj[m] = C[(int64_t)j * k + m];
+    __syncthreads();
+    const T Cjj = cj[j];
+    const bool frozen = !(Cjj > (T)1e-20);
+    double old = 0;
+    for (int64_t f = (int64_t)blockIdx.x * 4 + wid; f < s; f += (int64_t)gridDim.x * 4) {
+        const T *row = Dt + sub_row(subset, f) * k;
+        double dot = 0;
+        for (int m = lane; m < k; m += 64) dot += (double)row[m] * (double)cj[m];
+        dot = wave_sum(dot);
+        if (lane == 0) {
+            const T dj = row[j];
+            T val = dj;
+            if (!frozen) val = (T)((((double)Bt[sub_row(subset, f) * k + j] - dot) + (double)Cjj * (double)dj) / (double)Cjj);
+            if (pos && val < (T)0) val = 0;            // dict_fact.py:684-685
+            u[f] = val;
+            const double a = fabs((double)dj);
+            old += a * (rho + (1.0 - rho) * a);
+        }
+    }
+    old = block_sum(old, red);
+    if (threadIdx.x == 0) partial_old[blockIdx.x] = old;
+}
+
+// atom_project_kernel on 256 threads: the vector in registers up to kProjEpt * 256 sampled features (1024 threads would
+// leave the register-resident projection too few registers), beyond that the passes scan it from L2
+template <typename T>
+__global__ __launch_bounds__(256) void atom_project_wide_kernel(T *u, const double *partial_old, int nparts, T *Dt,
+                                                                const int32_t *subset, int64_t s, int k, int j,
+                                                                double rho, T *comp_norm) {
+    __shared__ double red[32];
+    atom_project<T>(u, nullptr, partial_old, nparts, Dt, subset, s, k, j, rho, comp_norm, red);
+}
+
+template <typename T>
+int dict_update_wide(hipStream_t stream, const DictUpdateArgs<T> &a, int *launches) {
+    const int k = a.k;
+    const int64_t s = a.s;
+    if (!a.h_order) return MODL_EINVAL;
+    const DuLayout L = du_layout(sizeof(T), s, k);
+    if (L.total > a.ws_bytes) return MODL_ENOMEM;
+    for (int t = 0; t < k; ++t)                                      // (checked before the first launch)
+        if (a.h_order[t] < 0 || a.h_order[t] >= k) return MODL_EINVAL;
+    char *ws = static_cast<char *>(a.ws);
+    T *u = reinterpret_cast<T *>(ws + L.off_u);
+    double *pold = reinterpret_cast<double *>(ws + L.off_pold);
+    const int nwg = (int)std::min<int64_t>(std::min<int64_t>(cdiv(s, 4), 512), L.nwg_grad);
+    const size_t lds = sizeof(T) * (size_t)k;                        // <= 32 KiB
+    for (int t = 0; t < k; ++t) {
+        const int j = (int)a.h_order[t];
+        hipLaunchKernelGGL((atom_grad_wide_kernel<T>), dim3(nwg), dim3(256), lds, stream, a.Dt, a.Bt, a.C, a.subset, s, k, j,
+                           a.comp_pos, a.comp_l1_ratio, u, pold);
+        MODL_LAUNCH_CHECK();
+        hipLaunchKernelGGL((atom_project_wide_kernel<T>), dim3(1), dim3(256), 0, stream, u, (const double *)pold, nwg, a.Dt,
+                           a.subset, s, k, j, a.comp_l1_ratio, a.comp_norm);
+        MODL_LAUNCH_CHECK();
+    }
+    if (launches) *launches += 2 * k;
+    return MODL_OK;
+}
+
 // ---------------------------------------------------------------------- driver
 template <typename T> int dict_update_generic(hipStream_t stream, const DictUpdateArgs<T> &a, int *launches);
 
@@ -2659,7 +2733,8 @@ int dict_update(hipStream_t stream, const DictUpdateArgs<T> &a, int *launches) {
     const int k = a.k;
     const int64_t s = a.s;
     if (s <= 0 || k <= 0) return MODL_OK;
-    if (k > 1024) return MODL_EINVAL;
+    if (k > MODL_MAX_COMPONENTS) return MODL_EINVAL;
+    if (k > 1024 && a.optimizer != MODL_OPT_SGD) return dict_update_wide<T>(stream, a, launches);   // (the sgd path takes any k)
     const DuLayout L = du_layout(sizeof(T), s, k);
     if (L.total > a.ws_bytes) return MODL_ENOMEM;
     char *ws = static_cast<char *>(a.ws);
@@ -2988,7 +3063,8 @@ int dict_update_generic(hipStream_t stream, const DictUpdateArgs<T> &a, int *lau
     const int k = a.k;
     const int64_t s = a.s;
     if (s <= 0 || k <= 0) return MODL_OK;
-    if (k > 1024) return MODL_EINVAL;
+    if (k > MODL_MAX_COMPONENTS) return MODL_EINVAL;
+    if (k > 1024) return dict_update_wide<T>(stream, a, launches);
     const DuLayout L = du_layout(sizeof(T), s, k);
     if (L.total > a.ws_bytes) return MODL_ENOMEM;
     char *ws = static_cast<char *>(a.ws);

@@ -29,6 +29,9 @@ struct CdArgs {
                            // (measured at k = 256: a sparse step costs 0.23 us, a dense sweep 14.3 us (f32) / 18.9 us (f64))
 };
 template <typename T> int launch_cd(hipStream_t stream, const CdArgs<T> &a);
+// cd_wide.hip: 1024 < k <= MODL_MAX_COMPONENTS, one workgroup per sample, the k-vectors in LDS; any Gram layout (shared or
+// per sample, any row stride ldg, any alignment)
+template <typename T> int launch_cd_wide(hipStream_t stream, const CdArgs<T> &a);
 // cd_split.hip: the same solver with the chain and the k-wide update on two wavefronts (shared Gram, 64 < k <= 512)
 template <typename T> bool cd_split_applies(const CdArgs<T> &a);
 template <typename T> int launch_cd_split(hipStream_t stream, const CdArgs<T> &a);

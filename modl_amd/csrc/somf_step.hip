@@ -360,7 +360,7 @@ size_t params_layout(modl_somf_plan *pl) {
 int validate_desc(const modl_somf_desc *d) {
     if (!d) return MODL_EINVAL;
     if (d->dtype != MODL_F32 && d->dtype != MODL_F64) return MODL_EINVAL;
-    if (d->k <= 0 || d->k > 1024 || d->p <= 0 || d->p > 0x7fffffff || d->n_samples < 0 || d->max_batch <= 0)
+    if (d->k <= 0 || d->k > MODL_MAX_COMPONENTS || d->p <= 0 || d->p > 0x7fffffff || d->n_samples < 0 || d->max_batch <= 0)
         return MODL_EINVAL;
     if (d->G_agg < 0 || d->G_agg > 2 || d->Dx_agg < 0 || d->Dx_agg > 2) return MODL_EINVAL;
     if (d->optimizer != MODL_OPT_VARIATIONAL && d->optimizer != MODL_OPT_SGD) return MODL_EINVAL;
@@ -578,7 +578,7 @@ int solve_codes(modl_somf_plan *pl, hipStream_t st, const T *G, int64_t g_stride
     a.idx = d_idx;
     a.code2 = scatter_dst; a.idx2 = scatter_idx;
     a.g_pad_rows = (G == reinterpret_cast<const T *>(pl->dws + pl->off_G)) ? 16 : 0;
-    if (!g_stride && pl->ld_gpad) {              // any k on the vectorised kernel (cd_solver.hip: cd_padded_ld)
+    if (!g_stride && pl->ld_gpad && k <= 1024) { // any k on the vectorised kernel (cd_solver.hip: cd_padded_ld)
         T *Gp = reinterpret_cast<T *>(pl->dws + pl->off_Gpad);
         MODL_TRY(launch_cd_pad_gram<T>(st, G, k, Gp, pl->ld_gpad));
         ++*nl;
@@ -588,6 +588,21 @@ int solve_codes(modl_somf_plan *pl, hipStream_t st, const T *G, int64_t g_stride
     a.alpha = (T)((T)d.code_alpha * (T)d.code_l1_ratio);
     a.beta = (T)((double)(T)d.code_alpha * (1.0 - (double)(T)d.code_l1_ratio));
     a.tol = (T)d.tol; a.max_iter = d.max_iter; a.positive = d.code_pos;
+    if (k > 1024) {                              // wide dictionaries, shared or per-sample Gram as stored (cd_wide.hip)
+        a.G = G; a.ldg = 0; a.g_pad_rows = 0;
+        if (!g_stride) {                         // H0 = code G on the matrix cores: k rows per sample, not streamed by one CU
+            Operand A, B;
+            A.ptr = code; A.si = k; A.sk = 1; A.gi = gather64(d_idx);
+            B.ptr = G; B.si = k; B.sk = 1;
+            EpiStore<T> epi{H0buf, k, (T)1};
+            SplitWs none;
+            MODL_TRY((launch_gemm<T, EpiStore<T>>(st, A, B, b, k, k, epi, none, nl, 512, 1)));
+            a.H0 = H0buf;
+        }
+        MODL_TRY(launch_cd_wide<T>(st, a));
+        ++*nl;
+        return MODL_OK;
+    }
     if (g_stride && k >= 32 && (cd_split_enabled() || !cd_one_wave_covers(k)) && !cd_split_applies<T>(a)) {
         // a Gram matrix per sample of a size the four-wavefront solver does not take as stored: zero-padded copies,
         // a slice of the minibatch at a time (cd_solver.hip: launch_cd_per_sample)
@@ -1030,7 +1045,7 @@ template <typename T>
 int enet_regression_abi(const T *G, int64_t g_stride, T *Dx, const T *X, int64_t ldx, int64_t p, T *code,
                         const int64_t *d_indices, int64_t b, int64_t k, T l1_ratio, T alpha, int positive, T tol,
                         int max_iter, int32_t *d_sweeps, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!G || !Dx || !X || !code || b < 0 || k <= 0 || k > 1024 || p < 0 || ldx < p) return MODL_EINVAL;
+    if (!G || !Dx || !X || !code || b < 0 || k <= 0 || k > MODL_MAX_COMPONENTS || p < 0 || ldx < p) return MODL_EINVAL;
     if (!(l1_ratio >= 0 && l1_ratio <= 1)) return MODL_EINVAL;
     if (b == 0) return MODL_OK;
     const size_t need = modl_enet_regression_workspace(DType<T>::id, b, k, g_stride != 0);
@@ -1081,6 +1096,7 @@ int enet_regression_abi(const T *G, int64_t g_stride, T *Dx, const T *X, int64_t
     a.alpha = alpha * l1_ratio;
     a.beta = (T)((double)alpha * (1.0 - (double)l1_ratio));
     a.tol = tol; a.max_iter = max_iter; a.positive = positive;
+    if (k > 1024) return launch_cd_wide<T>(st, a);   // any Gram as stored, H0 from the product above (cd_wide.hip)
     if (g_stride && k >= 32 && k <= 1024 && (cd_split_enabled() || !cd_one_wave_covers((int)k)) && !cd_split_applies<T>(a)) {  // one Gram matrix per sample, any k: zero-padded slots
         const size_t slot_bytes = cd_per_sample_scratch_bytes(sizeof(T), b, (int)k);   // (at the end of the workspace)
         T *slots = reinterpret_cast<T *>(w + need - align_up(slot_bytes, 256));
@@ -1164,7 +1180,7 @@ int modl_somf_plan_create(const modl_somf_desc *desc, modl_somf_plan **out) {
     pl->off_Dx = take(t * b * k);
     pl->off_H0 = take(t * b * k);
     pl->off_G = take(t * (k + 16) * k);        // 16 readable rows behind the Gram: the solver's row prefetch runs unclamped
-    if (desc->code_l1_ratio != 0.0 && cd_padded_ld(desc->k) != desc->k) {
+    if (desc->code_l1_ratio != 0.0 && desc->k <= 1024 && cd_padded_ld(desc->k) != desc->k) {
         pl->ld_gpad = cd_padded_ld(desc->k);
         pl->off_Gpad = take(t * ((size_t)pl->ld_gpad + 16) * pl->ld_gpad);
     }

@@ -71,9 +71,10 @@ class HipBackend:
 
     # -- allocation ---------------------------------------------------------
     def allocate(self, desc_kwargs, n_samples, p, k, dtype):
-        if k > 1024:
-            raise ValueError('modl_amd supports n_components <= 1024 (the code solvers keep a sample\'s %d coefficients in '
-                             'the registers of one wavefront); got %d' % (1024, k))
+        kmax = lib.modl_max_components()
+        if k > kmax:
+            raise ValueError('modl_amd supports n_components <= %d (beyond 1024 the code solver keeps four k-vectors per '
+                             'sample in the 160 KiB of LDS of a compute unit); got %d' % (kmax, k))
         self.dtype = np.dtype(dtype)
         self.k, self.p, self.n = k, p, n_samples
         td, dev = torch_dtype(dtype), self.device
@@ -1000,6 +1001,10 @@ class DictFact(CodingMixin, BaseEstimator):
             self.G_agg = 'full'
             self.Dx_agg = 'full'
         k = self.n_components
+        if k > 1024 and (_dist() is not None or getattr(self, '_force_reduce', False)):
+            # the wide route (k > 1024) runs on one GPU; the two-phase exchange of several ranks is not validated there
+            raise ValueError('n_components > 1024 is supported on a single GPU only (got %d with %d ranks)'
+                             % (k, self._world()))
         self._backend = be = self._make_backend()
         be.allocate(self._plan_kwargs(self.batch_size), n_samples, n_features, k, dtype)
 
