@@ -2,6 +2,7 @@
 (BASELINE.json), on N MI355X of one node.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full      (and everything else it measures, see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --steps K --warmup W      (no launcher: starts its N ranks itself, see self_launch)
@@ -20,11 +21,17 @@ minibatch of N*256 rows and the head of the statistics is all-reduced over RCCL
 before each dictionary update (weak scaling).
 
 Rank 0 prints ONE JSON line.  `value` is the driver-timed run (W warm-up steps
-from a fresh dictionary, then exactly K steps).  `steady_state` holds, from the
-same process, >= 2000 fresh-row steps after a 500-step burn-in for reduction = 10
-AND reduction = 1 (OMF), each with its `cd_sweeps_mean`.  The `cpu_baseline` leg
-times the CPU oracle (oracle/somf_oracle.py: the reference's algorithm and
-operation order) on a bounded prefix of the same rows on the host cores.
+from a fresh dictionary, then exactly K steps).  A plain run does only what that
+figure needs: set up, warm up, time the K steps (with the roofline's section
+events on one minibatch in four), write --dump-outputs, print the line.
+
+`--full` adds, from the same process and after the line's own timed region: an
+untimed pass of 50 minibatches with every section timed (`sections`);
+`steady_state`, >= 2000 fresh-row steps after a 500-step burn-in for reduction
+= 10 AND reduction = 1 (OMF), each with its `cd_sweeps_mean`; and, with one rank,
+the `cpu_baseline` leg, which times the CPU oracle (oracle/somf_oracle.py: the
+reference's algorithm and operation order) on a bounded prefix of the same rows
+on the host cores, with the `parity` block and the sweep-flip census next to it.
 """
 import argparse
 import json
@@ -274,14 +281,17 @@ def timed(run, steps, world):
 ROOF_SECTIONS = ('dict_update', 'code_solve')      # the two sections that can dominate the step: both are timed
 
 
-def run_gpu(args, reduction, steps, warmup, rank, world, device, breakdown=True):
+def run_gpu(args, reduction, steps, warmup, rank, world, device, breakdown=True, sections=True):
     """Warm-up, the timed region (HIP events around `dict_update` and `code_solve` only, on one minibatch in four:
-    every timed section costs two event records, i.e. a stream bubble of a few microseconds each), then an untimed
-    pass with all sections timed for the breakdown.  The roofline line is the section with the larger time OVER THE
-    TIMED REGION (not over a warm-up minibatch: the line means the same thing whatever --warmup is)."""
+    every timed section costs two event records, i.e. a stream bubble of a few microseconds each), then, with
+    `sections` (--full), an untimed pass with all sections timed for the breakdown.  The roofline line is the section
+    with the larger time OVER THE TIMED REGION (not over a warm-up minibatch: the line means the same thing whatever
+    --warmup is)."""
     import torch
     import torch.distributed as dist
     extra = min(steps, 50) if breakdown else 0
+    # the stream is sized for the breakdown pass even when it does not run: the timed steps then read the same
+    # resident chunks with and without --full
     run = Run(args, reduction, rank, world, device, steps + warmup + extra)
     be = run.be
     run.fit(warmup)
@@ -309,7 +319,7 @@ def run_gpu(args, reduction, steps, warmup, rank, world, device, breakdown=True)
         dump_outputs(run, args.dump_outputs, rank)
     lsw = be.last_sweeps()
     res['sweeps'], res['sweeps_max'] = float(lsw.mean()), int(lsw.max())
-    if extra:
+    if extra and sections:
         be.prof_enable(True)
         be.prof_reset()
         run.fit(extra)
@@ -716,10 +726,15 @@ def main():
     ap.add_argument('--features', type=int, default=10000,
                     help='p of the synthetic stream (10000: the metric\'s workload M1; 200000 with --reduction 12: the per-GPU '
                          'shape of BASELINE config 5, the HCP-shaped stream - same line format, config.workload names it)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what the headline figure does not need: the untimed section '
+                         'breakdown, the steady_state records and, with one rank, the CPU baseline, the parity block and the '
+                         'sweep-flip census')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline, parity and flip-census legs')
     ap.add_argument('--no-breakdown', action='store_true', help='no HIP events at all on the stream (for kernel-trace timelines)')
     ap.add_argument('--steady-steps', type=int, default=None,
-                    help='fresh-row steps of each steady_state record (0: skip; default 2000 at the metric\'s shape, 0 otherwise)')
+                    help='fresh-row steps of each steady_state record of --full (0: skip; default 2000 at the metric\'s shape, '
+                         '0 otherwise)')
     ap.add_argument('--steady-burn-in', type=int, default=500)
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL; gloo only to test the N > 1 path)')
     ap.add_argument('--force-reduce', action='store_true',
@@ -731,7 +746,7 @@ def main():
                     help='N > 1: dist.all_reduce of the head between two library calls per minibatch instead of the '
                          'library\'s own RCCL communicator')
     ap.add_argument('--flip-minibatches', default='200,50', metavar='N10,N1',
-                    help='minibatches of the sweep-flip census at reduction 10 and 1 (parity.flip_rate; one GPU, with the CPU baseline; '
+                    help='minibatches of the sweep-flip census at reduction 10 and 1 (parity.flip_rate; --full on one GPU, with the CPU baseline; '
                          '0,0: off).  Default: 51 200 and 12 800 samples, ~1.5 min of CPU oracle on the box; '
                          'tests/test_gpu_step.py::test_sweep_flip_rate runs 400,200 and profiles/r06_flip_census.json 800,800')
     ap.add_argument('--share-gpu', action='store_true', help='testing only: every rank uses cuda:0 (needs --backend gloo)')
@@ -743,6 +758,8 @@ def main():
     args = ap.parse_args()
     if args.steps is not None and args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.steady_steps and not args.full:
+        ap.error('--steady-steps %d: the steady_state records are part of --full' % args.steady_steps)
     global P_FEAT, CHUNK, BLOCK
     if args.features != P_FEAT:
         # another feature count (C5: p = 200 000): chunks of at most ~8 GB (a power of two of rows, whole minibatches),
@@ -751,7 +768,7 @@ def main():
         CHUNK = max(8 * BATCH, min(65536, 1 << int(np.log2(8e9 / (4.0 * P_FEAT)))))
         BLOCK = CHUNK // 8
     if args.steady_steps is None:
-        args.steady_steps = 2000 if P_FEAT == 10000 else 0
+        args.steady_steps = 2000 if P_FEAT == 10000 and args.full else 0
     if args.steps is None:
         args.steps = 2000 if P_FEAT == 10000 else 300
     if args.warmup is None:
@@ -785,7 +802,8 @@ def main():
         from modl_amd._lib import lib as _l, check as _c
         what, value = item.split('=')
         _c(_l.modl_debug_set(int(what), int(value)), 'modl_debug_set')
-    res = run_gpu(args, args.reduction, args.steps, args.warmup, rank, world, device, breakdown=not args.no_breakdown)
+    res = run_gpu(args, args.reduction, args.steps, args.warmup, rank, world, device, breakdown=not args.no_breakdown,
+                  sections=args.full)
     steady = []
     if args.steady_steps > 0:
         for r in ((10.0, 1.0) if P_FEAT == 10000 else (args.reduction,)):
@@ -846,7 +864,7 @@ def main():
                    host_enqueue_ms_per_step=res['enqueue_ms_per_step'],
                    rows=dict(fitted=res['rows_fitted'], generated=res['rows_generated']),
                    steady_state=steady)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_cpu = max(2, min(40, int(2e9 // (4 * P_FEAT * BATCH)))) * BATCH     # (host copy of the prefix <= 2 GB)
             Xh = M1Stream(P_FEAT, 1234, device, rank=0).rows(0, n_cpu).cpu().numpy()
             out['cpu_baseline'], st_ref, done = cpu_baseline(Xh, args.reduction)

@@ -1088,6 +1088,39 @@ def test_bench_launches_its_own_ranks():
     assert rec['config']['global_batch'] == 512 and rec['value'] > 0
 
 
+def test_bench_plain_and_full():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` fits the warm-up and the timed minibatches and nothing else;
+    `--full` adds the untimed section breakdown, both steady_state records and the CPU baseline with its parity block
+    (small sizes here, no flip census)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from .conftest import ROOT
+    env = {k_: v for k_, v in os.environ.items() if k_ not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '8', '--warmup', '4']
+    recs = []
+    for extra in ([], ['--full', '--steady-steps', '8', '--steady-burn-in', '4', '--flip-minibatches', '0,0']):
+        r = subprocess.run(base + extra, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        recs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    plain, full = recs
+    for rec in recs:
+        assert rec['steps'] == 8 and rec['warmup'] == 4 and rec['value'] > 0 and rec['ms_per_step'] > 0
+        assert rec['finite'] is True and rec['roofline'] is not None
+        assert rec['rows']['generated'] == plain['rows']['generated']
+    assert plain['rows']['fitted'] == 12 * 256
+    assert plain['sections'] == {} and plain['steady_state'] == []
+    assert plain['cpu_baseline'] is None and plain['parity'] is None
+    assert full['rows']['fitted'] == 20 * 256
+    assert 'dict_update' in full['sections'] and 'code_solve' in full['sections']
+    assert [s['reduction'] for s in full['steady_state']] == [10.0, 1.0]
+    assert all(s['steps'] == 8 and s['value'] > 0 for s in full['steady_state'])
+    assert full['cpu_baseline']['value'] > 0
+    assert full['parity']['steps'] >= 1 and full['parity']['flip_rate'] == []
+    assert 'parity' in full['steady_state'][1]
+
+
 def test_c5_shape_step_properties(DictFact):
     """BASELINE config 5's per-GPU shape (p = 200 000 features, k = 256, b = 256, reduction = 12, f32) through both
     the single-GPU step and the two-phase (multi-GPU) step: finite, only sampled columns move, atoms stay in the l2

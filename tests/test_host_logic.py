@@ -181,6 +181,18 @@ def test_bench_self_launch_relays_failure_without_hanging():
     assert 'must be launched with' not in r.stderr
 
 
+def test_bench_steady_state_needs_full():
+    """The steady_state records are part of `bench.py --full`: asking a plain run for them is an argument error, raised
+    before anything touches the GPU."""
+    import subprocess
+    import sys
+    from .conftest import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--steady-steps', '5'],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2, r.stderr[-2000:]
+    assert '--full' in r.stderr and 'needs a GPU' not in r.stderr, r.stderr[-2000:]
+
+
 def _rank_main_pickle(rank, world, port, kw, X_parts, out):
     import pickle
     import warnings
