@@ -291,7 +291,11 @@ int modl_gram_axpby_f64(const double *d_rows, int64_t b, int k, double *d_C, dou
 /* _update_dict on device-resident state (dict_fact.py:650-715, recsys.py:187-213): block-coordinate
  * update of the rows d_subset[s] (int32, NULL = all rows 0..s-1) of d_Dt[p][k].  d_order / h_order: the
  * atom order on the device (int32) and on the host (int64).  Scratch: modl_dict_update_workspace().
- * k <= MODL_MAX_COMPONENTS; beyond 1024 atoms every optimizer but sgd runs one launch pair per atom. */
+ * k <= MODL_MAX_COMPONENTS; beyond 1024 atoms every optimizer but sgd runs one launch pair per atom.
+ * This direct call carries no plan: where the f32 update runs as one persistent launch (MODL_DEBUG_BCD_PERSIST) and that
+ * launch cannot complete because its workgroups are not all resident (another process holds compute units), the call cannot
+ * report it - it returns MODL_OK when the launch was queued.  Only the plan-based entry points (modl_somf_partial_fit*)
+ * read the launch's flags back, recover, and return MODL_ETIMEOUT for an incomplete update. */
 size_t modl_dict_update_workspace(int dtype, int64_t s_max, int k);
 int modl_dict_update_f32(float *d_Dt, const float *d_Bt, const float *d_C, float *d_comp_norm,
                          const int32_t *d_subset, int64_t s, const int32_t *d_order, const int64_t *h_order, int k,

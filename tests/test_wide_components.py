@@ -110,39 +110,8 @@ def test_ridge_codes_k2048(gpu, oracle, kind):
 
 
 # ---- the dictionary update through modl_dict_update_* ------------------------------------------------------------
-def _dict_update_case(oracle, k, s, dt, optimizer='variational', comp_l1_ratio=0.0, comp_pos=False, seed=0):
-    import ctypes as C
-    import torch
-    from modl_amd._lib import lib, check
-    from modl_amd.device import dtype_id, sfx, ptr
-    p = s + 200
-    rs = np.random.RandomState(seed)
-    kw = dict(n_components=k, batch_size=16, reduction=2, code_alpha=1.0, learning_rate=0.92, random_state=0,
-              optimizer=optimizer, comp_l1_ratio=comp_l1_ratio, comp_pos=comp_pos)
-    pr = oracle.SomfParams(**kw)
-    st = oracle.prepare(pr, n_samples=8, X=_atoms(k, p, seed, dt))
-    A = rs.randn(k + 64, k) * (rs.rand(k + 64, k) < 0.1)
-    st.C = np.ascontiguousarray((A.T.dot(A) / 64 + np.diag(rs.rand(k) * (rs.rand(k) < 0.97))).astype(dt))
-    st.B = np.ascontiguousarray((st.C.dot(st.D) * 0.9 + 0.01 * rs.randn(k, p)).astype(dt))
-    subset = np.sort(rs.choice(p, s, replace=False)).astype(np.int64)
-    order = rs.permutation(k).astype(np.int64)
-    w = 0.3
-    dev = torch.device('cuda')
-    Dt = torch.from_numpy(np.ascontiguousarray(st.D.T)).to(dev)
-    Bt = torch.from_numpy(np.ascontiguousarray(st.B.T)).to(dev)
-    Cd = torch.from_numpy(st.C).to(dev)
-    cn = torch.from_numpy(st.comp_norm.copy()).to(dev)
-    dsub = torch.from_numpy(subset.astype(np.int32)).to(dev)
-    dord = torch.from_numpy(order.astype(np.int32)).to(dev)
-    nbytes = lib.modl_dict_update_workspace(dtype_id(dt), s, k)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    f = getattr(lib, 'modl_dict_update_' + sfx(dt))
-    check(f(ptr(Dt), ptr(Bt), ptr(Cd), ptr(cn), ptr(dsub), s, ptr(dord), order.ctypes.data_as(C.POINTER(C.c_int64)), k,
-            1 if optimizer == 'sgd' else 0, int(comp_pos), comp_l1_ratio, w, pr.step_size, ptr(ws), nbytes, None),
-          'modl_dict_update')
-    torch.cuda.synchronize()
-    oracle.update_dict(st, pr, subset, w, order=order)
-    return Dt.cpu().numpy().T, cn.cpu().numpy(), st.D, st.comp_norm
+# (the case builder and the call live in test_dict_update_routes.py, which runs them over every route up to 1024 atoms)
+from .test_dict_update_routes import dict_update_case as _dict_update_case  # noqa: E402
 
 
 UPDATE_CASES = [dict(), dict(comp_l1_ratio=1.0), dict(comp_l1_ratio=0.5), dict(comp_l1_ratio=1.0, comp_pos=True),
