@@ -514,6 +514,46 @@ int modl_image_patches_f32(const float *d_image, int64_t H, int64_t W, int64_t C
                            int y, int z, int with_mean, int with_std, float *d_out, int64_t ldo, void *stream);
 int modl_image_patches_f64(const double *d_image, int64_t H, int64_t W, int64_t C, const int64_t *d_idx3, int64_t n, int x,
                            int y, int z, int with_mean, int with_std, double *d_out, int64_t ldo, void *stream);
+/* Reconstruction of an image from the codes of its patches (no counterpart in the reference): encode every window of a
+ * regular PATCH GRID, decode it, undo the per-patch scaling, average the overlapping windows - all on the device.
+ * The grid: along an axis of length L with patch length x and stride s the origins are 0, s, 2 s, ... <= L - x, plus
+ * L - x itself when it is not already the last one (the border is always covered): ceil((L - x) / s) + 1 origins,
+ * origin(r) = min(r s, L - x).  A patch spans all channels; patches are numbered row-major over (grid row, grid
+ * column).  A pass is the contiguous range of grid rows [row0, row0 + nrows): nrows * grid_cols patches.  Every call
+ * below checks 1 <= si <= x <= H, 1 <= sj <= y <= W, 1 <= C <= 1024, 0 <= row0, row0 + nrows <= grid_rows, its
+ * pointers and leading dimensions before any device work (MODL_EINVAL); none needs scratch, none uses atomics: the
+ * results are bit-identical from run to run.
+ * modl_image_grid_shape: the number of grid rows and columns.  Host. */
+int modl_image_grid_shape(int64_t H, int64_t W, int64_t x, int64_t y, int64_t si, int64_t sj, int64_t *grid_rows,
+                          int64_t *grid_cols);
+/* modl_image_patches_* on the patches of a pass, origins computed from the grid (no index array): the rows equal those of
+ * modl_image_patches_* at the same origins bit for bit.  Also kept, per patch and channel: d_mean[nrows*grid_cols][C]
+ * (0 without with_mean) and d_den[..][C], the divisor that was applied (1 where none was). */
+int modl_image_grid_patches_f32(const float *d_image, int64_t H, int64_t W, int64_t C, int x, int y, int si, int sj,
+                                int64_t row0, int64_t nrows, int with_mean, int with_std, float *d_out, int64_t ldo,
+                                float *d_mean, float *d_den, void *stream);
+int modl_image_grid_patches_f64(const double *d_image, int64_t H, int64_t W, int64_t C, int x, int y, int si, int sj,
+                                int64_t row0, int64_t nrows, int with_mean, int with_std, double *d_out, int64_t ldo,
+                                double *d_mean, double *d_den, void *stream);
+/* d_out[m][e] = (d_code d_Dt^T)[m][e] * d_den[m][e % C] + d_mean[m][e % C]: the patches of the codes d_code[n][k] on the
+ * dictionary d_Dt[P][k] (feature-major, as the plan holds it), put back on the image's scale (P a multiple of C).
+ * d_mean and d_den both NULL: the plain product (CodingMixin.inverse_transform; C is then ignored).  Any k >= 1. */
+int modl_image_decode_f32(const float *d_code, int64_t n, int k, const float *d_Dt, int64_t P, int C, const float *d_mean,
+                          const float *d_den, float *d_out, int64_t ldo, void *stream);
+int modl_image_decode_f64(const double *d_code, int64_t n, int k, const double *d_Dt, int64_t P, int C,
+                          const double *d_mean, const double *d_den, double *d_out, int64_t ldo, void *stream);
+/* d_acc[H][W][C] (f64, zeroed by the caller before the first pass) += the flattened patches d_patches[nrows*grid_cols][ldp]
+ * of a pass, each at its window.  A gather: every accumulator adds its covering patches one at a time in grid order, so
+ * the sums do not depend on how the grid rows are cut into passes (passes in increasing row0), bit for bit. */
+int modl_image_overlap_add_f32(const float *d_patches, int64_t ldp, int64_t H, int64_t W, int64_t C, int x, int y, int si,
+                               int sj, int64_t row0, int64_t nrows, double *d_acc, void *stream);
+int modl_image_overlap_add_f64(const double *d_patches, int64_t ldp, int64_t H, int64_t W, int64_t C, int x, int y, int si,
+                               int sj, int64_t row0, int64_t nrows, double *d_acc, void *stream);
+/* d_image_out[H][W][C] = d_acc / (number of grid patches that cover the pixel) */
+int modl_image_overlap_finish_f32(const double *d_acc, int64_t H, int64_t W, int64_t C, int x, int y, int si, int sj,
+                                  float *d_image_out, void *stream);
+int modl_image_overlap_finish_f64(const double *d_acc, int64_t H, int64_t W, int64_t C, int x, int y, int si, int sj,
+                                  double *d_image_out, void *stream);
 /* The three sums of CodingMixin.score (dict_fact.py:108-114) on device-resident operands:
  * d_out3 = [ sum (X - code D)^2, sum |code|, sum code^2 ] (f64 accumulation, fixed order: run-to-run reproducible).
  * d_X[n][ldx], d_Dt[p][k], d_code[n][k]; scratch of modl_objective_workspace() bytes (any smaller size that holds at

@@ -7,6 +7,8 @@
 //   fill / clean_mask     : modl/input_data/image_fast.pyx:12-74 (host, integer work);
 //   objective terms       : modl/decomposition/dict_fact.py:94-114 (CodingMixin.score) on device-resident X, codes
 //                           and dictionary, so that scoring callbacks need no D2H copy of the dictionary.
+// Beyond the reference (it has no reconstruction): the way back from codes to an image on a regular PATCH GRID -
+// grid patches that keep their scaling, decode with unscale, overlap-add, finish (see "reconstruction" below).
 #include "gemm.hpp"
 #include "kernels.hpp"
 #include <algorithm>
@@ -21,18 +23,13 @@ namespace modl {
 // The image (a few MB) is L2-resident; the row is written once, coalesced, in flat element order.
 constexpr int kPatchMaxChannels = 1024;
 
+// The row of one patch by one wavefront (the body of both patch kernels, so that their rows agree bit for bit): `base`
+// = the window's first element, z channels from there.  s_mean / s_den: this wavefront's z slots of LDS.
 template <typename T>
-__global__ __launch_bounds__(256) void image_patches_kernel(const T *__restrict__ img, int64_t W, int64_t C,
-                                                            const int64_t *__restrict__ idx3, int64_t n, int x, int y,
-                                                            int z, int with_mean, int with_std, T sqrt_z,
-                                                            T *__restrict__ out, int64_t ldo) {
-    __shared__ T s_mean[4][kPatchMaxChannels];
-    __shared__ T s_den[4][kPatchMaxChannels];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int64_t row = (int64_t)blockIdx.x * 4 + wid;
-    if (row >= n) return;                                     // wave-uniform; no block barrier below
-    const int64_t i0 = idx3[row * 3 + 0], j0 = idx3[row * 3 + 1], c0 = idx3[row * 3 + 2];
-    const T *base = img + (i0 * W + j0) * C + c0;
+__device__ __forceinline__ void patch_row(const T *__restrict__ base, int64_t W, int64_t C, int x, int y, int z,
+                                          int with_mean, int with_std, T sqrt_z, T *s_mean, T *s_den,
+                                          T *__restrict__ o) {
+    const int lane = threadIdx.x & 63;
     const int xy = x * y;
     if (with_mean || with_std) {
         for (int c = 0; c < z; ++c) {
@@ -53,21 +50,35 @@ __global__ __launch_bounds__(256) void image_patches_kernel(const T *__restrict_
                 if (sd == (T)0) sd = 1;
                 den = sd * sqrt_z;
             }
-            if (lane == 0) { s_mean[wid][c] = mean; s_den[wid][c] = den; }
+            if (lane == 0) { s_mean[c] = mean; s_den[c] = den; }
         }
     }
     __builtin_amdgcn_wave_barrier();                          // LDS operations of one wavefront complete in order
-    T *o = out + row * ldo;
     const int P = xy * z;
     const int yz = y * z;
     for (int e = lane; e < P; e += 64) {
         const int xi = e / yz, rem = e - xi * yz;             // rem = yi * z + c: contiguous in the image row
         const int c = rem % z;
         T v = base[(int64_t)xi * W * C + (int64_t)(rem / z) * C + c];
-        if (with_mean) v -= s_mean[wid][c];
-        if (with_std) v /= s_den[wid][c];
+        if (with_mean) v -= s_mean[c];
+        if (with_std) v /= s_den[c];
         o[e] = v;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void image_patches_kernel(const T *__restrict__ img, int64_t W, int64_t C,
+                                                            const int64_t *__restrict__ idx3, int64_t n, int x, int y,
+                                                            int z, int with_mean, int with_std, T sqrt_z,
+                                                            T *__restrict__ out, int64_t ldo) {
+    __shared__ T s_mean[4][kPatchMaxChannels];
+    __shared__ T s_den[4][kPatchMaxChannels];
+    const int wid = threadIdx.x >> 6;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wid;
+    if (row >= n) return;                                     // wave-uniform; no block barrier below
+    const int64_t i0 = idx3[row * 3 + 0], j0 = idx3[row * 3 + 1], c0 = idx3[row * 3 + 2];
+    patch_row<T>(img + (i0 * W + j0) * C + c0, W, C, x, y, z, with_mean, with_std, sqrt_z, s_mean[wid], s_den[wid],
+                 out + row * ldo);
 }
 
 template <typename T>
@@ -134,6 +145,175 @@ int objective_impl(hipStream_t stream, const T *X, int64_t ldx, int64_t n, int64
     hipLaunchKernelGGL(obj_final_kernel, dim3(1), dim3(256), 0, stream, part, kObjBlocks, out3 + 1, 0);
     hipLaunchKernelGGL((obj_partial_kernel<T, 0>), dim3(kObjBlocks), dim3(256), 0, stream, code, n, (int64_t)k, (int64_t)k, part);
     hipLaunchKernelGGL(obj_final_kernel, dim3(1), dim3(256), 0, stream, part, kObjBlocks, out3 + 2, 0);
+    MODL_LAUNCH_CHECK();
+    return MODL_OK;
+}
+
+// ---- reconstruction -----------------------------------------------------------------------------------------------
+// THE PATCH GRID (stated once, here; modl_hip.h and modl_amd/image.py:grid_origins restate it).  Along an axis of
+// length L with patch length x and stride s (1 <= s <= x <= L) the origins are 0, s, 2 s, ... <= L - x, plus L - x
+// itself when it is not the last of them, so the border is always covered:
+//   count  g = ceil((L - x) / s) + 1,   origin(r) = min(r s, L - x).
+// A patch spans all channels (z = C, c0 = 0); patches are numbered row-major over (grid row, grid column).  A PASS is
+// the contiguous range of grid rows [row0, row0 + nrows); its patch q sits at grid (row0 + q / gcols, q % gcols).
+// Pixel t of the axis is covered by the grid indices [lo, hi]: lo = the first r with r s > t - x, hi = t / s, or the
+// clamped last index g - 1 once t >= L - x (every r <= g - 2 has r s < L - x, so only the last origin is clamped).
+struct GridAxis {
+    int64_t L, g;
+    int x, s;
+    __host__ __device__ __forceinline__ int64_t origin(int64_t r) const { return r * s < L - x ? r * s : L - x; }
+    __host__ __device__ __forceinline__ int64_t lo(int64_t t) const { return t - x + s > 0 ? (t - x + s) / s : 0; }
+    __host__ __device__ __forceinline__ int64_t hi(int64_t t) const { return t >= L - x ? g - 1 : t / s; }
+};
+static inline bool grid_axis(int64_t L, int64_t x, int64_t s, GridAxis *a) {
+    if (x <= 0 || s <= 0 || s > x || x > L || x > INT32_MAX) return false;
+    a->L = L; a->x = (int)x; a->s = (int)s; a->g = cdiv(L - x, s) + 1;
+    return true;
+}
+
+// image_patches_kernel on the grid: one wavefront per patch of the pass, the origin computed, no index array; the
+// statistics that the scaling applied are kept: mean[q][C] and den[q][C] (the divisor actually applied, 1 where none
+// was), so that a decoded patch can be put back on the image's scale.
+template <typename T>
+__global__ __launch_bounds__(256) void image_grid_patches_kernel(const T *__restrict__ img, int64_t C, GridAxis gi,
+                                                                 GridAxis gj, int64_t row0, int64_t n, int with_mean,
+                                                                 int with_std, T sqrt_z, T *__restrict__ out,
+                                                                 int64_t ldo, T *__restrict__ mean,
+                                                                 T *__restrict__ den) {
+    __shared__ T s_mean[4][kPatchMaxChannels];
+    __shared__ T s_den[4][kPatchMaxChannels];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int64_t q = (int64_t)blockIdx.x * 4 + wid;
+    if (q >= n) return;                                       // wave-uniform; no block barrier below
+    const int64_t i0 = gi.origin(row0 + q / gj.g), j0 = gj.origin(q % gj.g);
+    const int z = (int)C;
+    if (!(with_mean || with_std))
+        for (int c = lane; c < z; c += 64) { s_mean[wid][c] = 0; s_den[wid][c] = 1; }
+    patch_row<T>(img + (i0 * gj.L + j0) * C, gj.L, C, gi.x, gj.x, z, with_mean, with_std, sqrt_z, s_mean[wid],
+                 s_den[wid], out + q * ldo);
+    for (int c = lane; c < z; c += 64) { mean[q * C + c] = s_mean[wid][c]; den[q * C + c] = s_den[wid][c]; }
+}
+
+// decode: R[m][e] = (code D)[m][e] * den[m][e % C] + mean[m][e % C]; without mean / den the plain product
+template <typename T> struct EpiUnscale {
+    T *R; int64_t ldr; const T *mean, *den; int C;
+    __device__ __forceinline__ void operator()(int64_t m, int64_t n, T v) const {
+        if (mean) {
+            const int64_t s = m * C + (int)n % C;
+            v = v * den[s] + mean[s];
+        }
+        R[m * ldr + n] = v;
+    }
+};
+
+constexpr int64_t kDecodeChunk = (int64_t)1 << 21;            // rows per product launch: 32 768 row tiles of 64 in gridDim.y
+
+template <typename T>
+int decode_impl(hipStream_t stream, const T *code, int64_t n, int k, const T *Dt, int64_t P, int C, const T *mean,
+                const T *den, T *out, int64_t ldo) {
+    for (int64_t r0 = 0; r0 < n; r0 += kDecodeChunk) {
+        const int64_t rows = n - r0 < kDecodeChunk ? n - r0 : kDecodeChunk;
+        Operand A, B;
+        A.ptr = code + r0 * k; A.si = k; A.sk = 1;
+        B.ptr = Dt; B.si = k; B.sk = 1;
+        EpiUnscale<T> epi{out + r0 * ldo, ldo, mean ? mean + r0 * C : nullptr, den ? den + r0 * C : nullptr, C};
+        MODL_TRY((launch_gemm<T, EpiUnscale<T>>(stream, A, B, rows, P, k, epi, SplitWs{}, nullptr, 512, 1)));
+    }
+    return MODL_OK;
+}
+
+// overlap-add as a GATHER: one thread per (pixel, channel) of the pixel rows [i_begin, i_begin + rows) that the pass
+// touches.  The thread loads its f64 accumulator, adds the values of the covering patches of this pass one at a time
+// in grid order (grid row outer, grid column inner; their offsets follow from the grid, there is no index), stores it.
+// Every accumulator therefore sees the same additions in the same order however the grid rows are cut into passes:
+// no atomics, bit-identical from run to run and from partition to partition.  Reads of the patches: for one step of
+// the loop, neighbouring pixels read the SAME in-patch position of NEIGHBOURING patches (stride ldp), C contiguous
+// channels each - runs of C elements, not coalesced; every element of the pass is read exactly once, and the lines
+// are reused from L2 by the later steps of the same wavefront.
+template <typename T>
+__global__ __launch_bounds__(256) void image_overlap_add_kernel(const T *__restrict__ patches, int64_t ldp, int64_t C,
+                                                                GridAxis gi, GridAxis gj, int64_t row0, int64_t nrows,
+                                                                int64_t i_begin, int64_t total,
+                                                                double *__restrict__ acc) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int64_t WC = gj.L * C;
+    const int64_t i = i_begin + e / WC, rem = e % WC, j = rem / C, c = rem % C;
+    int64_t r_lo = gi.lo(i), r_hi = gi.hi(i);
+    if (r_lo < row0) r_lo = row0;
+    if (r_hi > row0 + nrows - 1) r_hi = row0 + nrows - 1;
+    const int64_t c_lo = gj.lo(j), c_hi = gj.hi(j);
+    double *a = acc + i * WC + rem;
+    double s = *a;
+    for (int64_t gr = r_lo; gr <= r_hi; ++gr) {
+        const int64_t di = i - gi.origin(gr);
+        for (int64_t gc = c_lo; gc <= c_hi; ++gc) {
+            const int64_t dj = j - gj.origin(gc);
+            s += (double)patches[((gr - row0) * gj.g + gc) * ldp + (di * gj.x + dj) * C + c];
+        }
+    }
+    *a = s;
+}
+
+// image = accumulator / cover count; the count of a pixel is analytic: (grid rows over i) * (grid columns over j)
+template <typename T>
+__global__ __launch_bounds__(256) void image_overlap_finish_kernel(const double *__restrict__ acc, int64_t C,
+                                                                   GridAxis gi, GridAxis gj, int64_t total,
+                                                                   T *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int64_t WC = gj.L * C;
+    const int64_t i = e / WC, j = e % WC / C;
+    const int64_t cnt = (gi.hi(i) - gi.lo(i) + 1) * (gj.hi(j) - gj.lo(j) + 1);
+    out[e] = (T)(acc[e] / (double)cnt);
+}
+
+// arguments of every grid entry point: the grid itself, the channel count and a pass inside the grid
+static inline bool grid_args(int64_t H, int64_t W, int64_t C, int64_t x, int64_t y, int64_t si, int64_t sj,
+                             GridAxis *gi, GridAxis *gj) {
+    return C > 0 && C <= kPatchMaxChannels && grid_axis(H, x, si, gi) && grid_axis(W, y, sj, gj) &&
+           x * y <= INT32_MAX / C;                            // a flattened row is indexed with int
+}
+
+template <typename T>
+int grid_patches_impl(hipStream_t stream, const T *img, int64_t H, int64_t W, int64_t C, int x, int y, int si, int sj,
+                      int64_t row0, int64_t nrows, int with_mean, int with_std, T *out, int64_t ldo, T *mean, T *den) {
+    GridAxis gi, gj;
+    if (!img || !out || !mean || !den || !grid_args(H, W, C, x, y, si, sj, &gi, &gj) || row0 < 0 || nrows < 0 ||
+        row0 + nrows > gi.g || ldo < (int64_t)x * y * C)
+        return MODL_EINVAL;
+    const int64_t n = nrows * gj.g;
+    if (n == 0) return MODL_OK;
+    hipLaunchKernelGGL((image_grid_patches_kernel<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, stream, img, C, gi, gj,
+                       row0, n, with_mean, with_std, (T)sqrt((double)C), out, ldo, mean, den);
+    MODL_LAUNCH_CHECK();
+    return MODL_OK;
+}
+
+template <typename T>
+int overlap_add_impl(hipStream_t stream, const T *patches, int64_t ldp, int64_t H, int64_t W, int64_t C, int x, int y,
+                     int si, int sj, int64_t row0, int64_t nrows, double *acc) {
+    GridAxis gi, gj;
+    if (!patches || !acc || !grid_args(H, W, C, x, y, si, sj, &gi, &gj) || row0 < 0 || nrows < 0 ||
+        row0 + nrows > gi.g || ldp < (int64_t)x * y * C)
+        return MODL_EINVAL;
+    if (nrows == 0) return MODL_OK;
+    const int64_t i_begin = gi.origin(row0), i_end = gi.origin(row0 + nrows - 1) + x;
+    const int64_t total = (i_end - i_begin) * W * C;
+    hipLaunchKernelGGL((image_overlap_add_kernel<T>), dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, patches,
+                       ldp, C, gi, gj, row0, nrows, i_begin, total, acc);
+    MODL_LAUNCH_CHECK();
+    return MODL_OK;
+}
+
+template <typename T>
+int overlap_finish_impl(hipStream_t stream, const double *acc, int64_t H, int64_t W, int64_t C, int x, int y, int si,
+                        int sj, T *out) {
+    GridAxis gi, gj;
+    if (!acc || !out || !grid_args(H, W, C, x, y, si, sj, &gi, &gj)) return MODL_EINVAL;
+    const int64_t total = H * W * C;
+    hipLaunchKernelGGL((image_overlap_finish_kernel<T>), dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, acc, C,
+                       gi, gj, total, out);
     MODL_LAUNCH_CHECK();
     return MODL_OK;
 }
@@ -217,6 +397,39 @@ int modl_image_patches_f64(const double *d_image, int64_t H, int64_t W, int64_t 
     if (!MODL_PATCH_ARGS_OK) return MODL_EINVAL;
     return launch_image_patches<double>((hipStream_t)stream, d_image, H, W, C, d_idx3, n, x, y, z, with_mean, with_std, d_out, ldo);
 }
+
+int modl_image_grid_shape(int64_t H, int64_t W, int64_t x, int64_t y, int64_t si, int64_t sj, int64_t *grid_rows,
+                          int64_t *grid_cols) {
+    GridAxis gi, gj;
+    if (!grid_rows || !grid_cols || !grid_axis(H, x, si, &gi) || !grid_axis(W, y, sj, &gj)) return MODL_EINVAL;
+    *grid_rows = gi.g; *grid_cols = gj.g;
+    return MODL_OK;
+}
+
+#define MODL_GRID_EXPORTS(SFX, T)                                                                                     \
+    int modl_image_grid_patches_##SFX(const T *d_image, int64_t H, int64_t W, int64_t C, int x, int y, int si, int sj, \
+                                      int64_t row0, int64_t nrows, int with_mean, int with_std, T *d_out, int64_t ldo, \
+                                      T *d_mean, T *d_den, void *stream) {                                            \
+        return grid_patches_impl<T>((hipStream_t)stream, d_image, H, W, C, x, y, si, sj, row0, nrows, with_mean,      \
+                                    with_std, d_out, ldo, d_mean, d_den);                                             \
+    }                                                                                                                 \
+    int modl_image_decode_##SFX(const T *d_code, int64_t n, int k, const T *d_Dt, int64_t P, int C, const T *d_mean,  \
+                                const T *d_den, T *d_out, int64_t ldo, void *stream) {                                \
+        if (!d_code || !d_Dt || !d_out || n < 0 || k <= 0 || P <= 0 || P > INT32_MAX || ldo < P ||                   \
+            (d_mean == nullptr) != (d_den == nullptr) || (d_mean && (C <= 0 || P % C != 0)))                         \
+            return MODL_EINVAL;                                                                                       \
+        return decode_impl<T>((hipStream_t)stream, d_code, n, k, d_Dt, P, C, d_mean, d_den, d_out, ldo);              \
+    }                                                                                                                 \
+    int modl_image_overlap_add_##SFX(const T *d_patches, int64_t ldp, int64_t H, int64_t W, int64_t C, int x, int y,  \
+                                     int si, int sj, int64_t row0, int64_t nrows, double *d_acc, void *stream) {      \
+        return overlap_add_impl<T>((hipStream_t)stream, d_patches, ldp, H, W, C, x, y, si, sj, row0, nrows, d_acc);   \
+    }                                                                                                                 \
+    int modl_image_overlap_finish_##SFX(const double *d_acc, int64_t H, int64_t W, int64_t C, int x, int y, int si,   \
+                                        int sj, T *d_image_out, void *stream) {                                       \
+        return overlap_finish_impl<T>((hipStream_t)stream, d_acc, H, W, C, x, y, si, sj, d_image_out);                \
+    }
+MODL_GRID_EXPORTS(f32, float)
+MODL_GRID_EXPORTS(f64, double)
 
 size_t modl_objective_workspace(int dtype, int64_t n, int64_t p) {
     const size_t e = dtype == MODL_F32 ? 4 : 8;

@@ -435,6 +435,19 @@ class HipBackend:
                                       stream_ptr(self.device)), 'modl_somf_transform')
         return out.cpu().numpy() if to_host else out
 
+    def decode(self, code, mean=None, den=None):
+        """code D as a (n, p) device tensor; with the (n, C) statistics of modl_image_grid_patches_* the decoded patches
+        are put back on the image's scale: * den + mean per channel (modl_image_decode_*, csrc/image.hip)."""
+        n = code.shape[0]
+        out = torch.empty((n, self.p), dtype=torch_dtype(self.dtype), device=self.device)
+        if n == 0:
+            return out
+        f = getattr(lib, 'modl_image_decode_' + sfx(self.dtype))
+        with torch.cuda.device(self.device):
+            check(f(ptr(code), n, self.k, ptr(self.Dt), self.p, 1 if mean is None else mean.shape[1], ptr(mean), ptr(den),
+                    ptr(out), self.p, stream_ptr(self.device)), 'modl_image_decode')
+        return out
+
     def objective(self, Xh, code):
         """[sum (X - code D)^2, sum |code|, sum code^2] of device-resident X and codes (dict_fact.py:108-112)."""
         n, p = Xh.shape
@@ -690,6 +703,19 @@ class CodingMixin(TransformerMixin):
     def transform(self, X):
         """Codes of the rows of X on the dictionary (dict_fact.py:47-92)."""
         return self._transform(X, True)[1]
+
+    def inverse_transform(self, code):
+        """code @ components_ for codes of shape (n, n_components), on the device (the reference has no counterpart);
+        a numpy array gives a numpy array, a CUDA tensor a CUDA tensor."""
+        check_is_fitted(self, 'components_')
+        be = self._backend
+        on_host = not isinstance(code, torch.Tensor)
+        if on_host:
+            code = check_array(code, order='C', dtype=be.dtype.type)
+        if code.ndim != 2 or code.shape[1] != be.k:
+            raise ValueError('code has shape %s, the dictionary has %d components' % (tuple(code.shape), be.k))
+        out = be.decode(to_device(code, be.device, dtype=be.dtype))
+        return out.cpu().numpy() if on_host else out
 
     def score(self, X):
         """Objective value on test data X (dict_fact.py:94-114).  Test data, codes and dictionary stay on the device:

@@ -7,17 +7,24 @@ buffer of patches is gathered, centred, normalised and flattened by one HIP laun
 modl/input_data/image.py:4-23 fused) and handed to the SOMF step as a device tensor.
 The patch-origin lists (fill / clean_mask, image_fast.pyx:12-74) are integer host
 work behind the same C-ABI.  The numpy `scale_patches` below serves the public
-transform / score on patches the caller holds in host memory."""
+transform / score on patches the caller holds in host memory.
+The way back (no counterpart in the reference): `ImageDictFact.reconstruct` encodes
+every window of a regular patch grid, decodes it, undoes the per-patch scaling and
+averages the overlapping windows, all on the device (`grid_origins`, `grid_patches`,
+`reconstruct_from_patches`; the kernels are in csrc/image.hip, "reconstruction")."""
 import ctypes as C
 import time
 from math import sqrt
 
 import numpy as np
+import torch
 from numpy.lib.stride_tricks import sliding_window_view
 from sklearn.base import BaseEstimator
 from sklearn.utils import check_random_state, gen_batches
+from sklearn.utils.validation import check_is_fitted
 
 from ._lib import lib, check
+from .device import default_device, ptr, stream_ptr, to_device
 from .dict_fact import DictFact
 
 
@@ -59,6 +66,144 @@ def clean_mask(patches, image):
     check(f(image.ctypes.data_as(C.c_void_p), H, W, Cc, x, y, z, out.ctypes.data_as(C.c_void_p), C.byref(n)),
           'modl_image_clean_mask')
     return out[:n.value].copy()
+
+
+# ---- the patch grid of reconstruction ----------------------------------------------------------------------------------
+def _grid(image_shape, patch_size, stride):
+    """(H, W, C, x, y, si, sj) of a grid, checked: every bad argument is a ValueError here, before any library call"""
+    if len(image_shape) != 3:
+        raise ValueError('an image of shape (height, width, channels) is expected, got shape %s' % (tuple(image_shape),))
+    H, W, Cc = (int(v) for v in image_shape)
+    x, y = (int(v) for v in patch_size)
+    si, sj = (int(v) for v in (stride if np.ndim(stride) else (stride, stride)))
+    if x < 1 or y < 1 or x > H or y > W:
+        raise ValueError('patch_size %s does not fit an image of shape %s' % ((x, y), (H, W, Cc)))
+    if not (1 <= si <= x and 1 <= sj <= y):
+        raise ValueError('stride %s: 1 <= stride <= patch_size %s is needed (a larger one leaves pixels uncovered)'
+                         % ((si, sj), (x, y)))
+    if not 1 <= Cc <= 1024:
+        raise ValueError('1 to 1024 channels are supported, got %d' % Cc)
+    return H, W, Cc, x, y, si, sj
+
+
+def _axis_origins(L, x, s):
+    o = np.arange(0, L - x + 1, s, dtype=np.int64)
+    return o if o[-1] == L - x else np.append(o, L - x)
+
+
+def grid_origins(image_shape, patch_size, stride=1):
+    """Origins (i, j, 0) of the patch grid of reconstruction, an (n, 3) int64 array in patch order.  The rule: along an
+    axis of length L with patch length x and stride s the origins are 0, s, 2 s, ... <= L - x, plus L - x itself when
+    it is not already the last one, so that the border is always covered; a patch spans all channels; patches are
+    numbered row-major over (grid row, grid column)."""
+    H, W, _, x, y, si, sj = _grid(image_shape, patch_size, stride)
+    oi, oj = _axis_origins(H, x, si), _axis_origins(W, y, sj)
+    out = np.zeros((oi.shape[0] * oj.shape[0], 3), dtype=np.int64)
+    out[:, 0], out[:, 1] = np.repeat(oi, oj.shape[0]), np.tile(oj, oi.shape[0])
+    return out
+
+
+def _grid_shape(g):
+    H, W, _, x, y, si, sj = g
+    rows, cols = C.c_int64(), C.c_int64()
+    check(lib.modl_image_grid_shape(H, W, x, y, si, sj, C.byref(rows), C.byref(cols)), 'modl_image_grid_shape')
+    return rows.value, cols.value
+
+
+def _sfx(t):
+    if t.dtype not in (torch.float32, torch.float64):
+        raise TypeError('float32 or float64 expected, got %s' % t.dtype)
+    return 'f32' if t.dtype == torch.float32 else 'f64'
+
+
+def _grid_patches_pass(d_image, g, gcols, row0, nrows, with_mean, with_std):
+    """the patches of the grid rows [row0, row0 + nrows) of a device image: (patches, mean, den)"""
+    H, W, Cc, x, y, si, sj = g
+    n, kw = nrows * gcols, dict(dtype=d_image.dtype, device=d_image.device)
+    out, mean, den = torch.empty((n, x * y * Cc), **kw), torch.empty((n, Cc), **kw), torch.empty((n, Cc), **kw)
+    with torch.cuda.device(d_image.device):
+        check(getattr(lib, 'modl_image_grid_patches_' + _sfx(d_image))(
+            ptr(d_image), H, W, Cc, x, y, si, sj, row0, nrows, int(bool(with_mean)), int(bool(with_std)), ptr(out),
+            x * y * Cc, ptr(mean), ptr(den), stream_ptr(d_image.device)), 'modl_image_grid_patches')
+    return out, mean, den
+
+
+def _overlap_add(d_patches, g, row0, nrows, acc):
+    H, W, Cc, x, y, si, sj = g
+    with torch.cuda.device(acc.device):
+        check(getattr(lib, 'modl_image_overlap_add_' + _sfx(d_patches))(
+            ptr(d_patches), d_patches.stride(0), H, W, Cc, x, y, si, sj, row0, nrows, ptr(acc), stream_ptr(acc.device)),
+            'modl_image_overlap_add')
+
+
+def _overlap_finish(acc, g, dtype):
+    H, W, Cc, x, y, si, sj = g
+    out = torch.empty((H, W, Cc), dtype=dtype, device=acc.device)
+    with torch.cuda.device(acc.device):
+        check(getattr(lib, 'modl_image_overlap_finish_' + _sfx(out))(
+            ptr(acc), H, W, Cc, x, y, si, sj, ptr(out), stream_ptr(acc.device)), 'modl_image_overlap_finish')
+    return out
+
+
+PASS_BYTES = 256 << 20      # a pass's patch buffer stays under this: a memory bound, not a tuned value
+
+
+def _passes(grows, gcols, row_bytes, rows_per_pass):
+    """(row0, nrows) of every pass over the grid rows, in order"""
+    if rows_per_pass is None:
+        rows_per_pass = max(1, PASS_BYTES // (gcols * row_bytes))
+    rows_per_pass = int(rows_per_pass)
+    if rows_per_pass < 1:
+        raise ValueError('rows_per_pass >= 1 is needed, got %d' % rows_per_pass)
+    return [(r0, min(rows_per_pass, grows - r0)) for r0 in range(0, grows, rows_per_pass)]
+
+
+def _stage_image(image, device=None, dtype=None):
+    """(H, W, C) image, numpy or tensor -> contiguous float32 / float64 device tensor"""
+    if isinstance(image, torch.Tensor):
+        floating = image.dtype in (torch.float32, torch.float64)
+        if device is None and image.is_cuda:
+            device = image.device
+    else:
+        image = np.asarray(image)
+        floating = image.dtype in (np.float32, np.float64)
+    if dtype is None and not floating:
+        dtype = np.float64
+    return to_device(image, torch.device(device) if device is not None else default_device(), dtype=dtype)
+
+
+def grid_patches(image, patch_size, stride=1, with_mean=True, with_std=True, device=None):
+    """Every patch of the grid (`grid_origins`) of an (H, W, C) image, flattened and scaled channel-wise as
+    `scale_patches` does, with what the scaling removed: the device tensors (patches (n, x*y*C), mean (n, C), den (n, C)),
+    den being the divisor that was applied (1 where none was) - `patches * den + mean` per channel is the window again."""
+    g = _grid(np.shape(image), patch_size, stride)
+    d_image = _stage_image(image, device)
+    grows, gcols = _grid_shape(g)
+    return _grid_patches_pass(d_image, g, gcols, 0, grows, with_mean, with_std)
+
+
+def reconstruct_from_patches(patches, image_shape, patch_size, stride=1, rows_per_pass=None):
+    """The image whose pixels are the averages of the flattened patches (n, x*y*C) that cover them, the patches lying
+    on the grid of `grid_origins` (already on the image's scale).  Sums are accumulated in float64 in grid order by a
+    gather on the device: the result does not depend on `rows_per_pass` (grid rows per launch) nor on the run, bit for
+    bit.  A numpy array gives a numpy array, a CUDA tensor a CUDA tensor, of the patches' dtype."""
+    g = _grid(image_shape, patch_size, stride)
+    H, W, Cc, x, y = g[:5]
+    on_host = not isinstance(patches, torch.Tensor)
+    if on_host:
+        patches = np.asarray(patches)
+        patches = torch.from_numpy(np.ascontiguousarray(
+            patches, dtype=None if patches.dtype in (np.float32, np.float64) else np.float64)).to(default_device())
+    grows, gcols = _grid_shape(g)
+    if patches.ndim != 2 or tuple(patches.shape) != (grows * gcols, x * y * Cc):
+        raise ValueError('patches of shape %s expected on this grid, got %s'
+                         % ((grows * gcols, x * y * Cc), tuple(patches.shape)))
+    patches = patches.contiguous()
+    acc = torch.zeros((H, W, Cc), dtype=torch.float64, device=patches.device)
+    for row0, nrows in _passes(grows, gcols, patches.shape[1] * patches.element_size(), rows_per_pass):
+        _overlap_add(patches[row0 * gcols:(row0 + nrows) * gcols], g, row0, nrows, acc)
+    out = _overlap_finish(acc, g, patches.dtype)
+    return out.cpu().numpy() if on_host else out
 
 
 class LazyCleanPatchExtractor(BaseEstimator):
@@ -227,6 +372,33 @@ class ImageDictFact(BaseEstimator):
 
     def score(self, patches):
         return self.dict_fact_.score(self._prep(patches))
+
+    def reconstruct(self, image, stride=1, rows_per_pass=None):
+        """The image rebuilt from the sparse codes of its patches: every window of the patch grid (`grid_origins`:
+        stride `stride`, an int or a pair, the last window clamped to the border) is scaled as in `fit`, encoded on the
+        fitted dictionary, decoded, put back on the image's scale, and the overlapping windows are averaged.  Returns
+        an array of the image's shape in the dtype of the fitted dictionary (the input is cast as `transform` casts).
+        Image, patches, codes and sums stay on the device, `rows_per_pass` grid rows at a time (default: as many as keep
+        the patch buffer under 256 MB); the result does not depend on it.  The value -1 is ordinary data here:
+        inpainting of missing pixels is out of scope."""
+        check_is_fitted(self, 'dict_fact_')
+        be = self.dict_fact_._backend
+        g = _grid(np.shape(image), self.patch_shape_[:2], stride)
+        if g[2] != self.patch_shape_[2]:
+            raise ValueError('the image has %d channels, the estimator was fitted on %d' % (g[2], self.patch_shape_[2]))
+        on_host = not isinstance(image, torch.Tensor)
+        d_image = _stage_image(image, be.device, dtype=be.dtype)
+        s = ImageDictFact.settings[self.setting]
+        kw = self.dict_fact_._plan_kwargs(4096)
+        G = be.G if self.dict_fact_.G_agg == 'full' else None              # as CodingMixin._transform
+        grows, gcols = _grid_shape(g)
+        acc = torch.zeros(g[:3], dtype=torch.float64, device=be.device)
+        for row0, nrows in _passes(grows, gcols, be.p * be.dtype.itemsize, rows_per_pass):
+            patches, mean, den = _grid_patches_pass(d_image, g, gcols, row0, nrows, s['with_mean'], s['with_std'])
+            code = be.transform(patches, kw, G, to_host=False)
+            _overlap_add(be.decode(code, mean, den), g, row0, nrows, acc)
+        out = _overlap_finish(acc, g, d_image.dtype)
+        return out.cpu().numpy() if on_host else out
 
     def stage_test_patches(self, patches):
         """Scaled, flattened test patches as a tensor on the estimator's device: `score_staged` then evaluates the
