@@ -554,6 +554,56 @@ int modl_image_overlap_finish_f32(const double *d_acc, int64_t H, int64_t W, int
                                   float *d_image_out, void *stream);
 int modl_image_overlap_finish_f64(const double *d_acc, int64_t H, int64_t W, int64_t C, int x, int y, int si, int sj,
                                   double *d_image_out, void *stream);
+/* Inpainting (no counterpart in the reference's image module).  The estimator is the reference's own: a code is
+ * estimated from a subset S of the features with Dx = r X_S D_S^T, G = r D_S D_S^T, r = p / |S|
+ * (modl/decomposition/dict_fact.py:594-604); here S is each row's own set of observed entries, so every row has its own
+ * Gram matrix and _enet_regression_multi_gram (dict_fact_fast.pyx:33-113, modl_enet_regression_multi_gram_*) solves it.
+ *
+ * modl_masked_gram_*: for sample ii of b, row i = d_rows[ii] (d_rows NULL: i = ii), M_i = { e : d_obs[i][e] != 0 },
+ * m_i = |M_i| (-> d_nobs[ii]; d_nobs may be NULL), r_i = p / m_i:
+ *   d_G[ii][a][c] = r_i sum_{e in M_i} d_Dt[e][a] d_Dt[e][c]     (the full k x k matrix, symmetric bit for bit)
+ *   d_Dx[ii][a]   = r_i sum_{e in M_i} d_X[i][e] d_Dt[e][a]
+ * and zeros when m_i = 0.  d_Dt[p][k] feature-major, d_X[..][ldx], d_obs[..][ldo] bytes.  Values of d_X at unobserved
+ * positions never reach the result (they may be NaN).  The products run on the matrix cores in the dtype, the scaling
+ * follows the sums; no atomics (bit-identical from run to run), no scratch.  1 <= k <= 1024, p >= 1, b >= 0; a NULL
+ * pointer (d_rows and d_nobs apart), k out of range, ldx < p or ldo < p -> MODL_EINVAL before any device work. */
+int modl_masked_gram_f32(const float *d_Dt, int64_t p, int k, const float *d_X, int64_t ldx, const uint8_t *d_obs,
+                         int64_t ldo, const int64_t *d_rows, int64_t b, float *d_G, float *d_Dx, int32_t *d_nobs,
+                         void *stream);
+int modl_masked_gram_f64(const double *d_Dt, int64_t p, int k, const double *d_X, int64_t ldx, const uint8_t *d_obs,
+                         int64_t ldo, const int64_t *d_rows, int64_t b, double *d_G, double *d_Dx, int32_t *d_nobs,
+                         void *stream);
+/* modl_image_grid_patches_* on an image with holes: d_obs_image[H][W][C] bytes, 1 = observed.  Per patch, channel c with
+ * the observed window elements O_c, n_c = |O_c|, N = x y:  mean_c = (sum_{O_c} v) / n_c (with_mean and n_c > 0, else
+ * 0); observed elements are centred, unobserved ones written as 0; with_std: den_c = norm_c sqrt(C) with norm_c =
+ * sqrt(sum_{O_c} u^2) sqrt(N / n_c), the estimate of the full window's norm (1 if it is 0 or n_c = 0), else den_c = 1.
+ * Also d_obs_out[n][x*y*C] (the window of d_obs_image in row order) and d_nobs[n] (its sum).  A patch with every
+ * element observed gives the row, mean and den of modl_image_grid_patches_* bit for bit. */
+int modl_image_grid_patches_masked_f32(const float *d_image, int64_t H, int64_t W, int64_t C, int x, int y, int si,
+                                       int sj, int64_t row0, int64_t nrows, int with_mean, int with_std, float *d_out,
+                                       int64_t ldo, float *d_mean, float *d_den, const uint8_t *d_obs_image,
+                                       uint8_t *d_obs_out, int32_t *d_nobs, void *stream);
+int modl_image_grid_patches_masked_f64(const double *d_image, int64_t H, int64_t W, int64_t C, int x, int y, int si,
+                                       int sj, int64_t row0, int64_t nrows, int with_mean, int with_std, double *d_out,
+                                       int64_t ldo, double *d_mean, double *d_den, const uint8_t *d_obs_image,
+                                       uint8_t *d_obs_out, int32_t *d_nobs, void *stream);
+/* modl_image_overlap_add_* over the patches q of the pass with d_use[q] != 0 only; d_cnt[H][W] (int32, zeroed by the
+ * caller before the first pass) counts them per pixel.  The same gather in grid order: sums and counts do not depend
+ * on how the grid rows are cut into passes. */
+int modl_image_overlap_add_weighted_f32(const float *d_patches, int64_t ldp, int64_t H, int64_t W, int64_t C, int x,
+                                        int y, int si, int sj, int64_t row0, int64_t nrows, double *d_acc,
+                                        const uint8_t *d_use, int32_t *d_cnt, void *stream);
+int modl_image_overlap_add_weighted_f64(const double *d_patches, int64_t ldp, int64_t H, int64_t W, int64_t C, int x,
+                                        int y, int si, int sj, int64_t row0, int64_t nrows, double *d_acc,
+                                        const uint8_t *d_use, int32_t *d_cnt, void *stream);
+/* d_image_out = d_acc / d_cnt where d_cnt > 0, d_image elsewhere; with keep_observed != 0 the observed elements
+ * (d_obs_image != 0) take d_image's value unchanged.  H, W >= 1, 1 <= C <= 1024. */
+int modl_image_inpaint_finish_f32(const double *d_acc, const int32_t *d_cnt, const float *d_image,
+                                  const uint8_t *d_obs_image, int64_t H, int64_t W, int64_t C, int keep_observed,
+                                  float *d_image_out, void *stream);
+int modl_image_inpaint_finish_f64(const double *d_acc, const int32_t *d_cnt, const double *d_image,
+                                  const uint8_t *d_obs_image, int64_t H, int64_t W, int64_t C, int keep_observed,
+                                  double *d_image_out, void *stream);
 /* The three sums of CodingMixin.score (dict_fact.py:108-114) on device-resident operands:
  * d_out3 = [ sum (X - code D)^2, sum |code|, sum code^2 ] (f64 accumulation, fixed order: run-to-run reproducible).
  * d_X[n][ldx], d_Dt[p][k], d_code[n][k]; scratch of modl_objective_workspace() bytes (any smaller size that holds at

@@ -156,6 +156,12 @@ def bind(lib):
              _i64, _i64, _vp, _vp)
         _sig('modl_image_overlap_finish_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
              _vp)
+        _sig('modl_masked_gram_' + _sfx, C.c_int, _vp, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp)
+        _sig('modl_image_grid_patches_masked_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int,
+             _i64, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp)
+        _sig('modl_image_overlap_add_weighted_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int,
+             C.c_int, _i64, _i64, _vp, _vp, _vp, _vp)
+        _sig('modl_image_inpaint_finish_' + _sfx, C.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp)
         _sig('modl_objective_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, C.c_int, _vp, _vp, _sz, _vp, _vp)
         _sig('modl_amari_' + _sfx, C.c_int, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _P(C.c_int))
     _sig('modl_image_fill', C.c_int, _i64, _i64, _i64, _vp)

@@ -268,6 +268,128 @@ __global__ __launch_bounds__(256) void image_overlap_finish_kernel(const double 
     out[e] = (T)(acc[e] / (double)cnt);
 }
 
+// ---- inpainting ---------------------------------------------------------------------------------------------------
+// image_grid_patches_kernel on an image with holes (obs[H][W][C], 1 = observed).  A window without a hole takes
+// patch_row itself, so its row, mean and den are those of modl_image_grid_patches_* bit for bit.  Otherwise the
+// statistics of a channel are taken over its n_c OBSERVED positions: mean_c = sum / n_c; the norm of the centred
+// observed values times sqrt(x y / n_c) estimates the norm of the full window (1 if it is 0 or n_c = 0); unobserved
+// elements of the row are 0.  obs_out[q][:] is the window of obs in the row's element order, nobs[q] its sum.
+template <typename T>
+__global__ __launch_bounds__(256) void image_grid_patches_masked_kernel(
+    const T *__restrict__ img, const uint8_t *__restrict__ obs, int64_t C, GridAxis gi, GridAxis gj, int64_t row0,
+    int64_t n, int with_mean, int with_std, T sqrt_z, T *__restrict__ out, int64_t ldo, T *__restrict__ mean,
+    T *__restrict__ den, uint8_t *__restrict__ obs_out, int32_t *__restrict__ nobs) {
+    __shared__ T s_mean[4][kPatchMaxChannels];
+    __shared__ T s_den[4][kPatchMaxChannels];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int64_t q = (int64_t)blockIdx.x * 4 + wid;
+    if (q >= n) return;                                       // wave-uniform; no block barrier below
+    const int64_t i0 = gi.origin(row0 + q / gj.g), j0 = gj.origin(q % gj.g), W = gj.L;
+    const int z = (int)C, x = gi.x, y = gj.x, xy = x * y, yz = y * z, P = xy * z;
+    const T *base = img + (i0 * W + j0) * C;
+    const uint8_t *obase = obs + (i0 * W + j0) * C;
+    T *o = out + q * ldo;
+    uint8_t *oo = obs_out + q * (int64_t)P;
+    int cnt = 0;
+    for (int e = lane; e < P; e += 64) {
+        const int xi = e / yz, rem = e - xi * yz;
+        const uint8_t on = obase[(int64_t)xi * W * C + rem] != 0;
+        oo[e] = on;
+        cnt += on;
+    }
+    cnt = (int)wave_sum((double)cnt);
+    if (lane == 0) nobs[q] = cnt;
+    if (cnt == P) {                                           // wave-uniform: the clean window
+        if (!(with_mean || with_std))
+            for (int c = lane; c < z; c += 64) { s_mean[wid][c] = 0; s_den[wid][c] = 1; }
+        patch_row<T>(base, W, C, x, y, z, with_mean, with_std, sqrt_z, s_mean[wid], s_den[wid], o);
+    } else {
+        for (int c = 0; c < z; ++c) {
+            T s = 0;
+            int nc = 0;
+            for (int pos = lane; pos < xy; pos += 64) {
+                const int64_t at = ((int64_t)(pos / y) * W + pos % y) * C + c;
+                const bool on = obase[at] != 0;
+                const T v = base[at];
+                s += on ? v : (T)0;
+                nc += on;
+            }
+            nc = (int)wave_sum((double)nc);
+            const T m = (with_mean && nc > 0) ? wave_sum(s) / (T)nc : (T)0;
+            T d = 1;
+            if (with_std) {
+                T s2 = 0;
+                for (int pos = lane; pos < xy; pos += 64) {
+                    const int64_t at = ((int64_t)(pos / y) * W + pos % y) * C + c;
+                    const T u = base[at] - m;
+                    s2 += obase[at] != 0 ? u * u : (T)0;
+                }
+                T sd = nc > 0 ? sqrt(wave_sum(s2)) * sqrt((T)xy / (T)nc) : (T)1;
+                if (sd == (T)0) sd = 1;
+                d = sd * sqrt_z;
+            }
+            if (lane == 0) { s_mean[wid][c] = m; s_den[wid][c] = d; }
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int e = lane; e < P; e += 64) {
+            const int xi = e / yz, rem = e - xi * yz, c = rem % z;
+            const int64_t at = (int64_t)xi * W * C + rem;
+            T v = base[at];
+            if (with_mean) v -= s_mean[wid][c];
+            if (with_std) v /= s_den[wid][c];
+            o[e] = obase[at] != 0 ? v : (T)0;
+        }
+    }
+    for (int c = lane; c < z; c += 64) { mean[q * C + c] = s_mean[wid][c]; den[q * C + c] = s_den[wid][c]; }
+}
+
+// image_overlap_add_kernel over the patches of the pass whose use[q] != 0 only; cnt[H][W] counts them per pixel (by
+// the thread of channel 0).  The same gather in grid order: sums and counts do not depend on the cut into passes.
+template <typename T>
+__global__ __launch_bounds__(256) void image_overlap_add_weighted_kernel(
+    const T *__restrict__ patches, int64_t ldp, const uint8_t *__restrict__ use, int64_t C, GridAxis gi, GridAxis gj,
+    int64_t row0, int64_t nrows, int64_t i_begin, int64_t total, double *__restrict__ acc, int32_t *__restrict__ cnt) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int64_t WC = gj.L * C;
+    const int64_t i = i_begin + e / WC, rem = e % WC, j = rem / C, c = rem % C;
+    int64_t r_lo = gi.lo(i), r_hi = gi.hi(i);
+    if (r_lo < row0) r_lo = row0;
+    if (r_hi > row0 + nrows - 1) r_hi = row0 + nrows - 1;
+    const int64_t c_lo = gj.lo(j), c_hi = gj.hi(j);
+    double *a = acc + i * WC + rem;
+    double s = *a;
+    int32_t added = 0;
+    for (int64_t gr = r_lo; gr <= r_hi; ++gr) {
+        const int64_t di = i - gi.origin(gr);
+        for (int64_t gc = c_lo; gc <= c_hi; ++gc) {
+            const int64_t q = (gr - row0) * gj.g + gc;
+            if (!use[q]) continue;
+            const int64_t dj = j - gj.origin(gc);
+            s += (double)patches[q * ldp + (di * gj.x + dj) * C + c];
+            ++added;
+        }
+    }
+    *a = s;
+    if (c == 0) cnt[i * gj.L + j] += added;
+}
+
+// out = acc / cnt where a used patch covers the pixel, the input image elsewhere - and, with keep_observed, wherever the
+// element was observed
+template <typename T>
+__global__ __launch_bounds__(256) void image_inpaint_finish_kernel(const double *__restrict__ acc,
+                                                                   const int32_t *__restrict__ cnt,
+                                                                   const T *__restrict__ img,
+                                                                   const uint8_t *__restrict__ obs, int64_t C,
+                                                                   int64_t total, int keep_observed,
+                                                                   T *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int32_t n = cnt[e / C];
+    const T v = img[e];
+    out[e] = (n > 0 && !(keep_observed && obs[e] != 0)) ? (T)(acc[e] / (double)n) : v;
+}
+
 // arguments of every grid entry point: the grid itself, the channel count and a pass inside the grid
 static inline bool grid_args(int64_t H, int64_t W, int64_t C, int64_t x, int64_t y, int64_t si, int64_t sj,
                              GridAxis *gi, GridAxis *gj) {
@@ -314,6 +436,50 @@ int overlap_finish_impl(hipStream_t stream, const double *acc, int64_t H, int64_
     const int64_t total = H * W * C;
     hipLaunchKernelGGL((image_overlap_finish_kernel<T>), dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, acc, C,
                        gi, gj, total, out);
+    MODL_LAUNCH_CHECK();
+    return MODL_OK;
+}
+
+template <typename T>
+int grid_patches_masked_impl(hipStream_t stream, const T *img, const uint8_t *obs, int64_t H, int64_t W, int64_t C, int x,
+                             int y, int si, int sj, int64_t row0, int64_t nrows, int with_mean, int with_std, T *out,
+                             int64_t ldo, T *mean, T *den, uint8_t *obs_out, int32_t *nobs) {
+    GridAxis gi, gj;
+    if (!img || !obs || !out || !mean || !den || !obs_out || !nobs || !grid_args(H, W, C, x, y, si, sj, &gi, &gj) ||
+        row0 < 0 || nrows < 0 || row0 + nrows > gi.g || ldo < (int64_t)x * y * C)
+        return MODL_EINVAL;
+    const int64_t n = nrows * gj.g;
+    if (n == 0) return MODL_OK;
+    hipLaunchKernelGGL((image_grid_patches_masked_kernel<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, stream, img, obs,
+                       C, gi, gj, row0, n, with_mean, with_std, (T)sqrt((double)C), out, ldo, mean, den, obs_out, nobs);
+    MODL_LAUNCH_CHECK();
+    return MODL_OK;
+}
+
+template <typename T>
+int overlap_add_weighted_impl(hipStream_t stream, const T *patches, int64_t ldp, const uint8_t *use, int64_t H, int64_t W,
+                              int64_t C, int x, int y, int si, int sj, int64_t row0, int64_t nrows, double *acc,
+                              int32_t *cnt) {
+    GridAxis gi, gj;
+    if (!patches || !use || !acc || !cnt || !grid_args(H, W, C, x, y, si, sj, &gi, &gj) || row0 < 0 || nrows < 0 ||
+        row0 + nrows > gi.g || ldp < (int64_t)x * y * C)
+        return MODL_EINVAL;
+    if (nrows == 0) return MODL_OK;
+    const int64_t i_begin = gi.origin(row0), i_end = gi.origin(row0 + nrows - 1) + x;
+    const int64_t total = (i_end - i_begin) * W * C;
+    hipLaunchKernelGGL((image_overlap_add_weighted_kernel<T>), dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream,
+                       patches, ldp, use, C, gi, gj, row0, nrows, i_begin, total, acc, cnt);
+    MODL_LAUNCH_CHECK();
+    return MODL_OK;
+}
+
+template <typename T>
+int inpaint_finish_impl(hipStream_t stream, const double *acc, const int32_t *cnt, const T *img, const uint8_t *obs,
+                        int64_t H, int64_t W, int64_t C, int keep_observed, T *out) {
+    if (!acc || !cnt || !img || !obs || !out || H <= 0 || W <= 0 || C <= 0 || C > kPatchMaxChannels) return MODL_EINVAL;
+    const int64_t total = H * W * C;
+    hipLaunchKernelGGL((image_inpaint_finish_kernel<T>), dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, acc, cnt,
+                       img, obs, C, total, keep_observed, out);
     MODL_LAUNCH_CHECK();
     return MODL_OK;
 }
@@ -427,6 +593,26 @@ int modl_image_grid_shape(int64_t H, int64_t W, int64_t x, int64_t y, int64_t si
     int modl_image_overlap_finish_##SFX(const double *d_acc, int64_t H, int64_t W, int64_t C, int x, int y, int si,   \
                                         int sj, T *d_image_out, void *stream) {                                       \
         return overlap_finish_impl<T>((hipStream_t)stream, d_acc, H, W, C, x, y, si, sj, d_image_out);                \
+    }                                                                                                                 \
+    int modl_image_grid_patches_masked_##SFX(const T *d_image, int64_t H, int64_t W, int64_t C, int x, int y, int si,  \
+                                             int sj, int64_t row0, int64_t nrows, int with_mean, int with_std,        \
+                                             T *d_out, int64_t ldo, T *d_mean, T *d_den,                              \
+                                             const uint8_t *d_obs_image, uint8_t *d_obs_out, int32_t *d_nobs,         \
+                                             void *stream) {                                                          \
+        return grid_patches_masked_impl<T>((hipStream_t)stream, d_image, d_obs_image, H, W, C, x, y, si, sj, row0,    \
+                                           nrows, with_mean, with_std, d_out, ldo, d_mean, d_den, d_obs_out, d_nobs); \
+    }                                                                                                                 \
+    int modl_image_overlap_add_weighted_##SFX(const T *d_patches, int64_t ldp, int64_t H, int64_t W, int64_t C, int x, \
+                                              int y, int si, int sj, int64_t row0, int64_t nrows, double *d_acc,      \
+                                              const uint8_t *d_use, int32_t *d_cnt, void *stream) {                   \
+        return overlap_add_weighted_impl<T>((hipStream_t)stream, d_patches, ldp, d_use, H, W, C, x, y, si, sj, row0,  \
+                                            nrows, d_acc, d_cnt);                                                     \
+    }                                                                                                                 \
+    int modl_image_inpaint_finish_##SFX(const double *d_acc, const int32_t *d_cnt, const T *d_image,                  \
+                                        const uint8_t *d_obs_image, int64_t H, int64_t W, int64_t C,                  \
+                                        int keep_observed, T *d_image_out, void *stream) {                            \
+        return inpaint_finish_impl<T>((hipStream_t)stream, d_acc, d_cnt, d_image, d_obs_image, H, W, C,               \
+                                      keep_observed, d_image_out);                                                    \
     }
 MODL_GRID_EXPORTS(f32, float)
 MODL_GRID_EXPORTS(f64, double)

@@ -435,6 +435,61 @@ class HipBackend:
                                       stream_ptr(self.device)), 'modl_somf_transform')
         return out.cpu().numpy() if to_host else out
 
+    def masked_gram(self, Xh, obs, rows=None):
+        """Per-row Gram matrix and Dx on each row's observed entries (modl_masked_gram_*, csrc/masked_gram.hip): for the
+        rows `rows` (an int64 device tensor; None: all) of Xh (n, p) and obs (n, p) uint8, 1 = observed, the device
+        tensors G (b, k, k), Dx (b, k) and nobs (b,) int32."""
+        b = Xh.shape[0] if rows is None else rows.shape[0]
+        kw = dict(dtype=torch_dtype(self.dtype), device=self.device)
+        G, Dx = torch.empty((b, self.k, self.k), **kw), torch.empty((b, self.k), **kw)
+        nobs = torch.empty(b, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(getattr(lib, 'modl_masked_gram_' + sfx(self.dtype))(
+                ptr(self.Dt), self.p, self.k, ptr(Xh), Xh.stride(0), ptr(obs), obs.stride(0), ptr(rows), b, ptr(G),
+                ptr(Dx), ptr(nobs), stream_ptr(self.device)), 'modl_masked_gram')
+        return G, Dx, nobs
+
+    def masked_chunk_rows(self):
+        """rows per masked solve: their Gram matrices stay under 256 MB (a memory bound, not a tuned value)"""
+        return max(1, min(4096, (256 << 20) // (self.k * self.k * self.dtype.itemsize)))
+
+    def transform_masked(self, Xh, obs, kw, G=None, nobs=None):
+        """Codes of the rows of Xh (n, p) from their observed entries only (obs (n, p) uint8, 1 = observed; nobs: its row
+        sums when the caller has them), a (n, k) device tensor.  Rows without a hole take `transform`'s shared-Gram
+        route, rows without an observed entry get zero codes, the others are solved chunk by chunk with a Gram matrix
+        of their own: modl_masked_gram_* then modl_enet_regression_multi_gram_* from a warm start of ones, the solver's
+        X being the zero-filled rows (its tolerance scales with the observed squared norm)."""
+        n = Xh.shape[0]
+        if nobs is None:
+            nobs = obs.sum(dim=1, dtype=torch.int32)
+        clean = torch.nonzero(nobs == self.p).flatten()
+        if clean.shape[0] == n:
+            return self.transform(Xh, kw, G, to_host=False)
+        code = torch.zeros((n, self.k), dtype=torch_dtype(self.dtype), device=self.device)
+        if clean.shape[0]:
+            code[clean] = self.transform(Xh[clean], kw, G, to_host=False)
+        holed = torch.nonzero((nobs > 0) & (nobs < self.p)).flatten()
+        if holed.shape[0] == 0:
+            return code
+        Xz = torch.where(obs != 0, Xh, torch.zeros((), dtype=Xh.dtype, device=Xh.device))
+        solve = getattr(lib, 'modl_enet_regression_multi_gram_' + sfx(self.dtype))
+        step = self.masked_chunk_rows()
+        for c0 in range(0, holed.shape[0], step):
+            rows = holed[c0:c0 + step].contiguous()
+            b = rows.shape[0]
+            Gm, Dx, _ = self.masked_gram(Xh, obs, rows)
+            Xc = Xz[rows]
+            out = torch.ones((b, self.k), dtype=code.dtype, device=self.device)
+            nbytes = lib.modl_enet_regression_workspace(dtype_id(self.dtype), b, self.k, 1)
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                check(solve(ptr(Gm), ptr(Dx), ptr(Xc), Xc.stride(0), self.p, ptr(out), None, b, self.k,
+                            kw['code_l1_ratio'], kw['code_alpha'], int(bool(kw['code_pos'])), kw['tol'],
+                            int(kw['max_iter']), None, ptr(ws), nbytes, stream_ptr(self.device)),
+                      'modl_enet_regression_multi_gram')
+            code[rows] = out
+        return code
+
     def decode(self, code, mean=None, den=None):
         """code D as a (n, p) device tensor; with the (n, C) statistics of modl_image_grid_patches_* the decoded patches
         are put back on the image's scale: * den + mean per channel (modl_image_decode_*, csrc/image.hip)."""
@@ -666,6 +721,9 @@ class _DeviceRows:
         self.backend.shuffle_rows(self.name, swaps)
 
 
+MASKED_MAX_COMPONENTS = 1024     # transform(X, mask): one k x k Gram matrix per row (modl_masked_gram_*: k <= 1024)
+
+
 class CodingMixin(TransformerMixin):
     def _set_coding_params(self, n_components, code_alpha=1, code_l1_ratio=1, tol=1e-2, max_iter=100,
                            code_pos=False, random_state=None, n_threads=1):
@@ -700,9 +758,38 @@ class CodingMixin(TransformerMixin):
         use_G = getattr(self, 'G_agg', None) == 'full' and be.G is not None
         return Xh, be.transform(Xh, self._plan_kwargs(4096), be.G if use_G else None, to_host=to_host)
 
-    def transform(self, X):
-        """Codes of the rows of X on the dictionary (dict_fact.py:47-92)."""
-        return self._transform(X, True)[1]
+    def transform(self, X, mask=None):
+        """Codes of the rows of X on the dictionary (dict_fact.py:47-92).  With `mask` (a boolean array or tensor of X's
+        shape, True = observed) every row is coded on its observed entries only, by the estimator of the SOMF step
+        itself with the row's own subset (dict_fact.py:594-604: Dx = r X_S D_S^T, G = r D_S D_S^T, r = p / |S|): rows
+        without a hole are coded as without a mask, rows without an observed entry get zero codes; values of X at
+        unobserved positions are never used.  Needs n_components <= MASKED_MAX_COMPONENTS."""
+        if mask is None:
+            return self._transform(X, True)[1]
+        if tuple(np.shape(mask)) != tuple(np.shape(X)) or len(np.shape(X)) != 2:
+            raise ValueError('mask of shape %s does not match X of shape %s (n_samples, n_features)'
+                             % (tuple(np.shape(mask)), tuple(np.shape(X))))
+        if self.n_components > MASKED_MAX_COMPONENTS:
+            raise ValueError('transform with a mask supports at most %d components (one Gram matrix per row), got %d'
+                             % (MASKED_MAX_COMPONENTS, self.n_components))
+        check_is_fitted(self, 'components_')
+        be = self._backend
+        on_host = not isinstance(X, torch.Tensor)
+        if isinstance(mask, torch.Tensor):
+            obs = (mask != 0).to(device=be.device, dtype=torch.uint8).contiguous()
+        else:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0)
+            obs = torch.from_numpy(mask.view(np.uint8)).to(be.device)
+        if on_host:
+            # unobserved entries may hold anything (NaN included): they are not validated, and never used
+            m = mask if isinstance(mask, np.ndarray) else obs.cpu().numpy() != 0
+            X = check_array(np.where(m, X, 0), order='C', dtype=be.dtype.type)
+        Xh = be.stage_X(X)
+        if Xh.shape[1] != be.p:
+            raise ValueError('X has %d features, the dictionary has %d' % (Xh.shape[1], be.p))
+        use_G = getattr(self, 'G_agg', None) == 'full' and be.G is not None
+        code = be.transform_masked(Xh, obs, self._plan_kwargs(4096), be.G if use_G else None)
+        return code.cpu().numpy() if on_host else code
 
     def inverse_transform(self, code):
         """code @ components_ for codes of shape (n, n_components), on the device (the reference has no counterpart);

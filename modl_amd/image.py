@@ -145,6 +145,40 @@ def _overlap_finish(acc, g, dtype):
     return out
 
 
+def _grid_patches_masked_pass(d_image, d_obs, g, gcols, row0, nrows, with_mean, with_std):
+    """`_grid_patches_pass` on an image with holes (d_obs (H, W, C) uint8, 1 = observed): (patches, mean, den, obs rows
+    (n, x*y*C) uint8, nobs (n,) int32), the statistics taken over the observed elements (modl_image_grid_patches_masked_*)"""
+    H, W, Cc, x, y, si, sj = g
+    n, kw = nrows * gcols, dict(dtype=d_image.dtype, device=d_image.device)
+    out, mean, den = torch.empty((n, x * y * Cc), **kw), torch.empty((n, Cc), **kw), torch.empty((n, Cc), **kw)
+    obs = torch.empty((n, x * y * Cc), dtype=torch.uint8, device=d_image.device)
+    nobs = torch.empty(n, dtype=torch.int32, device=d_image.device)
+    with torch.cuda.device(d_image.device):
+        check(getattr(lib, 'modl_image_grid_patches_masked_' + _sfx(d_image))(
+            ptr(d_image), H, W, Cc, x, y, si, sj, row0, nrows, int(bool(with_mean)), int(bool(with_std)), ptr(out),
+            x * y * Cc, ptr(mean), ptr(den), ptr(d_obs), ptr(obs), ptr(nobs), stream_ptr(d_image.device)),
+            'modl_image_grid_patches_masked')
+    return out, mean, den, obs, nobs
+
+
+def _overlap_add_weighted(d_patches, use, g, row0, nrows, acc, cnt):
+    H, W, Cc, x, y, si, sj = g
+    with torch.cuda.device(acc.device):
+        check(getattr(lib, 'modl_image_overlap_add_weighted_' + _sfx(d_patches))(
+            ptr(d_patches), d_patches.stride(0), H, W, Cc, x, y, si, sj, row0, nrows, ptr(acc), ptr(use), ptr(cnt),
+            stream_ptr(acc.device)), 'modl_image_overlap_add_weighted')
+
+
+def _inpaint_finish(acc, cnt, d_image, d_obs, keep_observed):
+    H, W, Cc = d_image.shape
+    out = torch.empty_like(d_image)
+    with torch.cuda.device(acc.device):
+        check(getattr(lib, 'modl_image_inpaint_finish_' + _sfx(out))(
+            ptr(acc), ptr(cnt), ptr(d_image), ptr(d_obs), H, W, Cc, int(bool(keep_observed)), ptr(out),
+            stream_ptr(acc.device)), 'modl_image_inpaint_finish')
+    return out
+
+
 PASS_BYTES = 256 << 20      # a pass's patch buffer stays under this: a memory bound, not a tuned value
 
 
@@ -379,8 +413,7 @@ class ImageDictFact(BaseEstimator):
         fitted dictionary, decoded, put back on the image's scale, and the overlapping windows are averaged.  Returns
         an array of the image's shape in the dtype of the fitted dictionary (the input is cast as `transform` casts).
         Image, patches, codes and sums stay on the device, `rows_per_pass` grid rows at a time (default: as many as keep
-        the patch buffer under 256 MB); the result does not depend on it.  The value -1 is ordinary data here:
-        inpainting of missing pixels is out of scope."""
+        the patch buffer under 256 MB); the result does not depend on it.  The value -1 is ordinary data here."""
         check_is_fitted(self, 'dict_fact_')
         be = self.dict_fact_._backend
         g = _grid(np.shape(image), self.patch_shape_[:2], stride)
@@ -399,6 +432,55 @@ class ImageDictFact(BaseEstimator):
             _overlap_add(be.decode(code, mean, den), g, row0, nrows, acc)
         out = _overlap_finish(acc, g, d_image.dtype)
         return out.cpu().numpy() if on_host else out
+
+    def inpaint(self, image, mask=None, stride=1, missing=-1, keep_observed=True, rows_per_pass=None,
+                return_filled=False):
+        """The image with its missing elements filled in from the fitted dictionary.  `mask` is a bool array of shape
+        (H, W) or (H, W, C), True = observed; None: `image != missing`, element by element (`clean_mask`'s rule).  As
+        `reconstruct`, on the same patch grid, but every window is scaled by the statistics of its observed elements
+        and coded on them alone (`CodingMixin.transform` with a mask: a window without a hole is coded exactly as
+        `reconstruct` codes it, one without an observed element is left out); the decoded windows that were used are
+        averaged.  Elements that no used window covers keep their input value, and so do, with `keep_observed`, the
+        observed ones.  Shape, dtype, host / device in -> out and the independence from `rows_per_pass` are those of
+        `reconstruct`; on an image without holes `inpaint(image, keep_observed=False)` is `reconstruct(image)` bit
+        for bit.  With `return_filled` the (H, W) bool array of the pixels that a used window covers comes along.
+        Holes wider than a patch are not filled (the method is not iterated)."""
+        check_is_fitted(self, 'dict_fact_')
+        be = self.dict_fact_._backend
+        g = _grid(np.shape(image), self.patch_shape_[:2], stride)
+        if g[2] != self.patch_shape_[2]:
+            raise ValueError('the image has %d channels, the estimator was fitted on %d' % (g[2], self.patch_shape_[2]))
+        if mask is not None and tuple(np.shape(mask)) not in (g[:2], g[:3]):
+            raise ValueError('mask of shape %s: %s or %s is expected' % (tuple(np.shape(mask)), g[:2], g[:3]))
+        if self.n_components > 1024:
+            raise ValueError('inpaint supports at most 1024 components (one Gram matrix per window), got %d'
+                             % self.n_components)
+        on_host = not isinstance(image, torch.Tensor)
+        d_image = _stage_image(image, be.device, dtype=be.dtype)
+        if mask is None:
+            d_obs = (d_image != missing).to(torch.uint8)
+        else:
+            m = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+            m = (m != 0).to(be.device)
+            d_obs = (m if m.ndim == 3 else m[:, :, None].expand(g[:3])).to(torch.uint8).contiguous()
+        s = ImageDictFact.settings[self.setting]
+        kw = self.dict_fact_._plan_kwargs(4096)
+        G = be.G if self.dict_fact_.G_agg == 'full' else None              # as CodingMixin._transform
+        grows, gcols = _grid_shape(g)
+        acc = torch.zeros(g[:3], dtype=torch.float64, device=be.device)
+        cnt = torch.zeros(g[:2], dtype=torch.int32, device=be.device)
+        for row0, nrows in _passes(grows, gcols, be.p * be.dtype.itemsize, rows_per_pass):
+            patches, mean, den, obs, nobs = _grid_patches_masked_pass(d_image, d_obs, g, gcols, row0, nrows,
+                                                                      s['with_mean'], s['with_std'])
+            code = be.transform_masked(patches, obs, kw, G, nobs=nobs)
+            use = (nobs > 0).to(torch.uint8)
+            _overlap_add_weighted(be.decode(code, mean, den), use, g, row0, nrows, acc, cnt)
+        out = _inpaint_finish(acc, cnt, d_image, d_obs, keep_observed)
+        out = out.cpu().numpy() if on_host else out
+        if not return_filled:
+            return out
+        filled = cnt > 0
+        return out, (filled.cpu().numpy() if on_host else filled)
 
     def stage_test_patches(self, patches):
         """Scaled, flattened test patches as a tensor on the estimator's device: `score_staged` then evaluates the
