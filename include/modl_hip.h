@@ -373,6 +373,24 @@ int modl_somf_plan_update(modl_somf_plan *plan, const modl_somf_desc *desc);
  * update).  Asynchronous on `stream`. */
 int modl_somf_step(modl_somf_plan *plan, const modl_somf_state *st, const modl_somf_batch *bt, void *stream);
 
+/* One MASKED minibatch in one call: DictFact._single_batch_fit (dict_fact.py:495-533) for dense rows with missing entries,
+ * by the algorithm of RecsysDictFact._single_batch_fit (modl/decomposition/recsys.py:147-213) with the elastic-net codes and
+ * atom constraints of DictFact.  d_obs[b][ldo] bytes (1 = observed) goes with bt->d_X[b][ldx]; the row's mask takes the
+ * place of the random feature subset: bt->h_subset must be NULL and bt->s == p, bt->reduction is not read; h_sample_idx,
+ * h_order and w are as in modl_somf_step.  In order, on `stream` (asynchronous):
+ *   codes   every row on its own observed entries - G_i, Dx_i of modl_masked_gram_* (dict_fact.py:594-604 with S = M_i),
+ *           solved as _enet_regression_multi_gram (dict_fact_fast.pyx:33-113) from the warm start code_[h_sample_idx],
+ *           the solver's X being the zero-filled row; chunks of rows keep the Gram matrices under 256 MB (scratch owned
+ *           by the plan, allocated on first use); a row without an observed entry gets a zero code;
+ *   C_      <- (1 - w) C_ + (w / b) code^T code                  (recsys.py:159-160, as modl_gram_axpby_*);
+ *   B_      per feature, as modl_masked_stats_* with n_iter = n_iter_ after this minibatch (recsys.py:175, 182-185);
+ *   D       the dictionary update of modl_somf_step over all p features, with the plan's flag word: an update that
+ *           gives up is reported by modl_somf_status / MODL_ETIMEOUT and counted by modl_somf_persist_recoveries.
+ * MODL_EINVAL before any device work: a plan whose aggregations are not both MODL_AGG_MASKED, optimizer sgd, k > 1024,
+ * a NULL pointer, ldo < p, a subset, b outside 1..max_batch, n_iter <= 0. */
+int modl_somf_masked_step(modl_somf_plan *plan, const modl_somf_state *st, const modl_somf_batch *bt, const uint8_t *d_obs,
+                          int64_t ldo, int64_t *d_feature_n_iter, int64_t n_iter, void *stream);
+
 /* The per-minibatch HOST loop of partial_fit / _single_batch_fit (dict_fact.py:331-337, 495-526) behind the boundary:
  * n_rows rows of d_X in minibatches of batch_size (the last one may be ragged), for each of them
  *   subset  = sampler.yield_subset(reduction)                      (:507)
@@ -573,6 +591,24 @@ int modl_masked_gram_f32(const float *d_Dt, int64_t p, int k, const float *d_X, 
 int modl_masked_gram_f64(const double *d_Dt, int64_t p, int k, const double *d_X, int64_t ldx, const uint8_t *d_obs,
                          int64_t ldo, const int64_t *d_rows, int64_t b, double *d_G, double *d_Dx, int32_t *d_nobs,
                          void *stream);
+/* The statistic B_ from dense rows with missing entries: the per-feature update of RecsysDictFact
+ * (modl/decomposition/recsys.py:175, 182-185) for a minibatch of b dense rows.  Sample ii is row i = d_rows[ii] (d_rows
+ * NULL: i = ii) of d_X[..][ldx] / d_obs[..][ldo] (bytes, 1 = observed), d_code_b[b][k] holds the minibatch's codes.  Per
+ * feature e with c_e = #{ii : d_obs[i][e] != 0} (-> d_count[e]; d_count may be NULL):
+ *   c_e = 0: d_Bt[e][:] and d_feature_n_iter[e] are left untouched, bit for bit;  otherwise
+ *   d_feature_n_iter[e] += c_e;   w_e = min(1, w (c_e / b) (n_iter / d_feature_n_iter[e]))     (f64, in that order)
+ *   d_Bt[e][:] <- (1 - w_e) d_Bt[e][:] + (w_e / c_e) sum_{ii : e observed} d_X[i][e] d_code_b[ii][:]
+ * (b = 1: the reference's w_B; every row observed everywhere: w_e = w, DictFact._update_B, dict_fact.py:567-575).  The
+ * product runs on the matrix cores in the dtype; values of d_X at unobserved positions never reach it (they may be
+ * NaN).  Two launches: the product launch only reads d_feature_n_iter, the launch behind it writes it; no atomics, no
+ * scratch, the same bits from run to run.  1 <= k <= 1024, p >= 1; a NULL pointer (d_rows and d_count apart), k out of
+ * range, ldx < p, ldo < p or b < 0 -> MODL_EINVAL before any device work; b = 0 does nothing. */
+int modl_masked_stats_f32(const float *d_X, int64_t ldx, const uint8_t *d_obs, int64_t ldo, const int64_t *d_rows,
+                          int64_t b, int64_t p, int k, const float *d_code_b, float *d_Bt, int64_t *d_feature_n_iter,
+                          int32_t *d_count, double w, int64_t n_iter, void *stream);
+int modl_masked_stats_f64(const double *d_X, int64_t ldx, const uint8_t *d_obs, int64_t ldo, const int64_t *d_rows,
+                          int64_t b, int64_t p, int k, const double *d_code_b, double *d_Bt, int64_t *d_feature_n_iter,
+                          int32_t *d_count, double w, int64_t n_iter, void *stream);
 /* modl_image_grid_patches_* on an image with holes: d_obs_image[H][W][C] bytes, 1 = observed.  Per patch, channel c with
  * the observed window elements O_c, n_c = |O_c|, N = x y:  mean_c = (sum_{O_c} v) / n_c (with_mean and n_c > 0, else
  * 0); observed elements are centred, unobserved ones written as 0; with_std: den_c = norm_c sqrt(C) with norm_c =
@@ -587,6 +623,19 @@ int modl_image_grid_patches_masked_f64(const double *d_image, int64_t H, int64_t
                                        int sj, int64_t row0, int64_t nrows, int with_mean, int with_std, double *d_out,
                                        int64_t ldo, double *d_mean, double *d_den, const uint8_t *d_obs_image,
                                        uint8_t *d_obs_out, int32_t *d_nobs, void *stream);
+/* modl_image_grid_patches_masked_* at the origins of an index list instead of a grid (the masked twin of
+ * modl_image_patches_*, modl/feature_extraction/image.py:54-63): window r sits at (d_idx3[r][0], d_idx3[r][1]) and spans
+ * all channels - z must equal C (MODL_EINVAL otherwise) and the channel origin d_idx3[r][2] must be 0 (it lives on the
+ * device and is not read).  d_mean[n][C], d_den[n][C], d_obs_out[n][x*y*C], d_nobs[n] as there.  The per-window device
+ * code is the grid kernel's: a window at a grid origin gives that kernel's row, mean, den, mask row and count bit for bit. */
+int modl_image_patches_masked_f32(const float *d_image, int64_t H, int64_t W, int64_t C, const int64_t *d_idx3, int64_t n,
+                                  int x, int y, int z, int with_mean, int with_std, float *d_out, int64_t ldo,
+                                  float *d_mean, float *d_den, const uint8_t *d_obs_image, uint8_t *d_obs_out,
+                                  int32_t *d_nobs, void *stream);
+int modl_image_patches_masked_f64(const double *d_image, int64_t H, int64_t W, int64_t C, const int64_t *d_idx3, int64_t n,
+                                  int x, int y, int z, int with_mean, int with_std, double *d_out, int64_t ldo,
+                                  double *d_mean, double *d_den, const uint8_t *d_obs_image, uint8_t *d_obs_out,
+                                  int32_t *d_nobs, void *stream);
 /* modl_image_overlap_add_* over the patches q of the pass with d_use[q] != 0 only; d_cnt[H][W] (int32, zeroed by the
  * caller before the first pass) counts them per pixel.  The same gather in grid order: sums and counts do not depend
  * on how the grid rows are cut into passes. */

@@ -159,6 +159,10 @@ def bind(lib):
         _sig('modl_masked_gram_' + _sfx, C.c_int, _vp, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp)
         _sig('modl_image_grid_patches_masked_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int,
              _i64, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp)
+        _sig('modl_masked_stats_' + _sfx, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, _f64,
+             _i64, _vp)
+        _sig('modl_image_patches_masked_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, _i64, C.c_int, C.c_int, C.c_int,
+             C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp)
         _sig('modl_image_overlap_add_weighted_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int,
              C.c_int, _i64, _i64, _vp, _vp, _vp, _vp)
         _sig('modl_image_inpaint_finish_' + _sfx, C.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp)
@@ -183,6 +187,7 @@ def bind(lib):
     _sig('modl_somf_code_and_partials', C.c_int, _vp, _P(SomfState), _P(SomfBatch), _vp, _vp)
     _sig('modl_somf_apply_and_update_dict', C.c_int, _vp, _P(SomfState), _P(SomfBatch), _vp, _vp)
     _sig('modl_somf_step', C.c_int, _vp, _P(SomfState), _P(SomfBatch), _vp)
+    _sig('modl_somf_masked_step', C.c_int, _vp, _P(SomfState), _P(SomfBatch), _vp, _i64, _vp, _i64, _vp)
     _sig('modl_somf_partial_fit_chunk', C.c_int, _vp, _P(SomfState), _vp, _i64, _i64, C.c_int32, _vp, _vp, _vp, _P(_i64), _f64,
          _f64, _vp, _vp, _P(_i64), _vp)
     _sig('modl_somf_head_elems', C.c_int, _vp, _P(_i64))

@@ -274,22 +274,16 @@ __global__ __launch_bounds__(256) void image_overlap_finish_kernel(const double 
 // statistics of a channel are taken over its n_c OBSERVED positions: mean_c = sum / n_c; the norm of the centred
 // observed values times sqrt(x y / n_c) estimates the norm of the full window (1 if it is 0 or n_c = 0); unobserved
 // elements of the row are 0.  obs_out[q][:] is the window of obs in the row's element order, nobs[q] its sum.
+// One window of an image with holes, by one wavefront: the device code both masked patch kernels share (the grid
+// kernel computes the origin, the index-list kernel reads it), so that the same origin gives the same bits.
 template <typename T>
-__global__ __launch_bounds__(256) void image_grid_patches_masked_kernel(
-    const T *__restrict__ img, const uint8_t *__restrict__ obs, int64_t C, GridAxis gi, GridAxis gj, int64_t row0,
-    int64_t n, int with_mean, int with_std, T sqrt_z, T *__restrict__ out, int64_t ldo, T *__restrict__ mean,
-    T *__restrict__ den, uint8_t *__restrict__ obs_out, int32_t *__restrict__ nobs) {
-    __shared__ T s_mean[4][kPatchMaxChannels];
-    __shared__ T s_den[4][kPatchMaxChannels];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int64_t q = (int64_t)blockIdx.x * 4 + wid;
-    if (q >= n) return;                                       // wave-uniform; no block barrier below
-    const int64_t i0 = gi.origin(row0 + q / gj.g), j0 = gj.origin(q % gj.g), W = gj.L;
-    const int z = (int)C, x = gi.x, y = gj.x, xy = x * y, yz = y * z, P = xy * z;
-    const T *base = img + (i0 * W + j0) * C;
-    const uint8_t *obase = obs + (i0 * W + j0) * C;
-    T *o = out + q * ldo;
-    uint8_t *oo = obs_out + q * (int64_t)P;
+__device__ __forceinline__ void masked_patch_window(const T *__restrict__ base, const uint8_t *__restrict__ obase,
+                                                    int64_t W, int64_t C, int x, int y, int with_mean, int with_std,
+                                                    T sqrt_z, T *s_mean, T *s_den, T *__restrict__ o,
+                                                    uint8_t *__restrict__ oo, int32_t *__restrict__ nobs_q,
+                                                    T *__restrict__ mean_q, T *__restrict__ den_q) {
+    const int lane = threadIdx.x & 63;
+    const int z = (int)C, xy = x * y, yz = y * z, P = xy * z;
     int cnt = 0;
     for (int e = lane; e < P; e += 64) {
         const int xi = e / yz, rem = e - xi * yz;
@@ -298,11 +292,11 @@ __global__ __launch_bounds__(256) void image_grid_patches_masked_kernel(
         cnt += on;
     }
     cnt = (int)wave_sum((double)cnt);
-    if (lane == 0) nobs[q] = cnt;
+    if (lane == 0) *nobs_q = cnt;
     if (cnt == P) {                                           // wave-uniform: the clean window
         if (!(with_mean || with_std))
-            for (int c = lane; c < z; c += 64) { s_mean[wid][c] = 0; s_den[wid][c] = 1; }
-        patch_row<T>(base, W, C, x, y, z, with_mean, with_std, sqrt_z, s_mean[wid], s_den[wid], o);
+            for (int c = lane; c < z; c += 64) { s_mean[c] = 0; s_den[c] = 1; }
+        patch_row<T>(base, W, C, x, y, z, with_mean, with_std, sqrt_z, s_mean, s_den, o);
     } else {
         for (int c = 0; c < z; ++c) {
             T s = 0;
@@ -328,20 +322,55 @@ __global__ __launch_bounds__(256) void image_grid_patches_masked_kernel(
                 if (sd == (T)0) sd = 1;
                 d = sd * sqrt_z;
             }
-            if (lane == 0) { s_mean[wid][c] = m; s_den[wid][c] = d; }
+            if (lane == 0) { s_mean[c] = m; s_den[c] = d; }
         }
         __builtin_amdgcn_wave_barrier();
         for (int e = lane; e < P; e += 64) {
             const int xi = e / yz, rem = e - xi * yz, c = rem % z;
             const int64_t at = (int64_t)xi * W * C + rem;
             T v = base[at];
-            if (with_mean) v -= s_mean[wid][c];
-            if (with_std) v /= s_den[wid][c];
+            if (with_mean) v -= s_mean[c];
+            if (with_std) v /= s_den[c];
             o[e] = obase[at] != 0 ? v : (T)0;
         }
     }
-    for (int c = lane; c < z; c += 64) { mean[q * C + c] = s_mean[wid][c]; den[q * C + c] = s_den[wid][c]; }
+    for (int c = lane; c < z; c += 64) { mean_q[c] = s_mean[c]; den_q[c] = s_den[c]; }
 }
+
+template <typename T>
+__global__ __launch_bounds__(256) void image_grid_patches_masked_kernel(
+    const T *__restrict__ img, const uint8_t *__restrict__ obs, int64_t C, GridAxis gi, GridAxis gj, int64_t row0,
+    int64_t n, int with_mean, int with_std, T sqrt_z, T *__restrict__ out, int64_t ldo, T *__restrict__ mean,
+    T *__restrict__ den, uint8_t *__restrict__ obs_out, int32_t *__restrict__ nobs) {
+    __shared__ T s_mean[4][kPatchMaxChannels];
+    __shared__ T s_den[4][kPatchMaxChannels];
+    const int wid = threadIdx.x >> 6;
+    const int64_t q = (int64_t)blockIdx.x * 4 + wid;
+    if (q >= n) return;                                       // wave-uniform; no block barrier below
+    const int64_t i0 = gi.origin(row0 + q / gj.g), j0 = gj.origin(q % gj.g), W = gj.L;
+    masked_patch_window<T>(img + (i0 * W + j0) * C, obs + (i0 * W + j0) * C, W, C, gi.x, gj.x, with_mean, with_std, sqrt_z,
+                           s_mean[wid], s_den[wid], out + q * ldo, obs_out + q * ((int64_t)gi.x * gj.x * C), nobs + q,
+                           mean + q * C, den + q * C);
+}
+
+// the same at the origins (i, j) of an index list idx3[n][3] (modl_image_patches_masked_*: windows span all channels,
+// the third entry of an origin is not read)
+template <typename T>
+__global__ __launch_bounds__(256) void image_patches_masked_kernel(
+    const T *__restrict__ img, const uint8_t *__restrict__ obs, int64_t W, int64_t C, const int64_t *__restrict__ idx3,
+    int64_t n, int x, int y, int with_mean, int with_std, T sqrt_z, T *__restrict__ out, int64_t ldo,
+    T *__restrict__ mean, T *__restrict__ den, uint8_t *__restrict__ obs_out, int32_t *__restrict__ nobs) {
+    __shared__ T s_mean[4][kPatchMaxChannels];
+    __shared__ T s_den[4][kPatchMaxChannels];
+    const int wid = threadIdx.x >> 6;
+    const int64_t q = (int64_t)blockIdx.x * 4 + wid;
+    if (q >= n) return;                                       // wave-uniform; no block barrier below
+    const int64_t i0 = idx3[q * 3 + 0], j0 = idx3[q * 3 + 1];
+    masked_patch_window<T>(img + (i0 * W + j0) * C, obs + (i0 * W + j0) * C, W, C, x, y, with_mean, with_std, sqrt_z,
+                           s_mean[wid], s_den[wid], out + q * ldo, obs_out + q * ((int64_t)x * y * C), nobs + q,
+                           mean + q * C, den + q * C);
+}
+
 
 // image_overlap_add_kernel over the patches of the pass whose use[q] != 0 only; cnt[H][W] counts them per pixel (by
 // the thread of channel 0).  The same gather in grid order: sums and counts do not depend on the cut into passes.
@@ -452,6 +481,20 @@ int grid_patches_masked_impl(hipStream_t stream, const T *img, const uint8_t *ob
     if (n == 0) return MODL_OK;
     hipLaunchKernelGGL((image_grid_patches_masked_kernel<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, stream, img, obs,
                        C, gi, gj, row0, n, with_mean, with_std, (T)sqrt((double)C), out, ldo, mean, den, obs_out, nobs);
+    MODL_LAUNCH_CHECK();
+    return MODL_OK;
+}
+
+template <typename T>
+int patches_masked_impl(hipStream_t stream, const T *img, const uint8_t *obs, int64_t H, int64_t W, int64_t C,
+                        const int64_t *idx3, int64_t n, int x, int y, int z, int with_mean, int with_std, T *out,
+                        int64_t ldo, T *mean, T *den, uint8_t *obs_out, int32_t *nobs) {
+    if (!img || !obs || !idx3 || !out || !mean || !den || !obs_out || !nobs || n < 0 || x <= 0 || y <= 0 || x > H ||
+        y > W || C <= 0 || C > kPatchMaxChannels || z != C || (int64_t)x * y > INT32_MAX / C || ldo < (int64_t)x * y * C)
+        return MODL_EINVAL;
+    if (n == 0) return MODL_OK;
+    hipLaunchKernelGGL((image_patches_masked_kernel<T>), dim3((unsigned)cdiv(n, 4)), dim3(256), 0, stream, img, obs, W, C,
+                       idx3, n, x, y, with_mean, with_std, (T)sqrt((double)C), out, ldo, mean, den, obs_out, nobs);
     MODL_LAUNCH_CHECK();
     return MODL_OK;
 }
@@ -601,6 +644,13 @@ int modl_image_grid_shape(int64_t H, int64_t W, int64_t x, int64_t y, int64_t si
                                              void *stream) {                                                          \
         return grid_patches_masked_impl<T>((hipStream_t)stream, d_image, d_obs_image, H, W, C, x, y, si, sj, row0,    \
                                            nrows, with_mean, with_std, d_out, ldo, d_mean, d_den, d_obs_out, d_nobs); \
+    }                                                                                                                 \
+    int modl_image_patches_masked_##SFX(const T *d_image, int64_t H, int64_t W, int64_t C, const int64_t *d_idx3,     \
+                                        int64_t n, int x, int y, int z, int with_mean, int with_std, T *d_out,        \
+                                        int64_t ldo, T *d_mean, T *d_den, const uint8_t *d_obs_image,                 \
+                                        uint8_t *d_obs_out, int32_t *d_nobs, void *stream) {                          \
+        return patches_masked_impl<T>((hipStream_t)stream, d_image, d_obs_image, H, W, C, d_idx3, n, x, y, z,         \
+                                      with_mean, with_std, d_out, ldo, d_mean, d_den, d_obs_out, d_nobs);             \
     }                                                                                                                 \
     int modl_image_overlap_add_weighted_##SFX(const T *d_patches, int64_t ldp, int64_t H, int64_t W, int64_t C, int x, \
                                               int y, int si, int sj, int64_t row0, int64_t nrows, double *d_acc,      \

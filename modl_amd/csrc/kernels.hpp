@@ -91,6 +91,21 @@ int launch_update_G_average(hipStream_t stream, T *G_average, const int64_t *idx
 template <typename T>
 int launch_transpose(hipStream_t stream, const T *in, T *out, int64_t rows, int64_t cols);
 
+// ---- masked_stats.hip -------------------------------------------------------
+// B_ from dense rows with missing entries (modl_masked_stats_*), and the two small launches around the per-row solve of
+// a masked minibatch: squared norms of the zero-filled rows; zero codes for the rows nobody observed + the minibatch's
+// codes compact in codeb[b][k]
+template <typename T>
+int launch_masked_stats(hipStream_t stream, const T *X, int64_t ldx, const uint8_t *obs, int64_t ldo, const int64_t *rows,
+                        int64_t b, int64_t p, int k, const T *code_b, T *Bt, int64_t *fni, int32_t *count, double w,
+                        int64_t n_iter);
+template <typename T>
+int launch_masked_row_norm2(hipStream_t stream, const T *X, int64_t ldx, const uint8_t *obs, int64_t ldo, int64_t p, int b,
+                            T *out);
+template <typename T>
+int launch_masked_codes_finish(hipStream_t stream, T *code, const int64_t *idx, const int32_t *nobs, int b, int k,
+                               T *codeb);
+
 // ---- bcd.hip ----------------------------------------------------------------
 // Work that rides along the block launches of the fused dictionary update, on the compute units that update
 // leaves idle: the statistics update of the rows of Bt that were NOT sampled,

@@ -326,6 +326,8 @@ struct modl_somf_plan {
     void *Gslots = nullptr;            // zero-padded copies of per-sample Gram matrices (lazily allocated, launch_cd_per_sample)
     size_t Gslots_bytes = 0;
     void *own_head = nullptr;          // [k*k + p*k] (lazily allocated): the head buffer of modl_somf_step_dist
+    void *masked_ws = nullptr;         // modl_somf_masked_step (lazily allocated, grown on demand): a chunk's per-row Gram
+    size_t masked_ws_bytes = 0;        // matrices, their Cholesky factors (ridge, 128 < k <= 512) and the rows' counts
     bool ride_pending = false;         // single-GPU step: the B_ update of the rows that were not sampled rides along
     StatsRider rider{};                // the dictionary update (see StatsRider)
     int32_t step_id = 0;
@@ -1229,6 +1231,7 @@ void modl_somf_plan_destroy(modl_somf_plan *pl) {
     if (pl->Bsum) (void)hipFree(pl->Bsum);
     if (pl->Gslots) (void)hipFree(pl->Gslots);
     if (pl->own_head) (void)hipFree(pl->own_head);
+    if (pl->masked_ws) (void)hipFree(pl->masked_ws);
     if (pl->pflags) (void)hipHostFree(pl->pflags);
     for (int i = 0; i < kStageSlots; ++i) {
         if (pl->hstage[i]) (void)hipHostFree(pl->hstage[i]);
@@ -1305,6 +1308,126 @@ int modl_somf_step(modl_somf_plan *pl, const modl_somf_state *st, const modl_som
 }
 
 }  // extern "C"
+
+namespace {
+
+inline int masked_gram_call(const float *Dt, int64_t p, int k, const float *X, int64_t ldx, const uint8_t *obs, int64_t ldo,
+                            int64_t b, float *G, float *Dx, int32_t *nobs, void *st) {
+    return modl_masked_gram_f32(Dt, p, k, X, ldx, obs, ldo, nullptr, b, G, Dx, nobs, st);
+}
+inline int masked_gram_call(const double *Dt, int64_t p, int k, const double *X, int64_t ldx, const uint8_t *obs, int64_t ldo,
+                            int64_t b, double *G, double *Dx, int32_t *nobs, void *st) {
+    return modl_masked_gram_f64(Dt, p, k, X, ldx, obs, ldo, nullptr, b, G, Dx, nobs, st);
+}
+inline int gram_axpby_call(const float *rows, int64_t b, int k, float *C, float beta, float alpha, void *st) {
+    return modl_gram_axpby_f32(rows, b, k, C, beta, alpha, st);
+}
+inline int gram_axpby_call(const double *rows, int64_t b, int k, double *C, double beta, double alpha, void *st) {
+    return modl_gram_axpby_f64(rows, b, k, C, beta, alpha, st);
+}
+
+// rows per masked solve: their Gram matrices stay under 256 MB (a memory bound, as HipBackend.masked_chunk_rows)
+inline int64_t masked_chunk_rows(int k, size_t tsz) {
+    const int64_t r = (int64_t)((size_t)(256u << 20) / ((size_t)k * k * tsz));
+    return r < 1 ? 1 : (r > 4096 ? 4096 : r);
+}
+
+// One masked minibatch (the dense-row form of recsys.py:147-213): every row coded on its own observed
+// entries with a Gram matrix of its own (dict_fact.py:594-604 with S = the row's mask; _enet_regression_multi_gram from
+// the warm start code_[idx]), C_ as recsys.py:159-160, B_ per feature (masked_stats.hip), then the dictionary update of
+// modl_somf_step over all p features - phase2 itself, with the plan's flag word.
+template <typename T>
+int masked_step(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_batch *bt, const uint8_t *obs, int64_t ldo,
+                int64_t *fni, int64_t n_iter, hipStream_t st) {
+    const modl_somf_desc &d = pl->d;
+    const int k = d.k, b = bt->b;
+    const int64_t p = d.p;
+    // the chunk's scratch: [c][k][k] Gram matrices (+ as many factors for the mid-size ridge systems) + [b] counts
+    const int64_t crows = std::min<int64_t>(masked_chunk_rows(k, sizeof(T)), d.max_batch);
+    const bool need_F = d.code_l1_ratio == 0.0 && !chol_blocked(k, sizeof(T), false) && !ridge_small_applies<T>(k);
+    const size_t g_bytes = align_up(sizeof(T) * (size_t)crows * k * k, 256);
+    const size_t need = g_bytes * (need_F ? 2 : 1) + align_up(sizeof(int32_t) * (size_t)d.max_batch, 256);
+    if (pl->masked_ws_bytes < need) {
+        if (pl->masked_ws) {                                   // (a larger max_batch after modl_somf_plan_update)
+            MODL_HIP(hipStreamSynchronize(st));
+            (void)hipFree(pl->masked_ws);
+            pl->masked_ws = nullptr;
+            pl->masked_ws_bytes = 0;
+        }
+        MODL_HIP(hipMalloc(&pl->masked_ws, need));
+        pl->masked_ws_bytes = need;
+    }
+    modl_somf_batch mb = *bt;                                  // the mask takes the subset's place
+    mb.s = (int32_t)p; mb.h_subset = nullptr; mb.h_w_sample = nullptr; mb.b_global = b;
+    MODL_TRY(stage_batch<T>(pl, &mb, st));
+    ++pl->prof_step;
+    pl->ride_pending = false;
+    pl->head_pending = false;
+    char *P = pl->dws + pl->off_params;
+    const int64_t *d_idx = pl->has_idx ? reinterpret_cast<const int64_t *>(P + pl->po_idx) : nullptr;
+    const T *X = static_cast<const T *>(bt->d_X);
+    const T *Dt = static_cast<const T *>(stt->d_Dt);
+    T *code = static_cast<T *>(stt->d_code);
+    T *xnorm = reinterpret_cast<T *>(pl->dws + pl->off_xnorm);
+    T *Dx = reinterpret_cast<T *>(pl->dws + pl->off_Dx);
+    T *H0 = reinterpret_cast<T *>(pl->dws + pl->off_H0);
+    T *codeb = reinterpret_cast<T *>(pl->dws + pl->off_codeb);
+    T *Gc = static_cast<T *>(pl->masked_ws);
+    T *Fc = need_F ? reinterpret_cast<T *>(static_cast<char *>(pl->masked_ws) + g_bytes)
+                   : reinterpret_cast<T *>(pl->dws + pl->off_F);
+    int32_t *nobs = reinterpret_cast<int32_t *>(static_cast<char *>(pl->masked_ws) + g_bytes * (need_F ? 2 : 1));
+    int32_t *d_sweeps = reinterpret_cast<int32_t *>(pl->dws + pl->off_sweeps);
+    if (pl->hist) d_sweeps = pl->hist + (pl->hist_n++ % pl->hist_cap) * (int64_t)d.max_batch;
+    pl->last_sweeps_ptr = d_sweeps;
+    pl->last_b = b;
+    if (d.code_l1_ratio != 0.0) MODL_TRY(launch_masked_row_norm2<T>(st, X, bt->ldx, obs, ldo, p, b, xnorm));
+    for (int64_t r0 = 0; r0 < b; r0 += crows) {
+        const int c = (int)std::min<int64_t>(crows, b - r0);
+        {
+            ProfScope ps(pl, st, SEC_CODE_GEMM);
+            MODL_TRY(masked_gram_call(Dt, p, k, X + r0 * bt->ldx, bt->ldx, obs + r0 * ldo, ldo, c, Gc, Dx + r0 * k,
+                                      nobs + r0, st));
+            ps.launches += 1;
+        }
+        {
+            ProfScope ps(pl, st, SEC_CODE_SOLVE);
+            // per-row matrices in chunk order: sample ii of the chunk uses Gc[ii]; rows d_idx[r0 + ii] of code_ are the warm
+            // starts and receive the solutions
+            MODL_TRY(solve_codes<T>(pl, st, Gc, (int64_t)k * k, nullptr, Dx + r0 * k, xnorm + r0,
+                                    d_idx ? code : code + r0 * k, d_idx ? d_idx + r0 : nullptr, c, d_sweeps + r0,
+                                    &ps.launches, H0, Fc));
+        }
+    }
+    {
+        ProfScope ps(pl, st, SEC_STATS_GEMM);
+        MODL_TRY(launch_masked_codes_finish<T>(st, code, d_idx, nobs, b, k, codeb));
+        MODL_TRY(gram_axpby_call(codeb, b, k, static_cast<T *>(stt->d_C), (T)(1.0 - bt->w), (T)(bt->w / (double)b), st));
+        MODL_TRY(launch_masked_stats<T>(st, X, bt->ldx, obs, ldo, nullptr, b, p, k, codeb, static_cast<T *>(stt->d_Bt), fni,
+                                        nullptr, bt->w, n_iter));
+        ps.launches += 4;
+    }
+    return phase2<T>(pl, stt, &mb, nullptr, st);
+}
+
+}  // namespace
+
+extern "C" int modl_somf_masked_step(modl_somf_plan *pl, const modl_somf_state *st, const modl_somf_batch *bt,
+                                     const uint8_t *d_obs, int64_t ldo, int64_t *d_feature_n_iter, int64_t n_iter,
+                                     void *stream) {
+    if (!pl || !st || !bt || !d_obs || !d_feature_n_iter) return MODL_EINVAL;
+    const modl_somf_desc &d = pl->d;
+    if (d.G_agg != MODL_AGG_MASKED || d.Dx_agg != MODL_AGG_MASKED || d.optimizer != MODL_OPT_VARIATIONAL || d.k > 1024)
+        return MODL_EINVAL;
+    if (ldo < d.p || bt->h_subset || bt->s != d.p || bt->b <= 0 || bt->b > d.max_batch || !bt->d_X || bt->ldx < d.p ||
+        !bt->h_order || n_iter <= 0)
+        return MODL_EINVAL;
+    if (!st->d_Dt || !st->d_Bt || !st->d_C || !st->d_code || !st->d_comp_norm) return MODL_EINVAL;
+    DeviceScope dev(pl);
+    pl->ahead = false;                              // (a minibatch staged ahead belongs to an abandoned chunk loop)
+    MODL_TRY(persist_gate(pl));
+    return DISPATCH(pl, masked_step<float>(pl, st, bt, d_obs, ldo, d_feature_n_iter, n_iter, (hipStream_t)stream),
+                    masked_step<double>(pl, st, bt, d_obs, ldo, d_feature_n_iter, n_iter, (hipStream_t)stream));
+}
 
 // ---- the collective inside the library: RCCL through its C API, resolved at run time -------------------------------
 // (librccl.so is looked up with dlopen: a process that already holds RCCL - e.g. through torch.distributed - gets that

@@ -82,6 +82,7 @@ class HipBackend:
         self.Dt, self.Bt, self.C = z(p, k), z(p, k), z(k, k)
         self.code = torch.ones((n_samples, k), dtype=td, device=dev)        # dict_fact.py:470
         self.comp_norm = z(k)
+        self.feature_n_iter = torch.zeros(p, dtype=torch.int64, device=dev)   # observers seen per feature (masked fits)
         self.G = z(k, k) if desc_kwargs['G_agg'] == 'full' else None
         self.Dx_average = z(n_samples, k) if desc_kwargs['Dx_agg'] == 'average' else None
         self.G_average = None
@@ -203,7 +204,10 @@ class HipBackend:
 
     def set(self, name, value):
         cur = getattr(self, name)
-        new = to_device(value, self.device, dtype=self.dtype)
+        if name == 'feature_n_iter':                     # the one integer state array
+            new = torch.from_numpy(np.ascontiguousarray(value, dtype=np.int64)).to(self.device)
+        else:
+            new = to_device(value, self.device, dtype=self.dtype)
         if cur is not None and tuple(cur.shape) == tuple(new.shape):
             cur.copy_(new)
         else:
@@ -322,6 +326,16 @@ class HipBackend:
         bt, keep = self._batch(Xh, batch, idx, subset, order, w_sample, w, reduction, b_global)
         st = self._state()
         check(lib.modl_somf_step(self.plan, C.byref(st), C.byref(bt), stream_ptr(self.device)), 'modl_somf_step')
+
+    def masked_step(self, Xh, obs, batch, idx, order, w, n_iter):
+        """One masked minibatch in one call (modl_somf_masked_step): the rows `batch` of Xh (n, p) and of obs (n, p)
+        uint8, 1 = observed; every row is coded on its own observed entries, `feature_n_iter` weighs B_ per feature."""
+        bt, keep = self._batch(Xh, batch, idx, None, order, None, w, 1.0, batch.stop - batch.start)
+        rows = obs[batch]
+        st = self._state()
+        check(lib.modl_somf_masked_step(self.plan, C.byref(st), C.byref(bt), ptr(rows), obs.stride(0),
+                                        ptr(self.feature_n_iter), int(n_iter), stream_ptr(self.device)),
+              'modl_somf_masked_step')
 
     def fit_chunk(self, Xh, batch_size, sample_indices, sampler, np_random_state, n_iter, learning_rate, reduction,
                   b_global=None, comm=None):
@@ -910,13 +924,17 @@ class DictFact(CodingMixin, BaseEstimator):
     local_C_ = _state_property('C', summed=True, local=True)
     code_ = _state_property('code')
     comp_norm_ = _state_property('comp_norm')
+    feature_n_iter_ = _state_property('feature_n_iter')     # int64[p]: observers each feature has had in masked minibatches
     G_ = _state_property('G')
     Dx_average_ = _state_property('Dx_average')
     G_average_ = _state_property('G_average')
 
     # ------------------------------------------------------------------ fit
-    def fit(self, X):
-        """dict_fact.py:286-311"""
+    def fit(self, X, mask=None):
+        """dict_fact.py:286-311.  With `mask` (n, p), True = observed: `partial_fit(X, mask=)` on every epoch, the mask
+        permuted along with X; the dictionary starts from the zero-filled first rows."""
+        if mask is not None:
+            return self._fit_masked(X, mask)
         X = _as_float_array(X)
         if self.dict_init is None:
             dict_init = X
@@ -931,11 +949,104 @@ class DictFact(CodingMixin, BaseEstimator):
             Xh = self._backend.take_rows(Xh, permutation)
         return self
 
-    def partial_fit(self, X, sample_indices=None, _sync=True):
+    # ------------------------------------------------------- missing entries
+    def _check_masked_fit(self):
+        """what a fit with a mask supports; everything else is a ValueError before any device work"""
+        if self.G_agg != 'masked' or self.Dx_agg != 'masked':
+            raise ValueError("a fit with a mask needs G_agg = Dx_agg = 'masked' (every row has its own Gram matrix), "
+                             "got G_agg=%r, Dx_agg=%r" % (self.G_agg, self.Dx_agg))
+        if self.optimizer != 'variational':
+            raise ValueError("a fit with a mask needs optimizer='variational', got %r" % (self.optimizer,))
+        if self.n_components > MASKED_MAX_COMPONENTS:
+            raise ValueError('a fit with a mask supports at most %d components (one Gram matrix per row), got %d'
+                             % (MASKED_MAX_COMPONENTS, self.n_components))
+        if self._world() > 1:
+            raise ValueError('a fit with a mask runs on one rank only (got %d ranks)' % self._world())
+
+    @staticmethod
+    def _masked_inputs(X, mask):
+        """(X, the mask as uint8), each on the side it came from.  Host input is zero-filled at its unobserved entries -
+        they may hold anything, NaN included, which the validation would refuse; a tensor is passed on untouched: every
+        kernel of the masked step selects on the mask, no zero-filled copy of X is made."""
+        if len(np.shape(X)) != 2 or tuple(np.shape(mask)) != tuple(np.shape(X)):
+            raise ValueError('mask of shape %s does not match X of shape %s (n_samples, n_features)'
+                             % (tuple(np.shape(mask)), tuple(np.shape(X))))
+        if isinstance(mask, torch.Tensor):
+            obs = mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
+        else:
+            obs = np.ascontiguousarray(np.asarray(mask) != 0).view(np.uint8)
+        if isinstance(X, torch.Tensor):
+            X = _as_float_array(X)
+        else:
+            m = obs.cpu().numpy() if isinstance(obs, torch.Tensor) else obs
+            X = check_array(np.where(m != 0, X, 0), order='C', dtype=[np.float32, np.float64])
+        return X, obs
+
+    def _fit_masked(self, X, mask):
+        self._check_masked_fit()
+        X, obs = self._masked_inputs(X, mask)
+        if self.dict_init is not None:
+            dict_init = check_array(self.dict_init, dtype=(np.float32 if X.dtype in (np.float32, torch.float32)
+                                                           else np.float64))
+        elif isinstance(X, torch.Tensor):                 # the zero-filled first rows (a tensor's holes may be NaN)
+            k = self.n_components
+            m = obs[:k] if isinstance(obs, torch.Tensor) else torch.from_numpy(obs[:k])
+            dict_init = torch.where(m.to(X.device) != 0, X[:k], torch.zeros((), dtype=X.dtype, device=X.device))
+        else:
+            dict_init = X
+        self.prepare(n_samples=X.shape[0], X=dict_init)
+        be = self._backend
+        Xh = be.stage_X(X)
+        oh = (obs if isinstance(obs, torch.Tensor) else torch.from_numpy(obs)).to(be.device)
+        for _ in range(self.n_epochs):
+            self.partial_fit(Xh, mask=oh)
+            permutation = self.shuffle()
+            Xh, oh = be.take_rows(Xh, permutation), oh[torch.from_numpy(np.asarray(permutation)).to(be.device)]
+        return self
+
+    def _partial_fit_masked(self, X, sample_indices, _sync, mask):
+        """partial_fit on rows with missing entries: the per-minibatch loop, every minibatch one
+        modl_somf_masked_step.  The row's mask takes the place of the random feature subset: `reduction` is not used and
+        the feature sampler is not drawn; X and the mask are staged whole."""
+        self._check_masked_fit()
+        X, obs = self._masked_inputs(X, mask)
+        be = self._backend
+        if X.shape[1] != be.p:
+            raise ValueError('X has %d features, expected %d' % (X.shape[1], be.p))
+        if self.batch_size > be._desc_kw['max_batch']:
+            be.update_plan(self._plan_kwargs(self.batch_size))
+        t0 = time.perf_counter()
+        self._cb_time = 0.0
+        Xh = be.stage_X(X)
+        oh = (obs if isinstance(obs, torch.Tensor) else torch.from_numpy(obs)).to(be.device).contiguous()
+        for batch in gen_batches(Xh.shape[0], self.batch_size):
+            if self.verbose and self.verbose_iter_ and self.n_iter_ >= self.verbose_iter_[0]:
+                tc = time.perf_counter()
+                print('Iteration %i' % self.n_iter_)
+                self.verbose_iter_ = self.verbose_iter_[1:]
+                self._callback()
+                self._cb_time += time.perf_counter() - tc
+            idx = get_sub_slice(sample_indices, batch)
+            b = batch.stop - batch.start
+            self.n_iter_ += b
+            self.sample_n_iter_[idx] += 1
+            w = batch_weight(self.n_iter_, b, self.learning_rate, 0)
+            order = self.random_state.permutation(self.n_components)       # dict_fact.py:672
+            be.masked_step(Xh, oh, batch, idx, order, w, self.n_iter_)
+        if _sync:
+            be.synchronize()
+        self.time_ += time.perf_counter() - t0 - self._cb_time
+        return self
+
+    def partial_fit(self, X, sample_indices=None, _sync=True, mask=None):
         """dict_fact.py:313-337.  X: numpy array or device tensor (n, n_features).
         `_sync=False` (not part of the reference's surface) returns as soon as the minibatches are enqueued on
         the stream, so that a streaming caller can overlap the production of its next chunk; `time_` then only
-        counts the host time."""
+        counts the host time.
+        `mask` (n, n_features), bool or uint8, numpy or device tensor, True = observed: the rows have missing entries
+        and the minibatches are masked ones (`_partial_fit_masked`); calls with and without a mask may alternate."""
+        if mask is not None:
+            return self._partial_fit_masked(X, sample_indices, _sync, mask)
         be = self._backend
         if not (isinstance(X, np.memmap) and X.dtype == be.dtype and X.flags.c_contiguous):
             X = _as_float_array(X)                           # (a memmap of the right type is left on disk)
@@ -1282,6 +1393,7 @@ class DictFact(CodingMixin, BaseEstimator):
             state['_saved'] = dict(
                 dtype=str(be.dtype), n=be.n, p=be.p, k=be.k, components_=be.get_dictionary(), B_=be.get_B(),
                 C=be.get('C'), code=be.get('code'), comp_norm=be.get('comp_norm'), G=be.get('G'),
+                feature_n_iter=be.get('feature_n_iter') if hasattr(be, 'feature_n_iter') else None,
                 Dx_average=be.get('Dx_average'), G_average=be.get('G_average'),
                 partial_of=None if whole else (rank, world))
         state.pop('_stats_on_rank0', None)
@@ -1308,6 +1420,8 @@ class DictFact(CodingMixin, BaseEstimator):
             for name in ('code', 'comp_norm', 'G', 'Dx_average', 'G_average'):
                 if saved[name] is not None:
                     be.set(name, saved[name])
+            if saved.get('feature_n_iter') is not None and hasattr(be, 'feature_n_iter'):   # (an older pickle: zeros)
+                be.set('feature_n_iter', saved['feature_n_iter'])
 
 
 class Coder(CodingMixin, BaseEstimator):

@@ -161,6 +161,39 @@ def _grid_patches_masked_pass(d_image, d_obs, g, gcols, row0, nrows, with_mean, 
     return out, mean, den, obs, nobs
 
 
+def _patches_masked(d_image, d_obs, origins, patch_shape, with_mean, with_std):
+    """`_grid_patches_masked_pass` at the origins of an index list (n, 3) (modl_image_patches_masked_*): (patches, mean,
+    den, obs rows, nobs) of the windows of an image with holes, scaled on their observed elements"""
+    H, W, Cc = d_image.shape
+    x, y, z = (int(v) for v in patch_shape)
+    idx = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.int64)).to(d_image.device)
+    n, kw = idx.shape[0], dict(dtype=d_image.dtype, device=d_image.device)
+    out, mean, den = torch.empty((n, x * y * z), **kw), torch.empty((n, Cc), **kw), torch.empty((n, Cc), **kw)
+    obs = torch.empty((n, x * y * z), dtype=torch.uint8, device=d_image.device)
+    nobs = torch.empty(n, dtype=torch.int32, device=d_image.device)
+    with torch.cuda.device(d_image.device):
+        check(getattr(lib, 'modl_image_patches_masked_' + _sfx(d_image))(
+            ptr(d_image), H, W, Cc, ptr(idx), n, x, y, z, int(bool(with_mean)), int(bool(with_std)), ptr(out),
+            x * y * z, ptr(mean), ptr(den), ptr(d_obs), ptr(obs), ptr(nobs), stream_ptr(d_image.device)),
+            'modl_image_patches_masked')
+    return out, mean, den, obs, nobs
+
+
+def masked_candidates(mask, patch_size, min_observed):
+    """Origins (i, j, 0), in C order, of the windows of an (H, W, C) bool mask whose observed share of their x*y*C
+    elements is at least `min_observed` (integer arithmetic on a summed-area table; host work, like clean_mask)"""
+    mask = np.asarray(mask) != 0
+    H, W, Cc = mask.shape
+    x, y = (int(v) for v in patch_size)
+    sat = np.zeros((H + 1, W + 1), dtype=np.int64)
+    sat[1:, 1:] = mask.sum(axis=2, dtype=np.int64).cumsum(axis=0).cumsum(axis=1)
+    cnt = sat[x:, y:] - sat[:-x, y:] - sat[x:, :-y] + sat[:-x, :-y]
+    ii, jj = np.nonzero(cnt >= min_observed * (x * y * Cc))
+    out = np.zeros((ii.shape[0], 3), dtype=np.int64)
+    out[:, 0], out[:, 1] = ii, jj
+    return out
+
+
 def _overlap_add_weighted(d_patches, use, g, row0, nrows, acc, cnt):
     H, W, Cc, x, y, si, sj = g
     with torch.cuda.device(acc.device):
@@ -343,8 +376,28 @@ class ImageDictFact(BaseEstimator):
 
     _dict_fact_class = DictFact
 
-    def fit(self, image, y=None):
-        """image.py:68-153"""
+    def fit(self, image, y=None, mask=None, min_observed=0.25):
+        """image.py:68-153.  With `mask` ((H, W) or (H, W, C), True = observed) the dictionary is learned from the damaged
+        image itself: every window whose observed share is at least `min_observed` is a candidate (instead of the clean
+        windows only), each buffer of windows is scaled on its observed elements on the device and fitted with its mask
+        (`DictFact.partial_fit(..., mask=)`).  The usual call: `est.fit(image, mask=image != -1).inpaint(image)`.
+        A masked fit needs G_agg = Dx_agg = 'masked' on every epoch: the methods 'masked' and 'reducing ratio' (whose
+        schedule of `reduction` is kept but has no effect, a masked minibatch does not use `reduction`), and 'gram' up to
+        n_epochs = 4 - its schedule switches to 'full' / 'average' at the fifth epoch, which a mask does not support."""
+        if mask is not None:
+            if self.method == 'sgd' or ImageDictFact.methods[self.method] != {'G_agg': 'masked', 'Dx_agg': 'masked'} or \
+                    (self.method == 'gram' and self.n_epochs > 4):
+                raise ValueError("a fit with a mask needs a method whose aggregations are G_agg = Dx_agg = 'masked' on "
+                                 "every epoch ('masked', 'reducing ratio', or 'gram' with n_epochs <= 4: it switches to "
+                                 "'full' / 'average' at the fifth), got method=%r, n_epochs=%d" % (self.method, self.n_epochs))
+            if np.ndim(image) == 2:
+                image = image[:, :, None]
+            if len(np.shape(image)) != 3 or tuple(np.shape(mask)) not in (tuple(np.shape(image))[:2], tuple(np.shape(image))):
+                raise ValueError('mask of shape %s does not match an image of shape %s'
+                                 % (tuple(np.shape(mask)), tuple(np.shape(image))))
+            if self.n_components > 1024:
+                raise ValueError('a fit with a mask supports at most 1024 components (one Gram matrix per window), got %d'
+                                 % self.n_components)
         self.random_state = check_random_state(self.random_state)
         if self.method != 'sgd':
             method = ImageDictFact.methods[self.method]
@@ -364,6 +417,8 @@ class ImageDictFact(BaseEstimator):
             G_agg=G_agg, Dx_agg=Dx_agg, reduction=reduction, code_alpha=self.alpha,
             code_l1_ratio=setting['code_l1_ratio'], tol=1e-2, callback=self._callback, verbose=self.verbose,
             n_threads=self.n_threads)
+        if mask is not None:
+            return self._fit_masked(image, mask, min_observed, with_mean, with_std, buffer_size)
 
         patch_extractor = LazyCleanPatchExtractor(patch_size=self.patch_size, max_patches=self.max_patches,
                                                   random_state=self.random_state)
@@ -395,6 +450,41 @@ class ImageDictFact(BaseEstimator):
                 self.dict_fact_.set_params(reduction=reduction)
             for buffer in buffers:
                 self.dict_fact_.partial_fit(scaled(buffer), buffer)
+        return self
+
+    def _fit_masked(self, image, mask, min_observed, with_mean, with_std, buffer_size):
+        df = self.dict_fact_
+        probe = df._make_backend()
+        d_image = _stage_image(image, probe.device)
+        H, W, Cc = d_image.shape
+        m = mask.cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+        m = np.array(np.broadcast_to((m != 0) if m.ndim == 3 else (m != 0)[:, :, None], (H, W, Cc)), order='C')
+        d_obs = torch.from_numpy(m.view(np.uint8)).to(d_image.device)
+        x, y = (int(v) for v in (self.patch_size if self.patch_size is not None else (H // 10, W // 10)))
+        if x < 1 or y < 1 or x > H or y > W:
+            raise ValueError('patch_size %s does not fit an image of shape %s' % ((x, y), (H, W, Cc)))
+        self.patch_shape_ = (x, y, Cc)
+        origins = masked_candidates(m, (x, y), min_observed)
+        keep = self.random_state.permutation(origins.shape[0])[:self.max_patches]
+        origins = origins[keep]
+        n_patches = origins.shape[0]
+        if n_patches < self.n_components:
+            raise ValueError('%d windows have at least %g of their elements observed: at least n_components = %d are '
+                             'needed' % (n_patches, min_observed, self.n_components))
+
+        def scaled(batch):
+            out = _patches_masked(d_image, d_obs, origins[batch], self.patch_shape_, with_mean, with_std)
+            return out[0], out[3]
+
+        df.prepare(n_samples=n_patches, X=scaled(slice(0, self.n_components))[0])
+        for i in range(self.n_epochs):
+            if i >= 1:
+                origins = origins[df.shuffle()]
+            if self.method == 'reducing ratio':
+                df.set_params(reduction=1 + (self.reduction - 1) / sqrt(i + 1))
+            for buffer in gen_batches(n_patches, buffer_size):
+                patches, obs = scaled(buffer)
+                df.partial_fit(patches, buffer, mask=obs)
         return self
 
     def _prep(self, patches):
