@@ -212,7 +212,16 @@ int modl_predict_csr(double *d_data, const int32_t *d_indices, const int32_t *d_
 /* Ridge codes on the observed columns of b CSR rows (recsys.py:168-181 and _refit :254-265):
  * code = (D_S D_S^T + alpha |S| / p I)^-1 D_S x_S.  d_row_ids[b] selects rows of the CSR matrix
  * (NULL = rows 0..b-1), d_code_rows[b] the destination rows of d_code (NULL = the CSR row id).
- * Rows without entries keep their code. */
+ * Rows without entries keep their code.
+ * k is NOT bounded by MODL_MAX_COMPONENTS here: a row's k x k system, its right-hand side and 32 staged dictionary rows share
+ * the 160 KiB of LDS of one workgroup.  f32: 1 <= k <= 186 (k <= 64 and k <= 128 factor with one / two rows of the system per
+ * lane, 129 .. 186 with the whole workgroup); f64: 1 <= k <= 127 (k <= 64, k <= 121, 122 .. 127 likewise).  A larger k is
+ * MODL_EINVAL and nothing is written.  The same limits hold for modl_recsys_minibatch_* and modl_recsys_fit_batches_*, whose
+ * minibatches of more than 64 (f64: 56) atoms, more than 64 rows or more than 64 chunks of 128 ratings solve their codes here.
+ * Those two do NOT refuse a larger k up front: modl_recsys_plan_create takes any k, and the minibatch answers MODL_EINVAL only
+ * when it reaches the code solve, after it has taken a staging slot of the plan and enqueued the staging copy (no state array
+ * is written; the plan counts the call as a split one).  Callers check k against these limits themselves, as
+ * RecsysDictFact.fit does. */
 int modl_recsys_codes_f32(const float *d_Dt, int64_t p, int k, const int32_t *d_indptr, const int32_t *d_indices,
                           const float *d_data, const int64_t *d_row_ids, const int64_t *d_code_rows, int64_t b,
                           double alpha, float *d_code, void *stream);

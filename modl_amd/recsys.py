@@ -19,6 +19,12 @@ from .device import default_device, dtype_id, sfx, torch_dtype, ptr, stream_ptr,
 from .randomkit import batch_weight
 
 
+# The largest n_components the ridge-code kernels take, per dtype: the row's k x k system, its right-hand side and 32 staged
+# dictionary rows must fit the 160 KiB of LDS of a workgroup (csrc/recsys.hip: recsys_codes; include/modl_hip.h,
+# modl_recsys_codes_*).  tests/test_recsys_kernels.py pins both numbers to what the entry point accepts.
+MAX_COMPONENTS = {np.dtype(np.float32): 186, np.dtype(np.float64): 127}
+
+
 def compute_biases(X, beta=0, inplace=False):
     """Row / column centring of a CSR matrix (recsys.py:268-306), host code."""
     if not inplace:
@@ -236,6 +242,11 @@ class RecsysDictFact(BaseEstimator):
         X = check_array(X, accept_sparse='csr', dtype=[np.float32, np.float64], copy=True)
         dtype = X.dtype
         n_samples, n_features = X.shape
+        if self.n_components > MAX_COMPONENTS[np.dtype(dtype)]:
+            raise ValueError('RecsysDictFact: n_components = %d, but at most %d components are supported for %s ratings '
+                             '(%d for float32, %d for float64): the ridge system of a row must fit the LDS of a workgroup'
+                             % (self.n_components, MAX_COMPONENTS[np.dtype(dtype)], np.dtype(dtype).name,
+                                MAX_COMPONENTS[np.dtype(np.float32)], MAX_COMPONENTS[np.dtype(np.float64)]))
         self.random_state = check_random_state(self.random_state)
         if self.detrend:
             self.row_mean_, self.col_mean_ = compute_biases(X, beta=self.beta, inplace=False)

@@ -89,6 +89,76 @@ def recsys_biases(X, beta=0):
     return acc_u, acc_m
 
 
+class RecsysState:
+    """What one minibatch of RecsysDictFact advances (recsys.py:81-213): D (k, p), code (n, k), C (k, k), B (k, p),
+    comp_norm (k), feature_n_iter (p, int)."""
+
+    def __init__(self, D, code, C, B, comp_norm, feature_n_iter):
+        self.D, self.code, self.C, self.B, self.comp_norm, self.feature_n_iter = D, code, C, B, comp_norm, feature_n_iter
+
+    def copy(self, dtype=None):
+        f = (lambda a: a.copy()) if dtype is None else (lambda a: a.astype(dtype))
+        return RecsysState(f(self.D), f(self.code), f(self.C), f(self.B), f(self.comp_norm), self.feature_n_iter.copy())
+
+
+def recsys_solve_row(X, D, i, alpha):
+    """recsys.py:176-181 for row i of the CSR matrix X: (code, its items, its ratings)"""
+    k, p = D.shape
+    s, e = X.indptr[i], X.indptr[i + 1]
+    sub, xs = X.indices[s:e], X.data[s:e]
+    Ds = D[:, sub]
+    G = Ds.dot(Ds.T)
+    G.flat[::k + 1] += alpha / (p / len(sub))
+    return linalg.solve(G, Ds.dot(xs)), sub, xs
+
+
+def recsys_batch_statistics(st, X, alpha, batch, w, n_iter):
+    """recsys.py:159-160, 168-185: the codes of the batch's rows, feature_n_iter and B_ entry by entry in batch order, then C_"""
+    D, code, Cm, B, fni = st.D, st.code, st.C, st.B, st.feature_n_iter
+    for i in batch:
+        if X.indptr[i + 1] != X.indptr[i]:
+            c, sub, xs = recsys_solve_row(X, D, i, alpha)
+            fni[sub] += 1
+            code[i] = c
+            w_B = np.minimum(1, w * n_iter / fni[sub])
+            B[:, sub] *= 1 - w_B
+            B[:, sub] += np.outer(c.astype(B.dtype), xs * w_B)
+    Cm *= 1 - w
+    Cm += w / len(batch) * code[batch].T.dot(code[batch])
+
+
+def recsys_batch_dictionary(st, X, batch, order):
+    """recsys.py:187-213: the dictionary update on the items the batch rates, atoms in `order`.  Returns those items."""
+    D, Cm, B, comp_norm = st.D, st.C, st.B, st.comp_norm
+    subset = np.unique(np.concatenate([X.indices[X.indptr[i]:X.indptr[i + 1]] for i in batch]))
+    if subset.size == 0:                                                  # (no item touched: nothing to update, BLAS aside)
+        return subset
+    Ds = D[:, subset]
+    gs = B[:, subset]
+    gs -= Cm.dot(Ds)
+    ger, = scipy.linalg.get_blas_funcs(('ger',), (Cm, D))
+    comp_norm += np.sum(Ds ** 2, axis=1)
+    for j in order:
+        gs = ger(1.0, Cm[j], Ds[j], a=gs, overwrite_a=True)
+        if Cm[j, j] > 1e-20:
+            Ds[j] = gs[j] / Cm[j, j]
+        nrm, lim = sqrt(np.sum(Ds[j] ** 2)), sqrt(comp_norm[j])
+        if nrm > lim:
+            Ds[j] /= nrm / lim
+        gs = ger(-1.0, Cm[j], Ds[j], a=gs, overwrite_a=True)
+    comp_norm -= np.sum(Ds ** 2, axis=1)
+    D[:, subset] = Ds
+    return subset
+
+
+def recsys_minibatch(st, X, alpha, batch, w, n_iter, order):
+    """recsys.py:147-213: one minibatch on the state `st` (a RecsysState, advanced in place).  batch: row ids of the CSR matrix X
+    in batch order; w: its weight; n_iter: n_iter_ after this batch; order: the atom order of the dictionary update."""
+    batch = np.asarray(batch)
+    recsys_batch_statistics(st, X, alpha, batch, w, n_iter)
+    return recsys_batch_dictionary(st, X, batch, order)
+
+
 def recsys_fit(X, alpha=1.0, beta=0.0, n_components=30, learning_rate=1.0, batch_size=1, n_epochs=1,
                random_state=None, detrend=False):
     """recsys.py:81-213.  Returns a dict of the fitted attributes."""
@@ -106,62 +176,25 @@ def recsys_fit(X, alpha=1.0, beta=0.0, n_components=30, learning_rate=1.0, batch
         out['row_mean'], out['col_mean'] = rm, cm
     D = rng.randn(k, p).astype(dtype)
     D /= np.sqrt(np.sum(D ** 2, axis=1))[:, None]
-    code = np.zeros((n, k), dtype=dtype)
-
-    def solve_row(i):
-        s, e = X.indptr[i], X.indptr[i + 1]
-        sub, xs = X.indices[s:e], X.data[s:e]
-        Ds = D[:, sub]
-        G = Ds.dot(Ds.T)
-        G.flat[::k + 1] += alpha / (p / len(sub))
-        return linalg.solve(G, Ds.dot(xs)), sub, xs
+    st = RecsysState(D, np.zeros((n, k), dtype=dtype), np.zeros((k, k), dtype=dtype), np.zeros((k, p), dtype=dtype),
+                     np.zeros(k, dtype=dtype), np.zeros(p, dtype=int))
 
     def refit():
         for i in range(n):
             if X.indptr[i + 1] > X.indptr[i]:
-                code[i] = solve_row(i)[0]
+                st.code[i] = recsys_solve_row(X, st.D, i, alpha)[0]
     refit()
-    fni = np.zeros(p, dtype=int)
-    comp_norm = np.zeros(k, dtype=dtype)
-    Cm = np.zeros((k, k), dtype=dtype)
-    B = np.zeros((k, p), dtype=dtype)
-    ger, = scipy.linalg.get_blas_funcs(('ger',), (Cm, D))
     n_iter = 0
     for _ in range(n_epochs):
         perm = rng.permutation(n)
         for b0 in range(0, n, batch_size):
             batch = perm[b0:b0 + batch_size]
-            bs = len(batch)
-            n_iter += bs
-            w = orc.batch_weight(n_iter, bs, learning_rate, 0)
-            for i in batch:                                              # recsys.py:168-185
-                if X.indptr[i + 1] - X.indptr[i] != 0:
-                    c, sub, xs = solve_row(i)
-                    fni[sub] += 1
-                    code[i] = c
-                    w_B = np.minimum(1, w * n_iter / fni[sub])
-                    B[:, sub] *= 1 - w_B
-                    B[:, sub] += np.outer(code[i], xs * w_B)
-            Cm *= 1 - w
-            Cm += w / bs * code[batch].T.dot(code[batch])
-            subset = np.unique(np.concatenate([X.indices[X.indptr[i]:X.indptr[i + 1]] for i in batch]))
-            Ds = D[:, subset]                                             # recsys.py:187-213
-            gs = B[:, subset]
-            gs -= Cm.dot(Ds)
-            order = rng.permutation(k)
-            comp_norm += np.sum(Ds ** 2, axis=1)
-            for j in order:
-                gs = ger(1.0, Cm[j], Ds[j], a=gs, overwrite_a=True)
-                if Cm[j, j] > 1e-20:
-                    Ds[j] = gs[j] / Cm[j, j]
-                nrm, lim = sqrt(np.sum(Ds[j] ** 2)), sqrt(comp_norm[j])
-                if nrm > lim:
-                    Ds[j] /= nrm / lim
-                gs = ger(-1.0, Cm[j], Ds[j], a=gs, overwrite_a=True)
-            comp_norm -= np.sum(Ds ** 2, axis=1)
-            D[:, subset] = Ds
+            n_iter += len(batch)
+            w = orc.batch_weight(n_iter, len(batch), learning_rate, 0)
+            # (recsys.py:196 draws the order after the codes and C_; nothing else draws in between)
+            recsys_minibatch(st, X, alpha, batch, w, n_iter, rng.permutation(k))
     refit()
-    out.update(D=D, code=code, C=Cm, B=B, comp_norm=comp_norm, X=X)
+    out.update(D=st.D, code=st.code, C=st.C, B=st.B, comp_norm=st.comp_norm, feature_n_iter=st.feature_n_iter, X=X)
     return out
 
 
