@@ -243,6 +243,31 @@ int modl_recsys_predict_f32(double *d_out, const int32_t *d_indices, const int32
                             int64_t n_rows, int k, const float *d_Dt, void *stream);
 int modl_recsys_predict_f64(double *d_out, const int32_t *d_indices, const int32_t *d_indptr, const double *d_code,
                             int64_t n_rows, int k, const double *d_Dt, void *stream);
+/* Recommendation: the n_top best items of b queries, without ever writing the b x p scores (csrc/recsys_topn.hip).
+ *   score[ii][f] = sum_c code[c] Dt[f][c] (+ d_item_bias[f]) over every item f of 0 .. p-1 that is not excluded for query ii;
+ *   d_items[ii * n_top + j] = the item with the j-th largest score, d_scores[...] that score: descending, equal scores by
+ *   ascending item id.  The result is a function of the inputs alone (run-to-run identical, whatever the number of slabs the
+ *   items are cut into).  Fewer than n_top items left: the tail is item -1 with score -inf.  Inputs are assumed finite.
+ * Query ii: its code is row d_code_rows[ii] of d_code[.][k] (NULL: row ii); its excluded items are the entries of row
+ * d_ex_rows[ii] (NULL: row ii) of the CSR pattern d_ex_indptr / d_ex_indices, whose column indices may be unsorted and may
+ * repeat; d_ex_indptr NULL: nothing is excluded.  d_Dt[p][k]: the feature-major dictionary.  d_item_bias: double[p] or NULL
+ * (f32: the sum is formed in double and rounded once).
+ * MODL_EINVAL before any device work: a NULL d_code / d_Dt / d_items / d_scores (or d_ex_indices with d_ex_indptr given),
+ * b < 0, p < 1 or p >= 2^31, n_top outside 1 .. MODL_RECSYS_MAX_TOPN, k < 1 or k beyond the limit of modl_recsys_codes_* (f32
+ * 186, f64 127).  b == 0 does nothing.  d_ws NULL or smaller than modl_recsys_topn_workspace(...): MODL_ENOMEM; no device:
+ * MODL_ENOGPU.  The workspace holds a bitmask of p bits per query and, for calls with few queries (the items are then cut into
+ * slabs over workgroups), one list per query and slab.  Asynchronous on `stream`. */
+#define MODL_RECSYS_MAX_TOPN 128
+/* bytes of d_ws for a call with these arguments; 0 for arguments the call refuses (and for b == 0) */
+size_t modl_recsys_topn_workspace(int dtype, int64_t p, int k, int64_t b, int n_top);
+int modl_recsys_topn_f32(const float *d_code, const int64_t *d_code_rows, int64_t b, int k, const float *d_Dt, int64_t p,
+                         const int32_t *d_ex_indptr, const int32_t *d_ex_indices, const int64_t *d_ex_rows,
+                         const double *d_item_bias, int n_top, int32_t *d_items, float *d_scores, void *d_ws,
+                         size_t ws_bytes, void *stream);
+int modl_recsys_topn_f64(const double *d_code, const int64_t *d_code_rows, int64_t b, int k, const double *d_Dt, int64_t p,
+                         const int32_t *d_ex_indptr, const int32_t *d_ex_indices, const int64_t *d_ex_rows,
+                         const double *d_item_bias, int n_top, int32_t *d_items, double *d_scores, void *d_ws,
+                         size_t ws_bytes, void *stream);
 /* One minibatch of RecsysDictFact._single_batch_fit (recsys.py:147-165, 168-213) in ONE call: the batch's ratings are
  * grouped by item on the host (batch order kept inside an item), staged through a pinned slot of the plan, and the
  * codes, the per-item B_ update, the C_ update and the dictionary update on the union of the batch's items are

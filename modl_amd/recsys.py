@@ -14,7 +14,7 @@ import torch
 from sklearn.base import BaseEstimator
 from sklearn.utils import check_array, check_random_state, gen_batches
 
-from ._lib import lib, check
+from ._lib import lib, check, RECSYS_MAX_TOPN
 from .device import default_device, dtype_id, sfx, torch_dtype, ptr, stream_ptr, to_device, transpose_to
 from .randomkit import batch_weight
 
@@ -23,6 +23,9 @@ from .randomkit import batch_weight
 # dictionary rows must fit the 160 KiB of LDS of a workgroup (csrc/recsys.hip: recsys_codes; include/modl_hip.h,
 # modl_recsys_codes_*).  tests/test_recsys_kernels.py pins both numbers to what the entry point accepts.
 MAX_COMPONENTS = {np.dtype(np.float32): 186, np.dtype(np.float64): 127}
+# recommend(): the longest list modl_recsys_topn_* returns (MODL_RECSYS_MAX_TOPN), and the workspace a call may take
+MAX_TOPN = RECSYS_MAX_TOPN
+TOPN_WORKSPACE_BYTES = 256 << 20
 
 
 def compute_biases(X, beta=0, inplace=False):
@@ -50,6 +53,12 @@ def rmse(X_true, X_pred):
     X_true = check_array(X_true, accept_sparse='csr')
     X_pred = check_array(X_pred, accept_sparse='csr')
     return np.sqrt(np.mean((X_true.data - X_pred.data) ** 2))
+
+
+def _csr_piece(a, dtype, device):
+    """a CSR array on the device; an empty one as a single unused element (the entry points refuse a NULL pointer)"""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return torch.from_numpy(a if a.size else np.zeros(1, dtype=dtype)).to(device)
 
 
 class _RecsysDevice:
@@ -177,15 +186,66 @@ class _RecsysDevice:
         except Exception:
             pass
 
-    def predict(self, Xp):
+    def predict(self, Xp, code=None):
+        """the product at the pattern of Xp (row u of Xp against row u of `code`; None: code_), in double"""
         dev = self.device
+        code = self.code if code is None else code
         out = torch.zeros(Xp.nnz, dtype=torch.float64, device=dev)
         ind = torch.from_numpy(Xp.indices.astype(np.int32)).to(dev)
         iptr = torch.from_numpy(Xp.indptr.astype(np.int32)).to(dev)
         f = getattr(lib, 'modl_recsys_predict_' + sfx(self.dtype))
-        check(f(ptr(out), ptr(ind), ptr(iptr), ptr(self.code), Xp.shape[0], self.k, ptr(self.Dt), stream_ptr(dev)),
+        check(f(ptr(out), ptr(ind), ptr(iptr), ptr(code), Xp.shape[0], self.k, ptr(self.Dt), stream_ptr(dev)),
               'modl_recsys_predict')
         return out.cpu().numpy()
+
+    def codes_of(self, X, alpha):
+        """ridge codes of the rows of ANY ratings matrix with p columns under the current dictionary, into a fresh (zero)
+        buffer: rows without ratings keep a zero code.  Returns the device tensor (rows, k)."""
+        dev = self.device
+        indptr = _csr_piece(X.indptr, np.int32, dev)
+        indices = _csr_piece(X.indices, np.int32, dev)
+        data = _csr_piece(X.data, self.dtype, dev)
+        code = torch.zeros((X.shape[0], self.k), dtype=torch_dtype(self.dtype), device=dev)
+        f = getattr(lib, 'modl_recsys_codes_' + sfx(self.dtype))
+        check(f(ptr(self.Dt), self.p, self.k, ptr(indptr), ptr(indices), ptr(data), None, None, X.shape[0], float(alpha),
+                ptr(code), stream_ptr(dev)), 'modl_recsys_codes')
+        return code
+
+    def topn_rows_per_call(self, b, n_top):
+        """the most queries of one modl_recsys_topn_* call whose workspace stays under TOPN_WORKSPACE_BYTES"""
+        rows = max(int(b), 1)
+        while rows > 1 and lib.modl_recsys_topn_workspace(dtype_id(self.dtype), self.p, self.k, rows, n_top) > TOPN_WORKSPACE_BYTES:
+            rows = (rows + 1) // 2
+        return rows
+
+    def topn(self, code, ex_indptr, ex_indices, ex_rows, item_bias, n_top, rows_per_call=None):
+        """the n_top best items (int32 tensor (b, n_top), -1 where nothing is left) of the rows of `code`; excluded for row ii
+        are the entries of row ex_rows[ii] (None: ii) of the CSR pattern ex_indptr / ex_indices (None: nothing)"""
+        dev = self.device
+        b = code.shape[0]
+        items = torch.empty((b, n_top), dtype=torch.int32, device=dev)
+        scores = torch.empty((b, n_top), dtype=torch_dtype(self.dtype), device=dev)
+        if rows_per_call is None:
+            rows_per_call = self.topn_rows_per_call(b, n_top)
+        rows_per_call = max(int(rows_per_call), 1)
+        f = getattr(lib, 'modl_recsys_topn_' + sfx(self.dtype))
+        nbytes = lib.modl_recsys_topn_workspace(dtype_id(self.dtype), self.p, self.k, min(rows_per_call, max(b, 1)), n_top)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        for s in range(0, b, rows_per_call):
+            e = min(s + rows_per_call, b)
+            need = lib.modl_recsys_topn_workspace(dtype_id(self.dtype), self.p, self.k, e - s, n_top)
+            if need > ws.numel():                           # (a short last chunk is cut into more slabs)
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            if ex_indptr is None:
+                ex = (None, None, None)
+            elif ex_rows is None:
+                # rows s .. e-1 of the pattern: the row pointers are absolute, so a view of indptr addresses them
+                ex = (ptr(ex_indptr[s:]), ptr(ex_indices), None)
+            else:
+                ex = (ptr(ex_indptr), ptr(ex_indices), ptr(ex_rows[s:e]))
+            check(f(ptr(code[s:e]), None, e - s, self.k, ptr(self.Dt), self.p, ex[0], ex[1], ex[2], ptr(item_bias), n_top,
+                    ptr(items[s:e]), ptr(scores[s:e]), ptr(ws), ws.numel(), stream_ptr(dev)), 'modl_recsys_topn')
+        return items
 
 
 class RecsysDictFact(BaseEstimator):
@@ -249,6 +309,7 @@ class RecsysDictFact(BaseEstimator):
                                 MAX_COMPONENTS[np.dtype(np.float32)], MAX_COMPONENTS[np.dtype(np.float64)]))
         self.random_state = check_random_state(self.random_state)
         if self.detrend:
+            self.global_mean_ = float(np.mean(X.data))        # (the average rating compute_biases shrinks the row means to)
             self.row_mean_, self.col_mean_ = compute_biases(X, beta=self.beta, inplace=False)
             X.data -= np.repeat(self.row_mean_, np.diff(X.indptr)).astype(dtype)
             X.data -= self.col_mean_.take(X.indices, mode='clip').astype(dtype)
@@ -298,19 +359,98 @@ class RecsysDictFact(BaseEstimator):
         """recsys.py:254-265: ridge codes of every row with the current dictionary"""
         self._dev.codes(None, self.alpha)
 
+    def _finish(self, out, row_bias, indptr, indices):
+        """raw products at a pattern -> predictions: the row bias, col_mean_ and the crop (recsys.py:236-244)"""
+        if self.detrend:
+            out += np.repeat(row_bias, np.diff(indptr))
+            out += self.col_mean_.take(indices, mode='clip')
+        if self.crop is not None:
+            out[out > self.crop[1]] = self.crop[1]
+            out[out < self.crop[0]] = self.crop[0]
+        return out
+
     def predict(self, X):
         """recsys.py:215-245"""
         if not sp.issparse(X):
             X = sp.csr_matrix(X)
         X = check_array(X, accept_sparse='csr')
-        out = self._dev.predict(X)
-        if self.detrend:
-            out += np.repeat(self.row_mean_, np.diff(X.indptr))
-            out += self.col_mean_.take(X.indices, mode='clip')
-        if self.crop is not None:
-            out[out > self.crop[1]] = self.crop[1]
-            out[out < self.crop[0]] = self.crop[0]
+        out = self._finish(self._dev.predict(X), self.row_mean_ if self.detrend else None, X.indptr, X.indices)
         return sp.csr_matrix((out, X.indices, X.indptr), shape=X.shape)
+
+    def _fold_in(self, X):
+        """(X as CSR of the fitted dtype, device codes (rows, k), row bias or None) of the rows of a ratings matrix X, which
+        need not be training rows: centred as fit centres (col_mean_ at the rated items, and the row bias
+        (sum_f (x_f - col_mean_[f]) + beta global_mean_) / (n_u + beta), the first pass of compute_biases for a row on its
+        own), then coded on their ratings by the kernel _refit uses."""
+        dev = self._dev
+        if not sp.issparse(X):
+            X = sp.csr_matrix(X)
+        X = check_array(X, accept_sparse='csr', dtype=[np.float32, np.float64], copy=True)
+        if X.shape[1] != dev.p:
+            raise ValueError('RecsysDictFact: X has %d columns, the fitted dictionary %d' % (X.shape[1], dev.p))
+        row_bias = None
+        if self.detrend:
+            data = X.data.astype(np.float64) - self.col_mean_.take(X.indices, mode='clip')
+            n_u = np.diff(X.indptr)
+            sums = np.bincount(np.repeat(np.arange(X.shape[0]), n_u), weights=data, minlength=X.shape[0])
+            den = n_u + float(self.beta)
+            row_bias = np.where(den > 0, (sums + self.beta * self.global_mean_) / np.where(den > 0, den, 1), 0.0)
+            data -= np.repeat(row_bias, n_u)
+            X = sp.csr_matrix((data, X.indices, X.indptr), shape=X.shape)
+        X = sp.csr_matrix((X.data.astype(dev.dtype), X.indices, X.indptr), shape=X.shape)
+        return X, dev.codes_of(X, self.alpha), row_bias
+
+    def transform(self, X):
+        """Ridge codes (rows of X, n_components) of the rows of a ratings matrix X under the fitted dictionary: what fit
+        computes for its own rows (recsys.py:176-181), for any rows.  Rows without ratings get a zero code."""
+        return self._fold_in(X)[1].cpu().numpy()
+
+    def recommend(self, X=None, n_items=10, users=None, exclude_seen=True, rows_per_call=None):
+        """The n_items items with the highest predicted rating per user: (items int64 (users, n_items), -1 where a user has
+        fewer candidates; scores float64, NaN there).
+
+        X=None: the training users (all, or the row ids `users`); their seen items are the training ratings.  X given: one new
+        user per row of X, coded on their ratings (transform); their seen items are the entries of X.  exclude_seen=False
+        ranks every item.  The ranking is by the uncropped prediction (equal ones by ascending item id); the scores are what
+        predict gives at the returned loci.  Users go through the kernel rows_per_call at a time (default: as many as keep
+        its workspace under 256 MB)."""
+        n_items = int(n_items)
+        if n_items < 1 or n_items > MAX_TOPN:
+            raise ValueError('RecsysDictFact.recommend: n_items = %d, but a call returns between 1 and %d items per user '
+                             '(MODL_RECSYS_MAX_TOPN)' % (n_items, MAX_TOPN))
+        dev = self._dev
+        d = dev.device
+        if X is None:
+            if users is None:
+                rows, code, ex_rows = np.arange(dev.n), dev.code, None
+            else:
+                rows = np.ascontiguousarray(users, dtype=np.int64).ravel()
+                if rows.size and (rows.min() < 0 or rows.max() >= dev.n):
+                    raise ValueError('RecsysDictFact.recommend: users must be row ids of the training matrix')
+                ex_rows = torch.from_numpy(rows).to(d)
+                code = dev.code.index_select(0, ex_rows)
+            row_bias = self.row_mean_[rows] if self.detrend else None
+            ex_indptr, ex_indices = dev.indptr, dev.indices
+        else:
+            if users is not None:
+                raise ValueError('RecsysDictFact.recommend: `users` selects training rows; with X every row is a user')
+            X, code, row_bias = self._fold_in(X)
+            ex_rows = None
+            ex_indptr, ex_indices = _csr_piece(X.indptr, np.int32, d), _csr_piece(X.indices, np.int32, d)
+        if not exclude_seen:
+            ex_indptr = ex_indices = ex_rows = None
+        bias = torch.from_numpy(np.ascontiguousarray(self.col_mean_, dtype=np.float64)).to(d) if self.detrend else None
+        nq = code.shape[0]
+        items = dev.topn(code, ex_indptr, ex_indices, ex_rows, bias, n_items, rows_per_call).cpu().numpy().astype(np.int64)
+        # the scores: predict's own kernel and arithmetic at the returned loci (the lists end in -1: the pattern is their head)
+        valid = items >= 0
+        indptr = np.concatenate([[0], np.cumsum(valid.sum(axis=1))]).astype(np.int64)
+        indices = items[valid].astype(np.int32)
+        pattern = sp.csr_matrix((np.zeros(len(indices)), indices, indptr), shape=(nq, dev.p))
+        out = self._finish(dev.predict(pattern, code), row_bias, indptr, indices)
+        scores = np.full(items.shape, np.nan)
+        scores[valid] = out
+        return items, scores
 
     def score(self, X):
         """Root mean squared error of the prediction at the loci of X (recsys.py:247-252)"""
