@@ -506,6 +506,36 @@ int modl_somf_full_gram(modl_somf_plan *plan, const void *d_Dt, void *d_G, void 
 int modl_somf_transform(modl_somf_plan *plan, const void *d_Dt, const void *d_G, const void *d_X, int64_t ldx,
                         int64_t n, void *d_code_out, void *stream);
 
+/* Orthogonal matching pursuit (Batch-OMP on Gram quantities, csrc/omp.hip; no counterpart in the reference): the code of a
+ * row has at most n_nonzero non-zeros, the atoms picked greedily by the largest |correlation| with the residual (equal
+ * values: the lowest index), the coefficients the least-squares fit on the picked atoms.  Sample i reads G_i = d_G + i *
+ * g_stride (g_stride 0: one shared k x k matrix; k * k: one per row, as modl_enet_regression_multi_gram_*), d_Dx[i][:] and,
+ * with tol >= 0, d_xnorm2[i] = |x_i|^2: a row then stops as soon as its squared residual is <= tol (the tol of scikit-learn's
+ * orthogonal_mp_gram), n_nonzero still capping the support.  tol < 0 (or NaN): no threshold, d_xnorm2 is not read and may
+ * be NULL.  A row also stops when no correlation is left, or when the best atom is numerically in the span of the picked
+ * ones (Schur complement d <= 16 eps_T G_jj).  Written in full by the kernel: d_code[b][k] (zeros off the support),
+ * d_support[b][n_nonzero] (selection order, -1 beyond the row's count) and d_n_active[b].  All arithmetic in the dtype; no
+ * atomics; the result of a row is the same bits from run to run and in any batch.
+ * 1 <= n_nonzero <= MODL_OMP_MAX_NONZERO, n_nonzero <= k; k <= MODL_MAX_COMPONENTS with a shared matrix, k <= 1024 with one
+ * per row.  MODL_EINVAL before any device work: a NULL pointer (d_xnorm2 with tol < 0 and d_ws apart), b < 0, k or n_nonzero
+ * out of range, g_stride neither 0 nor k * k.  b == 0 does nothing.  MODL_ENOMEM: ws_bytes below modl_omp_workspace(...)
+ * (which is 0 for every valid call today: a row's state lives in registers and LDS; the pair is there so that this can
+ * change without a new signature).  No device: MODL_ENOGPU. */
+#define MODL_OMP_MAX_NONZERO 64
+size_t modl_omp_workspace(int dtype, int64_t b, int k, int n_nonzero, int multi_gram);
+int modl_omp_gram_f32(const float *d_G, int64_t g_stride, const float *d_Dx, const float *d_xnorm2, int64_t b, int k,
+                      int n_nonzero, float tol, float *d_code, int32_t *d_support, int32_t *d_n_active, void *d_ws,
+                      size_t ws_bytes, void *stream);
+int modl_omp_gram_f64(const double *d_G, int64_t g_stride, const double *d_Dx, const double *d_xnorm2, int64_t b, int k,
+                      int n_nonzero, double tol, double *d_code, int32_t *d_support, int32_t *d_n_active, void *d_ws,
+                      size_t ws_bytes, void *stream);
+/* modl_somf_transform with the OMP coder in the place of the elastic-net solve: the same Gram matrix (d_G may be NULL) and
+ * Dx = X D^T products, row norms only when tol >= 0, chunks of the plan's max_batch.  d_code_out[n][k]; d_support_out
+ * [n][n_nonzero] and d_n_active_out[n] may be NULL.  The plan's code_* settings are not used. */
+int modl_somf_transform_omp(modl_somf_plan *plan, const void *d_Dt, const void *d_G, const void *d_X, int64_t ldx,
+                            int64_t n, int n_nonzero, double tol, void *d_code_out, int32_t *d_support_out,
+                            int32_t *d_n_active_out, void *stream);
+
 /* diagnostics: coordinate-descent sweeps per sample of the last phase-1 call of this plan
  * (0 for the ridge branch).  Synchronises `stream`. */
 int modl_somf_last_sweeps(modl_somf_plan *plan, int32_t *h_out, int cap, int *n_out, void *stream);

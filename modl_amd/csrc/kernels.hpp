@@ -106,6 +106,16 @@ template <typename T>
 int launch_masked_codes_finish(hipStream_t stream, T *code, const int64_t *idx, const int32_t *nobs, int b, int k,
                                T *codeb);
 
+// ---- omp.hip ----------------------------------------------------------------
+// Batch-OMP on Gram quantities, one wavefront per sample: at most s atoms (1 <= s <= MODL_OMP_MAX_NONZERO, s <= k <=
+// MODL_MAX_COMPONENTS), and with tol >= 0 only until the squared residual, started from xnorm2, is <= tol.  G shared
+// (g_stride == 0) or one per sample (g_stride == k * k).  code[b][k], support[b][s] (-1 beyond n_active) and n_active[b]
+// are written in full; support and n_active may be null.
+bool omp_args_ok(int64_t b, int k, int n_nonzero, bool multi_gram);
+template <typename T>
+int launch_omp(hipStream_t stream, const T *G, int64_t g_stride, const T *Dx, const T *xnorm2, int64_t b, int k, int s, T tol,
+               T *code, int32_t *support, int32_t *n_active);
+
 // ---- bcd.hip ----------------------------------------------------------------
 // Work that rides along the block launches of the fused dictionary update, on the compute units that update
 // leaves idle: the statistics update of the rows of Bt that were NOT sampled,

@@ -1043,6 +1043,41 @@ int transform_impl(modl_somf_plan *pl, const T *Dt, const T *G, const T *X, int6
     return MODL_OK;
 }
 
+// transform_impl with the OMP coder (omp.hip) in the place of solve_codes: nothing is warm-started, the kernel writes
+// every element of its outputs
+template <typename T>
+int transform_omp_impl(modl_somf_plan *pl, const T *Dt, const T *G, const T *X, int64_t ldx, int64_t n, int n_nonzero, T tol,
+                       T *code_out, int32_t *support_out, int32_t *n_active_out, hipStream_t st) {
+    const modl_somf_desc &d = pl->d;
+    const int k = d.k;
+    const int64_t p = d.p;
+    T *xnorm = reinterpret_cast<T *>(pl->dws + pl->off_xnorm);
+    T *Dx = reinterpret_cast<T *>(pl->dws + pl->off_Dx);
+    T *Gbuf = reinterpret_cast<T *>(pl->dws + pl->off_G);
+    SplitWs sws{pl->dws + pl->off_split, pl->split_bytes};
+    const bool use_tol = tol >= (T)0;
+    int nl = 0;
+    if (!G) {
+        EpiStore<T> epi{Gbuf, k, (T)1};
+        MODL_TRY((gram_of_rows<T, EpiStore<T>>(pl, st, Dt, nullptr, p, epi, &nl)));
+        G = Gbuf;
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += d.max_batch) {
+        const int b = (int)std::min<int64_t>(d.max_batch, n - r0);
+        const T *Xb = X + r0 * ldx;
+        if (use_tol) MODL_TRY(launch_row_norm2<T>(st, Xb, ldx, p, b, xnorm));
+        DenseOperand A, B;
+        A.ptr = Xb; A.si = ldx; A.sk = 1;
+        B.ptr = Dt; B.si = 1; B.sk = k;
+        EpiStore<T> epi{Dx, k, (T)1};
+        MODL_TRY((launch_gemm_dense<T, EpiStore<T>>(st, A, B, b, k, p, epi, sws, &nl)));
+        MODL_TRY(launch_omp<T>(st, G, 0, Dx, use_tol ? xnorm : nullptr, b, k, n_nonzero, tol, code_out + r0 * k,
+                               support_out ? support_out + r0 * n_nonzero : nullptr,
+                               n_active_out ? n_active_out + r0 : nullptr));
+    }
+    return MODL_OK;
+}
+
 template <typename T>
 int enet_regression_abi(const T *G, int64_t g_stride, T *Dx, const T *X, int64_t ldx, int64_t p, T *code,
                         const int64_t *d_indices, int64_t b, int64_t k, T l1_ratio, T alpha, int positive, T tol,
@@ -1772,6 +1807,24 @@ int modl_somf_transform(modl_somf_plan *pl, const void *d_Dt, const void *d_G, c
                     transform_impl<double>(pl, static_cast<const double *>(d_Dt), static_cast<const double *>(d_G),
                                            static_cast<const double *>(d_X), ldx, n, static_cast<double *>(d_code_out),
                                            (hipStream_t)stream));
+}
+
+int modl_somf_transform_omp(modl_somf_plan *pl, const void *d_Dt, const void *d_G, const void *d_X, int64_t ldx, int64_t n,
+                            int n_nonzero, double tol, void *d_code_out, int32_t *d_support_out, int32_t *d_n_active_out,
+                            void *stream) {
+    if (!pl || !d_Dt || !d_X || !d_code_out || n < 0 || ldx < pl->d.p) return MODL_EINVAL;
+    if (!omp_args_ok(0, pl->d.k, n_nonzero, false)) return MODL_EINVAL;
+    if (n == 0) return MODL_OK;
+    DeviceScope dev(pl);
+    return DISPATCH(pl,
+                    transform_omp_impl<float>(pl, static_cast<const float *>(d_Dt), static_cast<const float *>(d_G),
+                                              static_cast<const float *>(d_X), ldx, n, n_nonzero, (float)tol,
+                                              static_cast<float *>(d_code_out), d_support_out, d_n_active_out,
+                                              (hipStream_t)stream),
+                    transform_omp_impl<double>(pl, static_cast<const double *>(d_Dt), static_cast<const double *>(d_G),
+                                               static_cast<const double *>(d_X), ldx, n, n_nonzero, tol,
+                                               static_cast<double *>(d_code_out), d_support_out, d_n_active_out,
+                                               (hipStream_t)stream));
 }
 
 // rows d_idx[0..n) of a row-major device matrix, gathered into d_dst (the row permutations of fit / shuffle,

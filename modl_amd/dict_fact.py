@@ -431,8 +431,8 @@ class HipBackend:
                                                   stream_ptr(self.device)), 'modl_somf_apply_and_update_dict')
         self._pending = None
 
-    def transform(self, Xh, kw, G=None, to_host=True):
-        """Codes from a warm start of ones, in chunks of a dedicated plan (large max_batch)."""
+    def _transform_plan(self, kw):
+        """the dedicated plan of transform / omp (large max_batch), rebuilt when the coding parameters change"""
         kw = dict(kw, max_batch=4096, G_agg='masked', Dx_agg='masked', optimizer='variational')
         if getattr(self, 'tplan', None) is None or kw != self._tplan_kw:
             if getattr(self, 'tplan', None):
@@ -443,6 +443,10 @@ class HipBackend:
             with torch.cuda.device(self.device):
                 check(lib.modl_somf_plan_create(C.byref(d), C.byref(h)), 'modl_somf_plan_create')
             self.tplan, self._tplan_kw = h, kw
+
+    def transform(self, Xh, kw, G=None, to_host=True):
+        """Codes from a warm start of ones, in chunks of a dedicated plan (large max_batch)."""
+        self._transform_plan(kw)
         n = Xh.shape[0]
         out = torch.empty((n, self.k), dtype=torch_dtype(self.dtype), device=self.device)
         check(lib.modl_somf_transform(self.tplan, ptr(self.Dt), ptr(G), ptr(Xh), Xh.stride(0), n, ptr(out),
@@ -503,6 +507,58 @@ class HipBackend:
                       'modl_enet_regression_multi_gram')
             code[rows] = out
         return code
+
+    def omp(self, Xh, n_nonzero, tol, G=None, obs=None, *, kw, nobs=None):
+        """Orthogonal matching pursuit codes of the rows of Xh (n, p) (csrc/omp.hip): at most n_nonzero atoms per row and,
+        with tol (None: no threshold), only until the row's squared residual is <= tol.  Returns the device tensors
+        code (n, k), support (n, n_nonzero) int32 in selection order (-1 beyond the row's count) and n_active (n,) int32.
+        Without obs: modl_somf_transform_omp (the Gram matrix and Dx as `transform` forms them).  With obs (n, p) uint8,
+        1 = observed, the split of `transform_masked`: rows without a hole take the shared route, rows without an
+        observed entry get zero codes and n_active 0, the others go chunk by chunk through modl_masked_gram_* and
+        modl_omp_gram_* with a Gram matrix of their own, where the squared norm is r |x_S|^2 as G = r D_S D_S^T and
+        Dx = r x_S D_S^T are.  kw: the estimator's plan parameters (`_plan_kwargs`), for the plan that forms the products."""
+        n, s = Xh.shape[0], int(n_nonzero)
+        td, dev = torch_dtype(self.dtype), self.device
+        tolv = -1.0 if tol is None else float(tol)
+        if obs is None or n == 0:
+            self._transform_plan(kw)
+            code = torch.empty((n, self.k), dtype=td, device=dev)
+            support = torch.empty((n, s), dtype=torch.int32, device=dev)
+            n_active = torch.empty(n, dtype=torch.int32, device=dev)
+            check(lib.modl_somf_transform_omp(self.tplan, ptr(self.Dt), ptr(G), ptr(Xh), Xh.stride(0), n, s, tolv, ptr(code),
+                                              ptr(support), ptr(n_active), stream_ptr(dev)), 'modl_somf_transform_omp')
+            return code, support, n_active
+        if nobs is None:
+            nobs = obs.sum(dim=1, dtype=torch.int32)
+        clean = torch.nonzero(nobs == self.p).flatten()
+        if clean.shape[0] == n:
+            return self.omp(Xh, s, tol, G, kw=kw)
+        code = torch.zeros((n, self.k), dtype=td, device=dev)
+        support = torch.full((n, s), -1, dtype=torch.int32, device=dev)
+        n_active = torch.zeros(n, dtype=torch.int32, device=dev)
+        if clean.shape[0]:
+            code[clean], support[clean], n_active[clean] = self.omp(Xh[clean], s, tol, G, kw=kw)
+        holed = torch.nonzero((nobs > 0) & (nobs < self.p)).flatten()
+        if holed.shape[0] == 0:
+            return code, support, n_active
+        solve = getattr(lib, 'modl_omp_gram_' + sfx(self.dtype))
+        step = self.masked_chunk_rows()
+        for c0 in range(0, holed.shape[0], step):
+            rows = holed[c0:c0 + step].contiguous()
+            b = rows.shape[0]
+            Gm, Dx, _ = self.masked_gram(Xh, obs, rows)
+            xn = None
+            if tol is not None:
+                Xc = torch.where(obs[rows] != 0, Xh[rows], torch.zeros((), dtype=Xh.dtype, device=Xh.device))
+                xn = ((Xc * Xc).sum(dim=1) * (self.p / nobs[rows].to(td))).contiguous()
+            out = torch.empty((b, self.k), dtype=td, device=dev)
+            sup = torch.empty((b, s), dtype=torch.int32, device=dev)
+            na = torch.empty(b, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):                            # (no scratch: modl_omp_workspace is 0)
+                check(solve(ptr(Gm), self.k * self.k, ptr(Dx), ptr(xn), b, self.k, s, tolv, ptr(out), ptr(sup), ptr(na),
+                            None, 0, stream_ptr(dev)), 'modl_omp_gram')
+            code[rows], support[rows], n_active[rows] = out, sup, na
+        return code, support, n_active
 
     def decode(self, code, mean=None, den=None):
         """code D as a (n, p) device tensor; with the (n, C) statistics of modl_image_grid_patches_* the decoded patches
@@ -761,7 +817,8 @@ class CodingMixin(TransformerMixin):
                     comp_l1_ratio=g('comp_l1_ratio', 0), tol=self.tol, step_size=g('step_size', 1),
                     max_batch=max_batch)
 
-    def _transform(self, X, to_host):
+    def _stage_rows(self, X):
+        """(rows on the device, the full Gram matrix if the estimator keeps one) for the coders"""
         check_is_fitted(self, 'components_')
         be = self._backend
         if not isinstance(X, torch.Tensor):
@@ -770,14 +827,52 @@ class CodingMixin(TransformerMixin):
         if Xh.shape[1] != be.p:
             raise ValueError('X has %d features, the dictionary has %d' % (Xh.shape[1], be.p))
         use_G = getattr(self, 'G_agg', None) == 'full' and be.G is not None
-        return Xh, be.transform(Xh, self._plan_kwargs(4096), be.G if use_G else None, to_host=to_host)
+        return Xh, be.G if use_G else None
 
-    def transform(self, X, mask=None):
+    def _transform(self, X, to_host):
+        Xh, G = self._stage_rows(X)
+        return Xh, self._backend.transform(Xh, self._plan_kwargs(4096), G, to_host=to_host)
+
+    def _omp_params(self, algorithm, n_nonzero_coefs, residual_tol):
+        """(n_nonzero, tol) of an OMP call, or None for the elastic-net coder; ValueError for what neither coder takes"""
+        if algorithm == 'enet':
+            if n_nonzero_coefs is not None or residual_tol is not None:
+                raise ValueError("n_nonzero_coefs and residual_tol belong to algorithm='omp'")
+            return None
+        if algorithm != 'omp':
+            raise ValueError("algorithm must be 'enet' or 'omp', got %r" % (algorithm,))
+        k = self.n_components
+        if n_nonzero_coefs is None:
+            # scikit-learn's rule (10 % of the atoms) when nothing is given; with a threshold the support is only capped
+            s = max(1, k // 10) if residual_tol is None else k
+            s = min(s, _lib.OMP_MAX_NONZERO, k)
+        else:
+            s = int(n_nonzero_coefs)
+            if s != n_nonzero_coefs or not 1 <= s <= min(_lib.OMP_MAX_NONZERO, k):
+                raise ValueError('n_nonzero_coefs must be an integer in 1 .. min(%d, n_components = %d), got %r'
+                                 % (_lib.OMP_MAX_NONZERO, k, n_nonzero_coefs))
+        if residual_tol is not None and not residual_tol >= 0:
+            raise ValueError('residual_tol is a squared residual norm: it must be >= 0, got %r' % (residual_tol,))
+        return s, residual_tol
+
+    def transform(self, X, mask=None, algorithm='enet', n_nonzero_coefs=None, residual_tol=None):
         """Codes of the rows of X on the dictionary (dict_fact.py:47-92).  With `mask` (a boolean array or tensor of X's
         shape, True = observed) every row is coded on its observed entries only, by the estimator of the SOMF step
         itself with the row's own subset (dict_fact.py:594-604: Dx = r X_S D_S^T, G = r D_S D_S^T, r = p / |S|): rows
         without a hole are coded as without a mask, rows without an observed entry get zero codes; values of X at
-        unobserved positions are never used.  Needs n_components <= MASKED_MAX_COMPONENTS."""
+        unobserved positions are never used.  Needs n_components <= MASKED_MAX_COMPONENTS.
+
+        algorithm='omp' codes by orthogonal matching pursuit instead of the elastic-net solve (`code_alpha` is not
+        used): at most `n_nonzero_coefs` atoms per row (default max(1, n_components // 10), at most OMP_MAX_NONZERO =
+        64) and, with `residual_tol` (the largest squared residual norm of a row, the `tol` of scikit-learn's
+        orthogonal_mp_gram; the name `tol` is the coordinate-descent tolerance here), only until the row is explained
+        that well, `n_nonzero_coefs` still capping the support (default 64).  With a mask the residual is the estimate
+        r |x_S - code D_S|^2."""
+        omp = self._omp_params(algorithm, n_nonzero_coefs, residual_tol)
+        if mask is None and omp is not None:
+            Xh, G = self._stage_rows(X)
+            code = self._backend.omp(Xh, omp[0], omp[1], G, kw=self._plan_kwargs(4096))[0]
+            return code if isinstance(X, torch.Tensor) else code.cpu().numpy()
         if mask is None:
             return self._transform(X, True)[1]
         if tuple(np.shape(mask)) != tuple(np.shape(X)) or len(np.shape(X)) != 2:
@@ -802,7 +897,10 @@ class CodingMixin(TransformerMixin):
         if Xh.shape[1] != be.p:
             raise ValueError('X has %d features, the dictionary has %d' % (Xh.shape[1], be.p))
         use_G = getattr(self, 'G_agg', None) == 'full' and be.G is not None
-        code = be.transform_masked(Xh, obs, self._plan_kwargs(4096), be.G if use_G else None)
+        if omp is not None:
+            code = be.omp(Xh, omp[0], omp[1], be.G if use_G else None, obs=obs, kw=self._plan_kwargs(4096))[0]
+        else:
+            code = be.transform_masked(Xh, obs, self._plan_kwargs(4096), be.G if use_G else None)
         return code.cpu().numpy() if on_host else code
 
     def inverse_transform(self, code):

@@ -497,14 +497,19 @@ class ImageDictFact(BaseEstimator):
     def score(self, patches):
         return self.dict_fact_.score(self._prep(patches))
 
-    def reconstruct(self, image, stride=1, rows_per_pass=None):
+    def reconstruct(self, image, stride=1, rows_per_pass=None, algorithm='enet', n_nonzero_coefs=None,
+                    residual_tol=None):
         """The image rebuilt from the sparse codes of its patches: every window of the patch grid (`grid_origins`:
         stride `stride`, an int or a pair, the last window clamped to the border) is scaled as in `fit`, encoded on the
         fitted dictionary, decoded, put back on the image's scale, and the overlapping windows are averaged.  Returns
         an array of the image's shape in the dtype of the fitted dictionary (the input is cast as `transform` casts).
         Image, patches, codes and sums stay on the device, `rows_per_pass` grid rows at a time (default: as many as keep
-        the patch buffer under 256 MB); the result does not depend on it.  The value -1 is ordinary data here."""
+        the patch buffer under 256 MB); the result does not depend on it.  The value -1 is ordinary data here.
+        `algorithm`, `n_nonzero_coefs`, `residual_tol`: the coder, as in `DictFact.transform` ('omp': orthogonal matching
+        pursuit).  The threshold applies to the rows as they are coded, that is after the per-patch scaling of `fit`
+        (centred and, by the setting, divided by the patch's norm), not to the pixels of the image."""
         check_is_fitted(self, 'dict_fact_')
+        omp = self.dict_fact_._omp_params(algorithm, n_nonzero_coefs, residual_tol)
         be = self.dict_fact_._backend
         g = _grid(np.shape(image), self.patch_shape_[:2], stride)
         if g[2] != self.patch_shape_[2]:
@@ -518,13 +523,16 @@ class ImageDictFact(BaseEstimator):
         acc = torch.zeros(g[:3], dtype=torch.float64, device=be.device)
         for row0, nrows in _passes(grows, gcols, be.p * be.dtype.itemsize, rows_per_pass):
             patches, mean, den = _grid_patches_pass(d_image, g, gcols, row0, nrows, s['with_mean'], s['with_std'])
-            code = be.transform(patches, kw, G, to_host=False)
+            if omp is not None:
+                code = be.omp(patches, omp[0], omp[1], G, kw=kw)[0]
+            else:
+                code = be.transform(patches, kw, G, to_host=False)
             _overlap_add(be.decode(code, mean, den), g, row0, nrows, acc)
         out = _overlap_finish(acc, g, d_image.dtype)
         return out.cpu().numpy() if on_host else out
 
     def inpaint(self, image, mask=None, stride=1, missing=-1, keep_observed=True, rows_per_pass=None,
-                return_filled=False):
+                return_filled=False, algorithm='enet', n_nonzero_coefs=None, residual_tol=None):
         """The image with its missing elements filled in from the fitted dictionary.  `mask` is a bool array of shape
         (H, W) or (H, W, C), True = observed; None: `image != missing`, element by element (`clean_mask`'s rule).  As
         `reconstruct`, on the same patch grid, but every window is scaled by the statistics of its observed elements
@@ -534,8 +542,12 @@ class ImageDictFact(BaseEstimator):
         observed ones.  Shape, dtype, host / device in -> out and the independence from `rows_per_pass` are those of
         `reconstruct`; on an image without holes `inpaint(image, keep_observed=False)` is `reconstruct(image)` bit
         for bit.  With `return_filled` the (H, W) bool array of the pixels that a used window covers comes along.
-        Holes wider than a patch are not filled (the method is not iterated)."""
+        Holes wider than a patch are not filled (the method is not iterated).
+        `algorithm`, `n_nonzero_coefs`, `residual_tol`: the coder, as in `DictFact.transform` with a mask.  The threshold
+        applies to the rows as they are coded, after the per-patch scaling by the statistics of the observed elements:
+        a window's residual is r |x_S - code D_S|^2 on its scaled observed elements."""
         check_is_fitted(self, 'dict_fact_')
+        omp = self.dict_fact_._omp_params(algorithm, n_nonzero_coefs, residual_tol)
         be = self.dict_fact_._backend
         g = _grid(np.shape(image), self.patch_shape_[:2], stride)
         if g[2] != self.patch_shape_[2]:
@@ -562,7 +574,10 @@ class ImageDictFact(BaseEstimator):
         for row0, nrows in _passes(grows, gcols, be.p * be.dtype.itemsize, rows_per_pass):
             patches, mean, den, obs, nobs = _grid_patches_masked_pass(d_image, d_obs, g, gcols, row0, nrows,
                                                                       s['with_mean'], s['with_std'])
-            code = be.transform_masked(patches, obs, kw, G, nobs=nobs)
+            if omp is not None:
+                code = be.omp(patches, omp[0], omp[1], G, obs=obs, kw=kw, nobs=nobs)[0]
+            else:
+                code = be.transform_masked(patches, obs, kw, G, nobs=nobs)
             use = (nobs > 0).to(torch.uint8)
             _overlap_add_weighted(be.decode(code, mean, den), use, g, row0, nrows, acc, cnt)
         out = _inpaint_finish(acc, cnt, d_image, d_obs, keep_observed)
