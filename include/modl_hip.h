@@ -726,6 +726,33 @@ int modl_objective_f32(const float *d_X, int64_t ldx, int64_t n, int64_t p, cons
                        void *d_ws, size_t ws_bytes, double *d_out3, void *stream);
 int modl_objective_f64(const double *d_X, int64_t ldx, int64_t n, int64_t p, const double *d_Dt, int k, const double *d_code,
                        void *d_ws, size_t ws_bytes, double *d_out3, void *stream);
+/* The sums behind CodingMixin.score(X, mask) and held_out_error on rows with missing entries, in one pass over d_X and
+ * the selection bytes.  d_X[n][ldx], d_sel[n][lds] (bytes), d_Dt[p][k], d_code[n][k], d_row_w[n] (f64; NULL = all ones).
+ * res_ie = d_X[i][e] - sum_j d_code[i][j] d_Dt[e][j]: the product on the matrix cores in the dtype, the difference in
+ * the dtype, the square and every sum in f64.  Entry (i, e) belongs to class c in {1, 2} when d_sel[i][e] == c; any
+ * other byte selects nothing.  Per class  S_c = sum res^2,  W_c = sum_i w_i sum_e res^2,  N_c = the number of entries:
+ *   d_out8 = [ S_1, W_1, N_1, S_2, W_2, N_2, sum |code|, sum code^2 ]     (the code norms over all n rows)
+ * An entry of d_X that is not selected is dropped by a select and enters no arithmetic: NaN or Inf there leaves the eight
+ * numbers unchanged bit for bit.  Nothing of size n x p is written; every workgroup leaves its partial sums in d_ws
+ * (modl_masked_objective_workspace() bytes) and a last one-workgroup launch adds them in a fixed order: no atomics, the
+ * same bits from run to run.  n == 0 gives eight zeros.  MODL_EINVAL before any device work: a NULL d_X, d_sel, d_Dt,
+ * d_code, d_out8 or d_ws, n < 0, p < 1, k < 1 or k > MODL_MAX_COMPONENTS, ldx < p, lds < p (or more than 2^31 - 1 tiles
+ * of 64 x 64); ws_bytes too small: MODL_ENOMEM. */
+size_t modl_masked_objective_workspace(int dtype, int64_t n, int64_t p);
+int modl_masked_objective_f32(const float *d_X, int64_t ldx, const uint8_t *d_sel, int64_t lds, int64_t n, int64_t p,
+                              const float *d_Dt, int k, const float *d_code, const double *d_row_w, void *d_ws,
+                              size_t ws_bytes, double *d_out8, void *stream);
+int modl_masked_objective_f64(const double *d_X, int64_t ldx, const uint8_t *d_sel, int64_t lds, int64_t n, int64_t p,
+                              const double *d_Dt, int k, const double *d_code, const double *d_row_w, void *d_ws,
+                              size_t ws_bytes, double *d_out8, void *stream);
+/* Rows completed by their reconstruction: d_out[i][e] = d_obs[i][e] != 0 ? d_X[i][e] : sum_j d_code[i][j] d_Dt[e][j]
+ * (a select: observed entries carry the bits of d_X, d_X at unobserved positions is never used).  d_out[n][ldout] must
+ * not overlap d_X.  One launch, no scratch.  The same checks: a NULL pointer, n < 0, p < 1, k out of range, ldx, ldo or
+ * ldout below p -> MODL_EINVAL before any device work; n == 0 does nothing. */
+int modl_impute_f32(const float *d_code, int64_t n, int k, const float *d_Dt, int64_t p, const float *d_X, int64_t ldx,
+                    const uint8_t *d_obs, int64_t ldo, float *d_out, int64_t ldout, void *stream);
+int modl_impute_f64(const double *d_code, int64_t n, int k, const double *d_Dt, int64_t p, const double *d_X, int64_t ldx,
+                    const uint8_t *d_obs, int64_t ldo, double *d_out, int64_t ldout, void *stream);
 
 /* Amari discrepancy between dictionaries (modl/decomposition/stability.py:7-31: amari_discrepency,
  * mean_amari_discrepency).  For the n dictionaries h_d_dicts[i] (device, row-major k_i x p, atoms in rows), every pair

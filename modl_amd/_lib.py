@@ -172,10 +172,14 @@ def bind(lib):
              C.c_int, _i64, _i64, _vp, _vp, _vp, _vp)
         _sig('modl_image_inpaint_finish_' + _sfx, C.c_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp)
         _sig('modl_objective_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, C.c_int, _vp, _vp, _sz, _vp, _vp)
+        _sig('modl_masked_objective_' + _sfx, C.c_int, _vp, _i64, _vp, _i64, _i64, _i64, _vp, C.c_int, _vp, _vp, _vp, _sz,
+             _vp, _vp)
+        _sig('modl_impute_' + _sfx, C.c_int, _vp, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp)
         _sig('modl_amari_' + _sfx, C.c_int, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _P(C.c_int))
     _sig('modl_image_fill', C.c_int, _i64, _i64, _i64, _vp)
     _sig('modl_image_grid_shape', C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _P(_i64), _P(_i64))
     _sig('modl_objective_workspace', _sz, C.c_int, _i64, _i64)
+    _sig('modl_masked_objective_workspace', _sz, C.c_int, _i64, _i64)
     _sig('modl_amari_workspace', _sz, C.c_int, C.c_int, _vp, _i64)
     _sig('modl_dict_update_workspace', _sz, C.c_int, _i64, C.c_int)
     _sig('modl_recsys_topn_workspace', _sz, C.c_int, _i64, C.c_int, _i64, C.c_int)

@@ -17,6 +17,7 @@ phases; all ranks then perform the identical dictionary update.
 import ctypes as C
 import os
 import time
+from collections import namedtuple
 from math import ceil
 
 import numpy as np
@@ -585,6 +586,31 @@ class HipBackend:
                     stream_ptr(self.device)), 'modl_objective')
         return out.cpu().numpy()
 
+    def masked_objective(self, Xh, sel, code, row_w=None):
+        """[S_1, W_1, N_1, S_2, W_2, N_2, sum |code|, sum code^2] (modl_masked_objective_*, csrc/masked_objective.hip): the
+        squared residuals of Xh - code D over the entries with sel == 1 and with sel == 2 (sel (n, p) uint8), plain (S),
+        weighted by the row weights row_w (n,) f64 (W; None: ones) and counted (N).  Unselected entries of Xh are never
+        used.  A numpy (8,) f64 array."""
+        n, p = Xh.shape
+        nbytes = lib.modl_masked_objective_workspace(dtype_id(self.dtype), n, p)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty(8, dtype=torch.float64, device=self.device)
+        f = getattr(lib, 'modl_masked_objective_' + sfx(self.dtype))
+        with torch.cuda.device(self.device):
+            check(f(ptr(Xh), Xh.stride(0), ptr(sel), sel.stride(0), n, p, ptr(self.Dt), self.k, ptr(code), ptr(row_w),
+                    ptr(ws), nbytes, ptr(out), stream_ptr(self.device)), 'modl_masked_objective')
+        return out.cpu().numpy()
+
+    def impute(self, code, Xh, obs):
+        """Xh where obs != 0 (its bits), code D elsewhere (modl_impute_*): a (n, p) device tensor."""
+        n = Xh.shape[0]
+        out = torch.empty((n, self.p), dtype=torch_dtype(self.dtype), device=self.device)
+        f = getattr(lib, 'modl_impute_' + sfx(self.dtype))
+        with torch.cuda.device(self.device):
+            check(f(ptr(code), n, self.k, ptr(self.Dt), self.p, ptr(Xh), Xh.stride(0), ptr(obs), obs.stride(0), ptr(out),
+                    self.p, stream_ptr(self.device)), 'modl_impute')
+        return out
+
     def last_sweeps(self):
         out = np.zeros(self._desc_kw['max_batch'], dtype=np.int32)
         n = C.c_int()
@@ -855,6 +881,42 @@ class CodingMixin(TransformerMixin):
             raise ValueError('residual_tol is a squared residual norm: it must be >= 0, got %r' % (residual_tol,))
         return s, residual_tol
 
+    def _check_masked_args(self, X, mask):
+        """the ValueErrors of a call with a mask that need no fitted estimator"""
+        if tuple(np.shape(mask)) != tuple(np.shape(X)) or len(np.shape(X)) != 2:
+            raise ValueError('mask of shape %s does not match X of shape %s (n_samples, n_features)'
+                             % (tuple(np.shape(mask)), tuple(np.shape(X))))
+        if self.n_components > MASKED_MAX_COMPONENTS:
+            raise ValueError('transform with a mask supports at most %d components (one Gram matrix per row), got %d'
+                             % (MASKED_MAX_COMPONENTS, self.n_components))
+
+    def _stage_masked(self, X, mask):
+        """(rows on the device, mask as uint8 on the device, whether X came from the host, the full Gram matrix if the
+        estimator keeps one) for the calls with a mask; host rows are zero-filled at their unobserved entries"""
+        check_is_fitted(self, 'components_')
+        be = self._backend
+        on_host = not isinstance(X, torch.Tensor)
+        if isinstance(mask, torch.Tensor):
+            obs = (mask != 0).to(device=be.device, dtype=torch.uint8).contiguous()
+        else:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0)
+            obs = torch.from_numpy(mask.view(np.uint8)).to(be.device)
+        if on_host:
+            # unobserved entries may hold anything (NaN included): they are not validated, and never used
+            m = mask if isinstance(mask, np.ndarray) else obs.cpu().numpy() != 0
+            X = check_array(np.where(m, X, 0), order='C', dtype=be.dtype.type)
+        Xh = be.stage_X(X)
+        if Xh.shape[1] != be.p:
+            raise ValueError('X has %d features, the dictionary has %d' % (Xh.shape[1], be.p))
+        use_G = getattr(self, 'G_agg', None) == 'full' and be.G is not None
+        return Xh, obs, on_host, be.G if use_G else None
+
+    def _masked_codes(self, Xh, obs, G, omp):
+        be = self._backend
+        if omp is not None:
+            return be.omp(Xh, omp[0], omp[1], G, obs=obs, kw=self._plan_kwargs(4096))[0]
+        return be.transform_masked(Xh, obs, self._plan_kwargs(4096), G)
+
     def transform(self, X, mask=None, algorithm='enet', n_nonzero_coefs=None, residual_tol=None):
         """Codes of the rows of X on the dictionary (dict_fact.py:47-92).  With `mask` (a boolean array or tensor of X's
         shape, True = observed) every row is coded on its observed entries only, by the estimator of the SOMF step
@@ -875,32 +937,9 @@ class CodingMixin(TransformerMixin):
             return code if isinstance(X, torch.Tensor) else code.cpu().numpy()
         if mask is None:
             return self._transform(X, True)[1]
-        if tuple(np.shape(mask)) != tuple(np.shape(X)) or len(np.shape(X)) != 2:
-            raise ValueError('mask of shape %s does not match X of shape %s (n_samples, n_features)'
-                             % (tuple(np.shape(mask)), tuple(np.shape(X))))
-        if self.n_components > MASKED_MAX_COMPONENTS:
-            raise ValueError('transform with a mask supports at most %d components (one Gram matrix per row), got %d'
-                             % (MASKED_MAX_COMPONENTS, self.n_components))
-        check_is_fitted(self, 'components_')
-        be = self._backend
-        on_host = not isinstance(X, torch.Tensor)
-        if isinstance(mask, torch.Tensor):
-            obs = (mask != 0).to(device=be.device, dtype=torch.uint8).contiguous()
-        else:
-            mask = np.ascontiguousarray(np.asarray(mask) != 0)
-            obs = torch.from_numpy(mask.view(np.uint8)).to(be.device)
-        if on_host:
-            # unobserved entries may hold anything (NaN included): they are not validated, and never used
-            m = mask if isinstance(mask, np.ndarray) else obs.cpu().numpy() != 0
-            X = check_array(np.where(m, X, 0), order='C', dtype=be.dtype.type)
-        Xh = be.stage_X(X)
-        if Xh.shape[1] != be.p:
-            raise ValueError('X has %d features, the dictionary has %d' % (Xh.shape[1], be.p))
-        use_G = getattr(self, 'G_agg', None) == 'full' and be.G is not None
-        if omp is not None:
-            code = be.omp(Xh, omp[0], omp[1], be.G if use_G else None, obs=obs, kw=self._plan_kwargs(4096))[0]
-        else:
-            code = be.transform_masked(Xh, obs, self._plan_kwargs(4096), be.G if use_G else None)
+        self._check_masked_args(X, mask)
+        Xh, obs, on_host, G = self._stage_masked(X, mask)
+        code = self._masked_codes(Xh, obs, G, omp)
         return code.cpu().numpy() if on_host else code
 
     def inverse_transform(self, code):
@@ -916,13 +955,87 @@ class CodingMixin(TransformerMixin):
         out = be.decode(to_device(code, be.device, dtype=be.dtype))
         return out.cpu().numpy() if on_host else out
 
-    def score(self, X):
+    def score(self, X, mask=None):
         """Objective value on test data X (dict_fact.py:94-114).  Test data, codes and dictionary stay on the device:
-        only the three sums of the objective come back (X may be a device tensor, e.g. a scorer's resident test set)."""
+        only the three sums of the objective come back (X may be a device tensor, e.g. a scorer's resident test set).
+
+        With `mask` (True = observed) the value is the objective each row's masked solve of `transform(X, mask)`
+        minimises, G = r D_S D_S^T, Dx = r x_S D_S^T with r = p / m_i for a row with m_i observed entries:
+        (sum_i r_i |x_iS - code_i D_S|^2 / 2 + code_alpha (l1_ratio |code|_1 + (1 - l1_ratio) / 2 |code|^2)) / n, rows
+        without an observed entry weighing nothing.  Unobserved entries of X are never used; with a full mask this is
+        score(X) up to the order of the sums."""
+        if mask is not None:
+            self._check_masked_args(X, mask)
+            Xh, obs, _, G = self._stage_masked(X, mask)
+            code = self._masked_codes(Xh, obs, G, None)
+            m = obs.sum(dim=1, dtype=torch.float64)
+            row_w = torch.where(m > 0, Xh.shape[1] / m, torch.zeros_like(m))
+            s = self._backend.masked_objective(Xh, obs, code, row_w)
+            regul = self.code_alpha * (s[6] * self.code_l1_ratio + (1 - self.code_l1_ratio) * s[7] / 2)
+            return float((s[1] / 2 + regul) / Xh.shape[0])
         Xh, code = self._transform(X, False)
         sq_res, norm1_code, norm2_code = self._backend.objective(Xh, code)
         regul = self.code_alpha * (norm1_code * self.code_l1_ratio + (1 - self.code_l1_ratio) * norm2_code / 2)
         return float((sq_res / 2 + regul) / Xh.shape[0])
+
+    def held_out_error(self, X, mask=None, held_out=0.1, random_state=None, algorithm='enet', n_nonzero_coefs=None,
+                       residual_tol=None):
+        """Error of the dictionary on entries it was not shown: the observed entries (`mask`, True = observed; None:
+        all) are split by `held_out` - a boolean array or tensor of X's shape, or a fraction in (0, 1), in which case
+        H = check_random_state(random_state).random_sample(X.shape) < held_out -; every row is coded on mask & ~H by
+        the chosen coder (as `transform` with that mask; a row left without an entry gets a zero code) and the
+        reconstruction is compared with X on mask & H.  Returns HeldOutError(rmse, rmse_coded, n_held_out, n_coded):
+        the root mean squared residual over mask & H and over mask & ~H, and the two counts; an empty set gives nan.
+        The residuals are summed on the device in f64 (modl_masked_objective_*); unobserved entries are never used."""
+        omp = self._omp_params(algorithm, n_nonzero_coefs, residual_tol)
+        shape = tuple(np.shape(X))
+        if mask is None:
+            if len(shape) != 2:
+                raise ValueError('X of shape %s is not (n_samples, n_features)' % (shape,))
+        elif tuple(np.shape(mask)) != shape or len(shape) != 2:
+            raise ValueError('mask of shape %s does not match X of shape %s (n_samples, n_features)'
+                             % (tuple(np.shape(mask)), shape))
+        H = _held_out_set(held_out, shape, random_state)
+        if mask is None:
+            mask = torch.ones(shape, dtype=torch.bool, device=X.device) if isinstance(X, torch.Tensor) \
+                else np.ones(shape, dtype=bool)
+        self._check_masked_args(X, mask)
+        Xh, obs, _, G = self._stage_masked(X, mask)
+        Hd = H if isinstance(H, torch.Tensor) else torch.from_numpy(H)
+        sel = obs * (1 + Hd.to(device=obs.device, dtype=torch.uint8))        # 0 unobserved, 1 coded, 2 held out
+        code = self._masked_codes(Xh, (sel == 1).to(torch.uint8), G, omp)
+        s = self._backend.masked_objective(Xh, sel, code)
+        n_coded, n_held = int(s[2]), int(s[5])
+        return HeldOutError(float(np.sqrt(s[3] / n_held)) if n_held else float('nan'),
+                            float(np.sqrt(s[0] / n_coded)) if n_coded else float('nan'), n_held, n_coded)
+
+    def impute(self, X, mask, algorithm='enet', n_nonzero_coefs=None, residual_tol=None):
+        """X with its unobserved entries (`mask` False) replaced by code D, the rows being coded on their observed
+        entries as by `transform(X, mask, ...)`; observed entries keep their bits.  In the dictionary's dtype; a numpy
+        array gives a numpy array, a CUDA tensor a CUDA tensor."""
+        omp = self._omp_params(algorithm, n_nonzero_coefs, residual_tol)
+        self._check_masked_args(X, mask)
+        Xh, obs, on_host, G = self._stage_masked(X, mask)
+        out = self._backend.impute(self._masked_codes(Xh, obs, G, omp), Xh, obs)
+        return out.cpu().numpy() if on_host else out
+
+
+HeldOutError = namedtuple('HeldOutError', ['rmse', 'rmse_coded', 'n_held_out', 'n_coded'])
+
+
+def _held_out_set(held_out, shape, random_state):
+    """the hold-out set H of `held_out_error` as a boolean array (or tensor) of `shape`; ValueError for what is neither a
+    fraction in (0, 1) nor a boolean array of that shape"""
+    if isinstance(held_out, (float, np.floating)):
+        if not 0 < held_out < 1:
+            raise ValueError('held_out as a fraction must lie in (0, 1), got %r' % (held_out,))
+        return check_random_state(random_state).random_sample(shape) < held_out
+    H = held_out if isinstance(held_out, torch.Tensor) else np.asarray(held_out)
+    is_bool = H.dtype == torch.bool if isinstance(H, torch.Tensor) else H.dtype == np.bool_
+    if not is_bool or tuple(H.shape) != tuple(shape):
+        raise ValueError('held_out must be a fraction in (0, 1) or a boolean array of shape %s, got %s of shape %s'
+                         % (tuple(shape), H.dtype, tuple(H.shape)))
+    return H
 
 
 def _dist():

@@ -14,6 +14,7 @@ averages the overlapping windows, all on the device (`grid_origins`, `grid_patch
 `reconstruct_from_patches`; the kernels are in csrc/image.hip, "reconstruction")."""
 import ctypes as C
 import time
+from collections import namedtuple
 from math import sqrt
 
 import numpy as np
@@ -25,7 +26,10 @@ from sklearn.utils.validation import check_is_fitted
 
 from ._lib import lib, check
 from .device import default_device, ptr, stream_ptr, to_device
-from .dict_fact import DictFact
+from .dict_fact import DictFact, _held_out_set
+
+
+ImageHeldOutError = namedtuple('ImageHeldOutError', ['rmse', 'n_held_out', 'n_unfilled'])
 
 
 def scale_patches(X, with_mean=True, with_std=True, channel_wise=True, copy=True):
@@ -586,6 +590,42 @@ class ImageDictFact(BaseEstimator):
             return out
         filled = cnt > 0
         return out, (filled.cpu().numpy() if on_host else filled)
+
+    def held_out_error(self, image, mask=None, held_out=0.1, stride=1, missing=-1, random_state=None, algorithm='enet',
+                       n_nonzero_coefs=None, residual_tol=None):
+        """Error of `inpaint` on elements it was not shown.  The observed elements (`mask`, or `image != missing`) are
+        split by `held_out`: a bool array of shape (H, W) or (H, W, C), or a fraction in (0, 1), in which case
+        H = check_random_state(random_state).random_sample(image.shape) < held_out.  The image is inpainted from
+        observed & ~H (`inpaint(image, mask=observed & ~H, stride=stride, return_filled=True, ...)`) and compared with
+        its own values on observed & H.  Returns ImageHeldOutError(rmse, n_held_out, n_unfilled): the root mean squared
+        difference over the held-out elements that a used window covered (summed in f64 on the device; nan when there
+        is none), their number, and the number of held-out elements that no used window covered.  This is what a
+        `callback` of a masked fit calls: fit on mask & ~H, watch H."""
+        check_is_fitted(self, 'dict_fact_')
+        be = self.dict_fact_._backend
+        g = _grid(np.shape(image), self.patch_shape_[:2], stride)
+        if mask is not None and tuple(np.shape(mask)) not in (g[:2], g[:3]):
+            raise ValueError('mask of shape %s: %s or %s is expected' % (tuple(np.shape(mask)), g[:2], g[:3]))
+        if isinstance(held_out, (float, np.floating)):
+            H = _held_out_set(held_out, tuple(np.shape(image)), random_state)
+        else:
+            H = _held_out_set(held_out, g[:2] if len(np.shape(held_out)) == 2 else g[:3], random_state)
+
+        def on_device(m):
+            m = m if isinstance(m, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(m) != 0))
+            m = (m != 0).to(be.device)
+            return m if m.ndim == 3 else m[:, :, None].expand(g[:3])
+
+        d_image = _stage_image(image, be.device, dtype=be.dtype)
+        obs = (d_image != missing) if mask is None else on_device(mask)
+        H = on_device(H)
+        out, filled = self.inpaint(d_image, mask=obs & ~H, stride=stride, return_filled=True, algorithm=algorithm,
+                                   n_nonzero_coefs=n_nonzero_coefs, residual_tol=residual_tol)
+        held = obs & H
+        seen = held & filled[:, :, None]
+        diff = torch.where(seen, out.double() - d_image.double(), torch.zeros((), dtype=torch.float64, device=be.device))
+        sq, n_seen, n_held = float((diff * diff).sum()), int(seen.sum()), int(held.sum())
+        return ImageHeldOutError(sqrt(sq / n_seen) if n_seen else float('nan'), n_seen, n_held - n_seen)
 
     def stage_test_patches(self, patches):
         """Scaled, flattened test patches as a tensor on the estimator's device: `score_staged` then evaluates the
