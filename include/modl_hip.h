@@ -268,6 +268,33 @@ int modl_recsys_topn_f64(const double *d_code, const int64_t *d_code_rows, int64
                          const int32_t *d_ex_indptr, const int32_t *d_ex_indices, const int64_t *d_ex_rows,
                          const double *d_item_bias, int n_top, int32_t *d_items, double *d_scores, void *d_ws,
                          size_t ws_bytes, void *stream);
+/* Ranks of held-out items: where given items stand among the items a query has not excluded, without ever writing the b x p
+ * scores (csrc/recsys_rank.hip).  Queries, exclusions, d_Dt and d_item_bias are those of modl_recsys_topn_*, and score[ii][f]
+ * is that call's score bit for bit.  The targets of query ii are the entries d_t_indptr[ii] .. d_t_indptr[ii + 1] - 1 of
+ * d_t_indices (d_t_indptr: int32[b + 1]); t_max is the caller's promise of the longest target row.
+ *   d_ranks[e], for entry e of query ii with item t = d_t_indices[e]: the number of items c != t of 0 .. p-1 that are not
+ *   excluded for ii and beat t: a higher score, or an equal score and a smaller id.  With t not excluded that is the
+ *   position of t in the query's top-N list.  Whether t itself is excluded plays no part; the other targets of the query are
+ *   ordinary candidates; a repeated target gets its rank at every occurrence.  t outside 0 .. p-1: -1.  Entries of a row
+ *   beyond its first t_max: -2 (they are not otherwise read).  d_ranks is indexed as d_t_indices is.
+ *   d_n_candidates[ii] (int32[b], may be NULL): p minus the number of distinct in-range excluded items of query ii.
+ * The result is a function of the inputs alone (counts are summed as integers: no order enters).
+ * MODL_EINVAL before any device work: a NULL d_code / d_Dt / d_t_indptr / d_t_indices / d_ranks (or d_ex_indices with
+ * d_ex_indptr given), b < 0, p < 1 or p >= 2^31, t_max outside 1 .. MODL_RECSYS_MAX_RANK_TARGETS, k as for the top-N call.
+ * b == 0 does nothing.  d_ws NULL or smaller than modl_recsys_ranks_workspace(...): MODL_ENOMEM; no device: MODL_ENOGPU.
+ * Every refusal leaves the outputs untouched.  The workspace holds two bitmasks of p bits per query (exclusions, targets),
+ * t_max + 1 counters and t_max scores per query.  Asynchronous on `stream`. */
+#define MODL_RECSYS_MAX_RANK_TARGETS 64
+/* bytes of d_ws for a call with these arguments; 0 for arguments the call refuses (and for b == 0) */
+size_t modl_recsys_ranks_workspace(int dtype, int64_t p, int k, int64_t b, int t_max);
+int modl_recsys_ranks_f32(const float *d_code, const int64_t *d_code_rows, int64_t b, int k, const float *d_Dt, int64_t p,
+                          const int32_t *d_ex_indptr, const int32_t *d_ex_indices, const int64_t *d_ex_rows,
+                          const double *d_item_bias, const int32_t *d_t_indptr, const int32_t *d_t_indices, int t_max,
+                          int32_t *d_ranks, int32_t *d_n_candidates, void *d_ws, size_t ws_bytes, void *stream);
+int modl_recsys_ranks_f64(const double *d_code, const int64_t *d_code_rows, int64_t b, int k, const double *d_Dt, int64_t p,
+                          const int32_t *d_ex_indptr, const int32_t *d_ex_indices, const int64_t *d_ex_rows,
+                          const double *d_item_bias, const int32_t *d_t_indptr, const int32_t *d_t_indices, int t_max,
+                          int32_t *d_ranks, int32_t *d_n_candidates, void *d_ws, size_t ws_bytes, void *stream);
 /* One minibatch of RecsysDictFact._single_batch_fit (recsys.py:147-165, 168-213) in ONE call: the batch's ratings are
  * grouped by item on the host (batch order kept inside an item), staged through a pinned slot of the plan, and the
  * codes, the per-item B_ update, the C_ update and the dictionary update on the union of the batch's items are

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, 'libmodl_hip.so')
 
 MODL_F32, MODL_F64 = 0, 1
 RECSYS_MAX_TOPN = 128                           # MODL_RECSYS_MAX_TOPN
+RECSYS_MAX_RANK_TARGETS = 64                    # MODL_RECSYS_MAX_RANK_TARGETS
 OMP_MAX_NONZERO = 64                            # MODL_OMP_MAX_NONZERO
 FLAG_NO_RIDER, FLAG_GEMM_STAMPS = 1, 2          # modl_somf_desc.flags (diagnostics)
 DEBUG_CD_SPARSE_PCT = 1                         # modl_debug_set
@@ -147,6 +148,8 @@ def bind(lib):
         _sig('modl_recsys_predict_' + _sfx, C.c_int, _vp, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp)
         _sig('modl_recsys_topn_' + _sfx, C.c_int, _vp, _vp, _i64, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _sz,
              _vp)
+        _sig('modl_recsys_ranks_' + _sfx, C.c_int, _vp, _vp, _i64, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+             _vp, _sz, _vp)
         _sig('modl_omp_gram_' + _sfx, C.c_int, _vp, _i64, _vp, _vp, _i64, C.c_int, C.c_int, _ct, _vp, _vp, _vp, _vp, _sz, _vp)
         _sig('modl_gram_axpby_' + _sfx, C.c_int, _vp, _i64, C.c_int, _vp, _ct, _ct, _vp)
         _sig('modl_dict_update_' + _sfx, C.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _f64,
@@ -183,6 +186,7 @@ def bind(lib):
     _sig('modl_amari_workspace', _sz, C.c_int, C.c_int, _vp, _i64)
     _sig('modl_dict_update_workspace', _sz, C.c_int, _i64, C.c_int)
     _sig('modl_recsys_topn_workspace', _sz, C.c_int, _i64, C.c_int, _i64, C.c_int)
+    _sig('modl_recsys_ranks_workspace', _sz, C.c_int, _i64, C.c_int, _i64, C.c_int)
     _sig('modl_omp_workspace', _sz, C.c_int, _i64, C.c_int, C.c_int, C.c_int)
     _sig('modl_recsys_plan_create', C.c_int, C.c_int, _i64, C.c_int, _i64, _i64, _P(_vp))
     _sig('modl_recsys_plan_destroy', None, _vp)

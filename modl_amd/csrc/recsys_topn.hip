@@ -19,25 +19,10 @@
 //      only ever rejects what n_top earlier elements beat: the list is a function of the inputs, not of the arrival order.
 //   3. recsys_topn_merge_kernel (only with more than one slab): one wavefront per query merges the slabs' sorted lists under
 //      the same total order.  The order is total, so the result does not depend on the slab count.
-#include "gemm.hpp"
+#include "recsys_topn.hpp"
 #include <limits>
 
 namespace modl {
-
-constexpr int kTopnUsers = 32;        // queries of a workgroup
-constexpr int kTopnKC = 64;           // contraction chunk staged at a time
-constexpr int kTopnMergeMin = 32;     // candidates of a query that trigger a merge
-constexpr int kTopnMaxSlabs = 64;     // one list per lane of the merging wavefront
-constexpr int kTopnMinSlab = 256;     // items: the shortest slab
-constexpr int kTopnTargetWgs = 512;
-
-template <typename T> struct TopnCfg;
-template <> struct TopnCfg<float> { static constexpr int WN = 32, RM = 1, KMAX = 186; };     // items per wavefront and tile
-template <> struct TopnCfg<double> { static constexpr int WN = 16, RM = 2, KMAX = 127; };
-
-template <typename T> __device__ __forceinline__ bool topn_beats(T sa, int ia, T sb, int ib) {
-    return sa > sb || (sa == sb && ia < ib);
-}
 
 __global__ __launch_bounds__(256) void recsys_topn_mask_kernel(const int32_t *indptr, const int32_t *indices,
                                                                const int64_t *ex_rows, int64_t b, int64_t p, int64_t W,
@@ -297,19 +282,6 @@ __global__ __launch_bounds__(64) void recsys_topn_merge_kernel(const int32_t *pa
             cur_i = (lane < S && h < n_top) ? ni : -1;
         }
     }
-}
-
-// the dispatch: slabs of a call (stages of IT items per slab)
-template <typename T> static int topn_slabs(int64_t p, int64_t b, int64_t *slab_items) {
-    constexpr int IT = 4 * TopnCfg<T>::WN;
-    const int64_t tiles = cdiv(b, kTopnUsers);
-    int64_t want = kTopnTargetWgs / tiles;
-    want = want < 1 ? 1 : (want > kTopnMaxSlabs ? kTopnMaxSlabs : want);
-    const int64_t nst = cdiv(p, IT);
-    int64_t sps = cdiv(nst, want);
-    if (sps < kTopnMinSlab / IT) sps = kTopnMinSlab / IT;
-    *slab_items = sps * IT;
-    return (int)cdiv(nst, sps);
 }
 
 struct TopnWs { size_t mask, part_items, part_scores, total; int64_t W; };

@@ -6,6 +6,7 @@ kernels (csrc/recsys.hip), the dictionary update reuses the dense path's
 block-coordinate kernels."""
 import ctypes as C
 import os
+from collections import namedtuple
 from math import log, ceil
 
 import numpy as np
@@ -14,7 +15,7 @@ import torch
 from sklearn.base import BaseEstimator
 from sklearn.utils import check_array, check_random_state, gen_batches
 
-from ._lib import lib, check, RECSYS_MAX_TOPN
+from ._lib import lib, check, RECSYS_MAX_TOPN, RECSYS_MAX_RANK_TARGETS
 from .device import default_device, dtype_id, sfx, torch_dtype, ptr, stream_ptr, to_device, transpose_to
 from .randomkit import batch_weight
 
@@ -26,6 +27,10 @@ MAX_COMPONENTS = {np.dtype(np.float32): 186, np.dtype(np.float64): 127}
 # recommend(): the longest list modl_recsys_topn_* returns (MODL_RECSYS_MAX_TOPN), and the workspace a call may take
 MAX_TOPN = RECSYS_MAX_TOPN
 TOPN_WORKSPACE_BYTES = 256 << 20
+# ranks(): the longest target row of one query of modl_recsys_ranks_* (MODL_RECSYS_MAX_RANK_TARGETS); longer rows are split
+MAX_RANK_TARGETS = RECSYS_MAX_RANK_TARGETS
+
+RankingScore = namedtuple('RankingScore', ['hit_rate', 'precision', 'recall', 'ndcg', 'mrr', 'auc', 'n_users', 'n_targets'])
 
 
 def compute_biases(X, beta=0, inplace=False):
@@ -53,6 +58,51 @@ def rmse(X_true, X_pred):
     X_true = check_array(X_true, accept_sparse='csr')
     X_pred = check_array(X_pred, accept_sparse='csr')
     return np.sqrt(np.mean((X_true.data - X_pred.data) ** 2))
+
+
+def ranking_metrics(ranks, indptr, n_candidates, n_items):
+    """Ranking figures at n_items from 0-based ranks: a RankingScore.  ranks[indptr[u]:indptr[u + 1]] are the ranks of the
+    m targets of user u among the user's n_candidates[u] candidates (the targets are distinct candidates; a target's rank
+    counts the user's other targets that beat it).  Per user, with hits = #(rank < n_items):
+    hit_rate = [hits > 0]; precision = hits / n_items; recall = hits / m; ndcg = sum_{rank < n_items} 1 / log2(rank + 2) over
+    its best possible value sum_{i < min(m, n_items)} 1 / log2(i + 2); mrr = 1 / (min rank + 1); auc = the share of the
+    m (n_candidates - m) pairs (target, other candidate) that the target wins.  Means over the users with targets (auc: over
+    those with n_candidates > m as well); NaN where no user is left.  Host code, float64."""
+    ranks = np.asarray(ranks, dtype=np.int64)
+    indptr = np.asarray(indptr, dtype=np.int64)
+    n_candidates = np.asarray(n_candidates, dtype=np.int64)
+    n_items = int(n_items)
+    n_u = len(indptr) - 1
+    if n_items < 1 or n_u < 0 or ranks.shape != (int(indptr[-1]) - int(indptr[0]),) or n_candidates.shape != (n_u,):
+        raise ValueError('ranking_metrics: ranks, indptr and n_candidates do not fit together, or n_items < 1')
+    if np.any(ranks < 0):
+        raise ValueError('ranking_metrics: a rank is negative (a target outside the items?)')
+    m = np.diff(indptr)
+    start = indptr[:-1] - indptr[0]
+    user = np.repeat(np.arange(n_u), m)
+    hit = ranks < n_items
+    hits = np.bincount(user, weights=hit, minlength=n_u)
+    dcg = np.bincount(user, weights=np.where(hit, 1.0 / np.log2(ranks + 2.0), 0.0), minlength=n_u)
+    ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(n_items) + 2.0))])[np.minimum(m, n_items)]
+    best = np.full(n_u, np.iinfo(np.int64).max)
+    np.minimum.at(best, user, ranks)
+    # j_t, the user's own targets that beat t: its place among the user's ranks (equal ranks share the first place)
+    order = np.lexsort((ranks, user))
+    su, sr = user[order], ranks[order]
+    idx = np.arange(len(sr))
+    new = np.ones(len(sr), dtype=bool)
+    new[1:] = (su[1:] != su[:-1]) | (sr[1:] != sr[:-1])
+    first = np.maximum.accumulate(np.where(new, idx, 0)) if len(sr) else idx
+    lost = np.bincount(su, weights=(sr - (first - start[su])).astype(np.float64), minlength=n_u)
+    has = m > 0
+    mh = m[has].astype(np.float64)
+    pairs = (m * (n_candidates - m)).astype(np.float64)
+    ok = has & (n_candidates > m)
+    mean = lambda v: float(np.mean(v)) if len(v) else float('nan')
+    return RankingScore(hit_rate=mean((hits[has] > 0).astype(np.float64)), precision=mean(hits[has] / n_items),
+                        recall=mean(hits[has] / mh), ndcg=mean(dcg[has] / ideal[has]),
+                        mrr=mean(1.0 / (best[has] + 1.0)), auc=mean(1.0 - lost[ok] / pairs[ok]), n_users=int(has.sum()),
+                        n_targets=int(m.sum()))
 
 
 def _csr_piece(a, dtype, device):
@@ -246,6 +296,58 @@ class _RecsysDevice:
             check(f(ptr(code[s:e]), None, e - s, self.k, ptr(self.Dt), self.p, ex[0], ex[1], ex[2], ptr(item_bias), n_top,
                     ptr(items[s:e]), ptr(scores[s:e]), ptr(ws), ws.numel(), stream_ptr(dev)), 'modl_recsys_topn')
         return items
+
+    def ranks_rows_per_call(self, b, t_max):
+        """the most queries of one modl_recsys_ranks_* call whose workspace stays under TOPN_WORKSPACE_BYTES"""
+        rows = max(int(b), 1)
+        while rows > 1 and lib.modl_recsys_ranks_workspace(dtype_id(self.dtype), self.p, self.k, rows, t_max) > TOPN_WORKSPACE_BYTES:
+            rows = (rows + 1) // 2
+        return rows
+
+    def ranks(self, code, ex_indptr, ex_indices, ex_rows, item_bias, t_indptr, t_indices, rows_per_call=None):
+        """(ranks int32 (entries,), n_candidates int32 (users,)) on the host: for user u (row u of `code`; exclusions as in
+        topn) the rank of every entry of row u of the host CSR pattern t_indptr / t_indices among the items that are not
+        excluded (-1: not an item).  n_candidates is -1 for a user without targets: no query is run for it.  A row of more
+        than MAX_RANK_TARGETS entries becomes several queries with the same code and exclusion row and a finer row pointer
+        over the same t_indices: the ranks come back in entry order."""
+        dev = self.device
+        nu = code.shape[0]
+        t_indptr = np.ascontiguousarray(t_indptr, dtype=np.int64)
+        m = np.diff(t_indptr)
+        pieces = -(-m // MAX_RANK_TARGETS)                         # queries per user (none without targets)
+        q_user = np.repeat(np.arange(nu, dtype=np.int64), pieces)
+        nq = len(q_user)
+        ranks = np.zeros(int(t_indptr[-1]), dtype=np.int32)
+        n_cand = np.full(nu, -1, dtype=np.int32)
+        if nq == 0:
+            return ranks, n_cand
+        q_first = np.cumsum(pieces) - pieces                       # the first query of each user
+        q_ptr = t_indptr[q_user] + MAX_RANK_TARGETS * (np.arange(nq) - q_first[q_user])
+        q_ptr = np.concatenate([q_ptr, t_indptr[-1:]]).astype(np.int32)
+        q_len = np.diff(q_ptr)
+        t_max = int(q_len.max())
+        d_user = torch.from_numpy(q_user).to(dev)
+        d_ex_rows = None if ex_indptr is None else (d_user if ex_rows is None else ex_rows.index_select(0, d_user))
+        d_ptr = torch.from_numpy(q_ptr).to(dev)
+        d_tidx = _csr_piece(t_indices, np.int32, dev)
+        d_ranks = torch.zeros(max(len(ranks), 1), dtype=torch.int32, device=dev)
+        d_cand = torch.zeros(nq, dtype=torch.int32, device=dev)
+        if rows_per_call is None:
+            rows_per_call = self.ranks_rows_per_call(nq, t_max)
+        rows_per_call = max(int(rows_per_call), 1)
+        f = getattr(lib, 'modl_recsys_ranks_' + sfx(self.dtype))
+        nbytes = lib.modl_recsys_ranks_workspace(dtype_id(self.dtype), self.p, self.k, min(rows_per_call, nq), t_max)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        for s in range(0, nq, rows_per_call):
+            e = min(s + rows_per_call, nq)
+            ex = (None, None, None) if ex_indptr is None else (ptr(ex_indptr), ptr(ex_indices), ptr(d_ex_rows[s:e]))
+            # queries s .. e-1: the row pointers are absolute, so a view of them addresses the same t_indices and ranks
+            check(f(ptr(code), ptr(d_user[s:e]), e - s, self.k, ptr(self.Dt), self.p, ex[0], ex[1], ex[2], ptr(item_bias),
+                    ptr(d_ptr[s:]), ptr(d_tidx), t_max, ptr(d_ranks), ptr(d_cand[s:e]), ptr(ws), ws.numel(), stream_ptr(dev)),
+                  'modl_recsys_ranks')
+        ranks[:] = d_ranks.cpu().numpy()[:len(ranks)]
+        n_cand[q_user] = d_cand.cpu().numpy()
+        return ranks, n_cand
 
 
 class RecsysDictFact(BaseEstimator):
@@ -451,6 +553,62 @@ class RecsysDictFact(BaseEstimator):
         scores = np.full(items.shape, np.nan)
         scores[valid] = out
         return items, scores
+
+    def _ranks(self, n_rows, t_indptr, t_indices, X, exclude_seen, rows_per_call, what):
+        """(ranks, n_candidates) of _RecsysDevice.ranks for the target pattern t_indptr / t_indices over n_rows users: the
+        training users (X None) or the rows of X, folded in; the queries, exclusions and item bias are those of recommend"""
+        dev = self._dev
+        if X is None:
+            if n_rows != dev.n:
+                raise ValueError('RecsysDictFact.%s: X_test has %d rows, the training matrix %d (row u is training user u; '
+                                 'pass X= for other users)' % (what, n_rows, dev.n))
+            code, ex_indptr, ex_indices = dev.code, dev.indptr, dev.indices
+        else:
+            X, code, _ = self._fold_in(X)
+            if n_rows != X.shape[0]:
+                raise ValueError('RecsysDictFact.%s: X_test has %d rows, X %d' % (what, n_rows, X.shape[0]))
+            d = dev.device
+            ex_indptr, ex_indices = _csr_piece(X.indptr, np.int32, d), _csr_piece(X.indices, np.int32, d)
+        if not exclude_seen:
+            ex_indptr = ex_indices = None
+        bias = torch.from_numpy(np.ascontiguousarray(self.col_mean_, dtype=np.float64)).to(dev.device) if self.detrend else None
+        return dev.ranks(code, ex_indptr, ex_indices, None, bias, t_indptr, t_indices, rows_per_call)
+
+    def _test_pattern(self, X_test, what):
+        if not sp.issparse(X_test):
+            X_test = sp.csr_matrix(X_test)
+        X_test = X_test.tocsr()
+        if X_test.shape[1] != self._dev.p:
+            raise ValueError('RecsysDictFact.%s: X_test has %d columns, the fitted dictionary %d'
+                             % (what, X_test.shape[1], self._dev.p))
+        return X_test
+
+    def ranks(self, X_test, X=None, exclude_seen=True, rows_per_call=None):
+        """The rank of every entry of X_test among the items its user has not seen: an int64 array aligned with the entries of
+        X_test in CSR order.  Rank r means that r unseen items other than the entry's own are predicted above it (equal
+        predictions by ascending item id): with r < N the item is recommend(n_items=N)'s column r for that user, otherwise
+        it is not in that list.  The ranking is recommend's: by the uncropped prediction, formed with the same arithmetic.
+
+        X=None: row u of X_test belongs to training user u, whose seen items are the training ratings.  X given: one new user
+        per row of X and of X_test, coded on X's ratings (transform); the seen items are the entries of X.
+        exclude_seen=False ranks among all items.  An entry that is itself a seen item is ranked as if it were not."""
+        X_test = self._test_pattern(X_test, 'ranks')
+        r, _ = self._ranks(X_test.shape[0], X_test.indptr, X_test.indices, X, exclude_seen, rows_per_call, 'ranks')
+        return r.astype(np.int64)
+
+    def ranking_score(self, X_test, n_items=10, X=None, min_rating=None, exclude_seen=True):
+        """Ranking quality of recommend(n_items=n_items) on held-out ratings: a RankingScore (hit_rate, precision, recall,
+        ndcg, mrr, auc: means over the users with targets; n_users, n_targets), see ranking_metrics.  The targets are the
+        entries of X_test, with min_rating those rated min_rating or higher (the others stay ordinary unseen candidates).
+        X as in ranks."""
+        X_test = self._test_pattern(X_test, 'ranking_score')
+        indptr, indices = X_test.indptr, X_test.indices
+        if min_rating is not None:
+            keep = X_test.data >= min_rating
+            indptr = np.concatenate([[0], np.cumsum(keep)])[X_test.indptr]
+            indices = indices[keep]
+        r, n_cand = self._ranks(X_test.shape[0], indptr, indices, X, exclude_seen, None, 'ranking_score')
+        return ranking_metrics(r, indptr, n_cand, n_items)
 
     def score(self, X):
         """Root mean squared error of the prediction at the loci of X (recsys.py:247-252)"""
