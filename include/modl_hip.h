@@ -781,6 +781,53 @@ int modl_impute_f32(const float *d_code, int64_t n, int k, const float *d_Dt, in
 int modl_impute_f64(const double *d_code, int64_t n, int k, const double *d_Dt, int64_t p, const double *d_X, int64_t ldx,
                     const uint8_t *d_obs, int64_t ldo, double *d_out, int64_t ldout, void *stream);
 
+/* Sparse codes as CSR (csrc/sparse_codes.hip; no counterpart in the reference).  A dense chunk d_code[b][ld] (row-major,
+ * ld >= k; the padding columns k .. ld-1 are never read) is compacted in two calls.  An element is kept iff its bits with
+ * the sign cleared are non-zero: `value != 0`, scipy's csr_matrix(dense) rule - NaN, +-inf and denormals kept, -0.0
+ * dropped - decided on the bits, whatever the floating-point mode does with denormals.  No atomics: the result is a pure
+ * function of the chunk.  All of these are asynchronous on `stream`.
+ * modl_csr_compact_workspace(b): bytes of scratch of modl_csr_count_* for b rows (0 for b < 0). */
+size_t modl_csr_compact_workspace(int64_t b);
+/* Count + scan: d_indptr[0] = base, d_indptr[i + 1] = base + the number of kept elements of rows 0 .. i (b + 1 int64;
+ * base: the non-zeros of the chunks before this one).  Four launches: a count per row (one wavefront per row), sums of
+ * tiles of 1024 rows, a one-workgroup scan of the tile sums, a scan of every tile from its offset.  MODL_EINVAL before any
+ * device work: a NULL d_code or d_indptr, b < 0 or b > 2^31 - 1, k < 1 or k > 2^31 - 1, ld < k, base < 0.  b == 0 does
+ * nothing (nothing is written).  d_ws NULL or ws_bytes below modl_csr_compact_workspace(b): MODL_ENOMEM; no device:
+ * MODL_ENOGPU. */
+int modl_csr_count_f32(const float *d_code, int64_t ld, int64_t b, int64_t k, int64_t base, int64_t *d_indptr, void *d_ws,
+                       size_t ws_bytes, void *stream);
+int modl_csr_count_f64(const double *d_code, int64_t ld, int64_t b, int64_t k, int64_t base, int64_t *d_indptr, void *d_ws,
+                       size_t ws_bytes, void *stream);
+/* Fill: row i's kept elements go to the positions d_indptr[i] - base ... of d_indices (int32, the column) and d_data (the
+ * value, bit for bit), in ascending column order.  d_indptr, base: what modl_csr_count_* made of the same chunk; nnz: the
+ * length of d_indices and d_data, at least d_indptr[b] - base (a position outside [0, nnz) is never written).  One launch,
+ * one wavefront per row, no scratch.  MODL_EINVAL before any device work: the cases of modl_csr_count_*, a NULL
+ * d_indices or d_data, nnz < 0.  b == 0 or nnz == 0 does nothing.  No device: MODL_ENOGPU. */
+int modl_csr_fill_f32(const float *d_code, int64_t ld, int64_t b, int64_t k, int64_t base, const int64_t *d_indptr,
+                      int64_t nnz, int32_t *d_indices, float *d_data, void *stream);
+int modl_csr_fill_f64(const double *d_code, int64_t ld, int64_t b, int64_t k, int64_t base, const int64_t *d_indptr,
+                      int64_t nnz, int32_t *d_indices, double *d_data, void *stream);
+/* modl_csr_decode_workspace(dtype, k, p): bytes of scratch of modl_csr_decode_* - the atom-major copy of the dictionary,
+ * k * p elements (0 for bad arguments). */
+size_t modl_csr_decode_workspace(int dtype, int64_t k, int64_t p);
+/* CSR codes times the dictionary: d_out[i][e] = sum_j d_data[j] * d_Dt[e][d_indices[j]] over j = d_indptr[i] ..
+ * d_indptr[i + 1] - 1 in stored order, one fma chain in the dtype per (i, e), for n rows and e < p (d_out[n][ldo], its
+ * padding columns untouched).  Unsorted and repeated indices are legal, repeats add up; an empty row gives zeros.  The
+ * order of a row's sum depends on that row alone: a row decodes to the same bits in any batch.  d_Dt[p][k] is first
+ * transposed into d_ws (an atom's features side by side), then one launch: a wavefront per row and tile of 256 features.
+ * Nothing out of range is dereferenced: an entry whose index is outside [0, k) contributes nothing, a row whose d_indptr
+ * pair is negative, decreasing or beyond nnz (the length of d_indices and d_data) contributes nothing, and either sets
+ * *d_status (int32, may be NULL; zeroed by the call) to 1.  MODL_EINVAL before any device work: a NULL pointer (d_status
+ * and d_ws apart), nnz < 0, n < 0, k < 1 or k > 2^31 - 1, p < 1 or p > 32 * 65535 (the transpose's grid), ldo < p.
+ * n == 0 does nothing.  d_ws NULL or ws_bytes below modl_csr_decode_workspace(...): MODL_ENOMEM; no device:
+ * MODL_ENOGPU. */
+int modl_csr_decode_f32(const int64_t *d_indptr, const int32_t *d_indices, const float *d_data, int64_t nnz, int64_t n,
+                        int64_t k, const float *d_Dt, int64_t p, float *d_out, int64_t ldo, int32_t *d_status, void *d_ws,
+                        size_t ws_bytes, void *stream);
+int modl_csr_decode_f64(const int64_t *d_indptr, const int32_t *d_indices, const double *d_data, int64_t nnz, int64_t n,
+                        int64_t k, const double *d_Dt, int64_t p, double *d_out, int64_t ldo, int32_t *d_status, void *d_ws,
+                        size_t ws_bytes, void *stream);
+
 /* Amari discrepancy between dictionaries (modl/decomposition/stability.py:7-31: amari_discrepency,
  * mean_amari_discrepency).  For the n dictionaries h_d_dicts[i] (device, row-major k_i x p, atoms in rows), every pair
  * a < b in the reference's generator order (a outer, b inner) gets

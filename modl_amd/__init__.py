@@ -1,9 +1,9 @@
 """modl_amd — MI355X-native implementation of MODL's SOMF hot path
 (DictFact.partial_fit: code solve, surrogate statistics, block-coordinate
 dictionary update) behind the reference's estimator API."""
-from .dict_fact import DictFact, Coder  # noqa: F401
+from .dict_fact import DictFact, Coder, SparseCodes  # noqa: F401
 from .stability import amari_discrepency, mean_amari_discrepency  # noqa: F401
 from .image import grid_origins, grid_patches, reconstruct_from_patches  # noqa: F401
 
-__all__ = ['DictFact', 'Coder', 'amari_discrepency', 'mean_amari_discrepency', 'grid_origins', 'grid_patches',
+__all__ = ['DictFact', 'Coder', 'SparseCodes', 'amari_discrepency', 'mean_amari_discrepency', 'grid_origins', 'grid_patches',
            'reconstruct_from_patches']

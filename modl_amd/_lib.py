@@ -179,6 +179,11 @@ def bind(lib):
              _vp, _vp)
         _sig('modl_impute_' + _sfx, C.c_int, _vp, _i64, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp)
         _sig('modl_amari_' + _sfx, C.c_int, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _P(C.c_int))
+        _sig('modl_csr_count_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp)
+        _sig('modl_csr_fill_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp)
+        _sig('modl_csr_decode_' + _sfx, C.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp)
+    _sig('modl_csr_compact_workspace', _sz, _i64)
+    _sig('modl_csr_decode_workspace', _sz, C.c_int, _i64, _i64)
     _sig('modl_image_fill', C.c_int, _i64, _i64, _i64, _vp)
     _sig('modl_image_grid_shape', C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _P(_i64), _P(_i64))
     _sig('modl_objective_workspace', _sz, C.c_int, _i64, _i64)

@@ -574,6 +574,56 @@ class HipBackend:
                     ptr(out), self.p, stream_ptr(self.device)), 'modl_image_decode')
         return out
 
+    def compact(self, code, base=0):
+        """A dense chunk of codes (b, k) as CSR on the device (modl_csr_count_* + modl_csr_fill_*, csrc/sparse_codes.hip):
+        the tensors indptr (b + 1,) int64 starting at `base` (the non-zeros of the chunks before this one), indices
+        (nnz,) int32 in ascending order within a row and data (nnz,) of the chunk's dtype, bit for bit.  Kept: value != 0.
+        The chunk's total is read back between the two calls to size the outputs: one synchronise per chunk."""
+        b, k = code.shape
+        dev, sx = self.device, 'f32' if code.dtype == torch.float32 else 'f64'
+        if code.stride(1) != 1 and b:
+            code = code.contiguous()
+        indptr = torch.full((b + 1,), base, dtype=torch.int64, device=dev)
+        total = 0
+        if b:
+            nbytes = lib.modl_csr_compact_workspace(b)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                check(getattr(lib, 'modl_csr_count_' + sx)(ptr(code), code.stride(0), b, k, base, ptr(indptr), ptr(ws),
+                                                           nbytes, stream_ptr(dev)), 'modl_csr_count')
+            total = int(indptr[b].item()) - base
+        indices = torch.empty(total, dtype=torch.int32, device=dev)
+        data = torch.empty(total, dtype=code.dtype, device=dev)
+        if total:
+            with torch.cuda.device(dev):
+                check(getattr(lib, 'modl_csr_fill_' + sx)(ptr(code), code.stride(0), b, k, base, ptr(indptr), total,
+                                                          ptr(indices), ptr(data), stream_ptr(dev)), 'modl_csr_fill')
+        return indptr, indices, data
+
+    def decode_csr(self, indptr, indices, data, n):
+        """CSR codes times the dictionary as a (n, p) device tensor (modl_csr_decode_*): indptr (n + 1,) int64, indices
+        int32, data in the dictionary's dtype, all on the device.  Repeated indices add up.  ValueError when the kernel
+        met an index outside the dictionary or a row whose indptr pair is not inside the arrays (its status word, read
+        back after the launch; such entries contribute nothing)."""
+        dev = self.device
+        out = torch.empty((n, self.p), dtype=torch_dtype(self.dtype), device=dev)
+        if n == 0:
+            return out
+        nnz = data.shape[0]
+        if nnz == 0:                                 # (an empty tensor has no address; the kernel still checks indptr)
+            indices, data = indices.new_zeros(1), data.new_zeros(1)
+        nbytes = lib.modl_csr_decode_workspace(dtype_id(self.dtype), self.k, self.p)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(getattr(lib, 'modl_csr_decode_' + sfx(self.dtype))(
+                ptr(indptr), ptr(indices), ptr(data), nnz, n, self.k, ptr(self.Dt), self.p, ptr(out), self.p,
+                ptr(status), ptr(ws), nbytes, stream_ptr(dev)), 'modl_csr_decode')
+        if int(status.item()):
+            raise ValueError('sparse codes are corrupt: an index outside [0, %d) or an indptr pair that is decreasing or '
+                             'reaches beyond the %d stored entries' % (self.k, nnz))
+        return out
+
     def objective(self, Xh, code):
         """[sum (X - code D)^2, sum |code|, sum code^2] of device-resident X and codes (dict_fact.py:108-112)."""
         n, p = Xh.shape
@@ -917,7 +967,45 @@ class CodingMixin(TransformerMixin):
             return be.omp(Xh, omp[0], omp[1], G, obs=obs, kw=self._plan_kwargs(4096))[0]
         return be.transform_masked(Xh, obs, self._plan_kwargs(4096), G)
 
-    def transform(self, X, mask=None, algorithm='enet', n_nonzero_coefs=None, residual_tol=None):
+    def _device_codes(self, X, mask, omp):
+        """the dense codes of `transform(X, mask, ...)` as a (n, k) device tensor, by the same calls"""
+        if mask is None:
+            Xh, G = self._stage_rows(X)
+            if omp is not None:
+                return self._backend.omp(Xh, omp[0], omp[1], G, kw=self._plan_kwargs(4096))[0]
+            return self._backend.transform(Xh, self._plan_kwargs(4096), G, to_host=False)
+        Xh, obs, _, G = self._stage_masked(X, mask)
+        return self._masked_codes(Xh, obs, G, omp)
+
+    def _transform_sparse(self, X, mask, omp, rows_per_chunk):
+        """`transform(..., sparse=True)`: slices of rows_per_chunk rows are coded as `transform` codes them, into a dense
+        (rows, k) buffer that is compacted to CSR on the device and dropped before the next slice is coded."""
+        be = self._backend
+        on_host = not isinstance(X, torch.Tensor)
+        if on_host:
+            X = np.asarray(X)
+        if mask is not None and not isinstance(mask, torch.Tensor):
+            mask = np.asarray(mask)
+        n = int(X.shape[0])
+        parts, base = [], 0
+        for c0 in range(0, max(n, 1), rows_per_chunk):
+            sl = slice(c0, c0 + rows_per_chunk)
+            code = self._device_codes(X[sl], None if mask is None else mask[sl], omp)
+            indptr, indices, data = be.compact(code, base)
+            del code
+            base += indices.shape[0]
+            if c0:
+                indptr = indptr[1:]
+            parts.append(tuple(t.cpu().numpy() for t in (indptr, indices, data)) if on_host else (indptr, indices, data))
+        cat = np.concatenate if on_host else torch.cat
+        indptr, indices, data = (cat([part[i] for part in parts]) for i in range(3))
+        if not on_host:
+            return SparseCodes(indptr, indices, data, (n, be.k))
+        import scipy.sparse as sp
+        return sp.csr_matrix((data, indices, indptr), shape=(n, be.k))
+
+    def transform(self, X, mask=None, algorithm='enet', n_nonzero_coefs=None, residual_tol=None, sparse=False,
+                  rows_per_chunk=None):
         """Codes of the rows of X on the dictionary (dict_fact.py:47-92).  With `mask` (a boolean array or tensor of X's
         shape, True = observed) every row is coded on its observed entries only, by the estimator of the SOMF step
         itself with the row's own subset (dict_fact.py:594-604: Dx = r X_S D_S^T, G = r D_S D_S^T, r = p / |S|): rows
@@ -929,8 +1017,27 @@ class CodingMixin(TransformerMixin):
         64) and, with `residual_tol` (the largest squared residual norm of a row, the `tol` of scikit-learn's
         orthogonal_mp_gram; the name `tol` is the coordinate-descent tolerance here), only until the row is explained
         that well, `n_nonzero_coefs` still capping the support (default 64).  With a mask the residual is the estimate
-        r |x_S - code D_S|^2."""
+        r |x_S - code D_S|^2.
+
+        sparse=True returns the codes as CSR instead of a dense (n, n_components) array: host input gives a canonical
+        scipy.sparse.csr_matrix in the dictionary's dtype, a CUDA tensor a `SparseCodes` of device tensors.  The rows are
+        coded `rows_per_chunk` at a time (default 4096) into a dense buffer of that many rows, which is compacted on the
+        device (kept: value != 0) before the next slice is coded, so device memory holds one slice's dense codes and the
+        non-zeros, never (n, n_components).  Slice c of the result is csr_matrix(transform(X[c], mask[c], ...)) of the
+        dense call on those rows, bit for bit; without a mask and with rows_per_chunk a multiple of 4096 the whole
+        result is csr_matrix(transform(X, ...)).  `inverse_transform` takes either form back."""
         omp = self._omp_params(algorithm, n_nonzero_coefs, residual_tol)
+        if rows_per_chunk is not None:
+            if not sparse:
+                raise ValueError('rows_per_chunk belongs to sparse=True')
+            if rows_per_chunk != int(rows_per_chunk) or rows_per_chunk < 1:
+                raise ValueError('rows_per_chunk must be an integer >= 1, got %r' % (rows_per_chunk,))
+        if sparse:
+            if mask is not None:
+                self._check_masked_args(X, mask)
+            elif len(np.shape(X)) != 2:
+                raise ValueError('X of shape %s is not (n_samples, n_features)' % (tuple(np.shape(X)),))
+            return self._transform_sparse(X, mask, omp, 4096 if rows_per_chunk is None else int(rows_per_chunk))
         if mask is None and omp is not None:
             Xh, G = self._stage_rows(X)
             code = self._backend.omp(Xh, omp[0], omp[1], G, kw=self._plan_kwargs(4096))[0]
@@ -944,7 +1051,18 @@ class CodingMixin(TransformerMixin):
 
     def inverse_transform(self, code):
         """code @ components_ for codes of shape (n, n_components), on the device (the reference has no counterpart);
-        a numpy array gives a numpy array, a CUDA tensor a CUDA tensor."""
+        a numpy array gives a numpy array, a CUDA tensor a CUDA tensor.  Sparse codes stay sparse on the way in: any
+        scipy sparse matrix (taken as CSR; only indptr, indices and data are uploaded) gives a numpy array, a
+        `SparseCodes` a CUDA tensor (modl_csr_decode_*); repeated entries add up.  ValueError for a shape that does not
+        match the dictionary and for an index outside it."""
+        sparse = _csr_parts(code, self.n_components)
+        if sparse is not None:
+            check_is_fitted(self, 'components_')
+            be = self._backend
+            td = torch_dtype(be.dtype)
+            indptr, indices, data = (to_device(t, be.device).to(d) for t, d in zip(sparse, (torch.int64, torch.int32, td)))
+            out = be.decode_csr(indptr, indices, data, code.shape[0])
+            return out if isinstance(code, SparseCodes) else out.cpu().numpy()
         check_is_fitted(self, 'components_')
         be = self._backend
         on_host = not isinstance(code, torch.Tensor)
@@ -1021,6 +1139,41 @@ class CodingMixin(TransformerMixin):
 
 
 HeldOutError = namedtuple('HeldOutError', ['rmse', 'rmse_coded', 'n_held_out', 'n_coded'])
+
+
+class SparseCodes(namedtuple('SparseCodes', ['indptr', 'indices', 'data', 'shape'])):
+    """Codes as CSR on the device, what `transform(X, sparse=True)` returns for a CUDA tensor: indptr (n + 1,) int64,
+    indices (nnz,) int32, data (nnz,) in the dictionary's dtype, shape = (n, n_components)."""
+    __slots__ = ()
+
+    def to_scipy(self):
+        """the same matrix as a scipy.sparse.csr_matrix on the host"""
+        import scipy.sparse as sp
+        return sp.csr_matrix(tuple(t.cpu().numpy() for t in (self.data, self.indices, self.indptr)),
+                             shape=tuple(self.shape))
+
+
+def _csr_parts(code, k):
+    """(indptr, indices, data) of sparse codes - a scipy sparse matrix (numpy arrays) or a SparseCodes (device tensors) -
+    or None for dense codes; ValueError for a shape that does not fit k components or a structure that is not CSR's,
+    and, for host input, for an index outside [0, k)"""
+    if isinstance(code, SparseCodes):
+        indptr, indices, data = code.indptr, code.indices, code.data
+        shape = tuple(code.shape)
+    elif hasattr(code, 'tocsr') and hasattr(code, 'nnz'):
+        code = code.tocsr()
+        indptr, indices, data = code.indptr, code.indices, code.data
+        shape = tuple(code.shape)
+    else:
+        return None
+    if len(shape) != 2 or shape[1] != k:
+        raise ValueError('code has shape %s, the dictionary has %d components' % (shape, k))
+    if indptr.ndim != 1 or indptr.shape[0] != shape[0] + 1 or indices.ndim != 1 or indices.shape != data.shape:
+        raise ValueError('sparse codes need indptr of n + 1 = %d entries and indices and data of one length, got %s, %s '
+                         'and %s' % (shape[0] + 1, tuple(indptr.shape), tuple(indices.shape), tuple(data.shape)))
+    if isinstance(indices, np.ndarray) and indices.shape[0] and (indices.min() < 0 or indices.max() >= k):
+        raise ValueError('sparse codes hold an index outside [0, %d)' % k)
+    return indptr, indices, data
 
 
 def _held_out_set(held_out, shape, random_state):

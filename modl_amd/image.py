@@ -495,8 +495,9 @@ class ImageDictFact(BaseEstimator):
         s = ImageDictFact.settings[self.setting]
         return _flatten_patches(np.asarray(patches), with_mean=s['with_mean'], with_std=s['with_std'], copy=True)
 
-    def transform(self, patches):
-        return self.dict_fact_.transform(self._prep(patches))
+    def transform(self, patches, sparse=False):
+        """codes of the patches; sparse=True: as CSR (`DictFact.transform`)"""
+        return self.dict_fact_.transform(self._prep(patches), sparse=sparse)
 
     def score(self, patches):
         return self.dict_fact_.score(self._prep(patches))
