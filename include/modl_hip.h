@@ -828,6 +828,32 @@ int modl_csr_decode_f64(const int64_t *d_indptr, const int32_t *d_indices, const
                         int64_t k, const double *d_Dt, int64_t p, double *d_out, int64_t ldo, int32_t *d_status, void *d_ws,
                         size_t ws_bytes, void *stream);
 
+/* Signal cleaning of a record (csrc/clean.hip; the arithmetic of nilearn.signal.clean that the
+ * reference's masker applies to every record, modl/decomposition/fmri.py:525-526).  d_X[T][ldx] holds T time points of V
+ * voxels (ldx >= V, the padding is never read); every column x is treated on its own:
+ *   r = x - Q (Q^T x),    out = standardize ? r sqrt(T) / |r| : r
+ * with d_Q[T][q] (f64, row-major) a basis with orthonormal columns that the caller builds (modl_amd/signal.py:
+ * cleaning_basis - constant, linear ramp, confounds).  With standardize a column is FLAT when |r|^2 <= (q T eps64)^2 |x|^2
+ * (the worst-case f64 rounding of the projection) and comes out as exact zeros; without it nothing is zeroed.  The
+ * coefficients Q^T x, |x|^2 and |r|^2 are summed in f64 for both dtypes, the residual is formed in f64 and rounded once on
+ * store.  The order of every sum depends on T alone - not on V, on the column's place in the call, on ldx / ldo or on
+ * d_dst_row - so a column has the same bits wherever it stands and from run to run; a column that holds a NaN or Inf (|x|^2 not
+ * finite in f64) comes out as NaN throughout and touches no other column.
+ * d_dst_row (int64[T], may be NULL): cleaned row t is written to row d_dst_row[t] of d_out[T][ldo]; it has to be a
+ * permutation of 0 .. T-1, which the CALLER checks (an entry outside 0 .. T-1 is skipped on the device, nothing more).
+ * d_out == d_X (in place) is legal with d_dst_row == NULL and ldo == ldx only; any other overlap of the address ranges
+ * of d_X[T][ldx] and d_out[T][ldo] (d_out shifted by rows, a permutation into the input) is refused.  Asynchronous on `stream`: a copy of the
+ * basis into d_ws and one launch, no atomics.
+ * MODL_EINVAL before any device work: a NULL d_X / d_Q / d_out, T < 1, V < 1, q outside 1 .. min(T, 64), ldx < V,
+ * ldo < V, the in-place / overlap rule.  d_ws NULL or ws_bytes below modl_clean_workspace(...): MODL_ENOMEM; no device: MODL_ENOGPU.
+ * modl_clean_max_regressors(): 64.  modl_clean_workspace: bytes of scratch (0 for bad arguments). */
+int modl_clean_max_regressors(void);
+size_t modl_clean_workspace(int dtype, int64_t T, int64_t V, int q);
+int modl_clean_f32(const float *d_X, int64_t ldx, int64_t T, int64_t V, const double *d_Q, int q, int standardize,
+                   const int64_t *d_dst_row, float *d_out, int64_t ldo, void *d_ws, size_t ws_bytes, void *stream);
+int modl_clean_f64(const double *d_X, int64_t ldx, int64_t T, int64_t V, const double *d_Q, int q, int standardize,
+                   const int64_t *d_dst_row, double *d_out, int64_t ldo, void *d_ws, size_t ws_bytes, void *stream);
+
 /* Amari discrepancy between dictionaries (modl/decomposition/stability.py:7-31: amari_discrepency,
  * mean_amari_discrepency).  For the n dictionaries h_d_dicts[i] (device, row-major k_i x p, atoms in rows), every pair
  * a < b in the reference's generator order (a outer, b inner) gets

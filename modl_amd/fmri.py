@@ -9,7 +9,12 @@ The reference's loop rebinds `method` to the dict of aggregation modes (fmri.py:
 method NAME - the 'gram' switch to G_agg='full' / Dx_agg='average' at epoch 5 (:508), the shrinking reduction of
 'reducing ratio' (:511-513) and the per-record sample_indices of 'average' / 'gram' (:535-539) - never fire.  The
 default here reproduces that EFFECTIVE behaviour (same results as the reference on the same inputs, pinned by
-tests/golden/fmri.npz); `intended_schedules=True` runs what the code was written to do."""
+tests/golden/fmri.npz); `intended_schedules=True` runs what the code was written to do.
+
+Signal cleaning.  In the reference every record passes through the masker's nilearn.signal.clean before it is fitted or
+coded (fmri.py:525-526, :577-585), steered by `standardize`, `detrend` and per-record `confounds`.  That arithmetic -
+unlike the masking - is not IO: it runs here on the device (modl_amd/signal.py) on the record
+that `_RecordStager` has already uploaded, with the epoch's row permutation folded into the cleaning's write."""
 import time
 from concurrent.futures import ThreadPoolExecutor
 from math import sqrt
@@ -22,6 +27,7 @@ from sklearn.utils import check_random_state
 
 from .device import gather_rows
 from .dict_fact import DictFact, Coder
+from .signal import clean, clean_host, cleaning_basis
 
 METHODS = {'masked': {'G_agg': 'masked', 'Dx_agg': 'masked'},           # fmri.py:440-445
            'dictionary only': {'G_agg': 'full', 'Dx_agg': 'full'},
@@ -34,6 +40,29 @@ def _load(record, mmap=False):
     if isinstance(record, str):
         return np.load(record, mmap_mode='r' if mmap else None)
     return record
+
+
+def _check_confounds(confounds, records):
+    """one entry (None, array or path) per record"""
+    if confounds is None:
+        return [None] * len(records)
+    if isinstance(confounds, (str, np.ndarray)) or len(confounds) != len(records):
+        raise ValueError('confounds must be a list with one entry (None, array or path) per record')
+    return list(confounds)
+
+
+def _clean_staged(data, detrend, standardize, confounds, permutation=None, basis=None):
+    """A staged record (a CUDA tensor, or a numpy array on a backend without a GPU) cleaned where it is; with
+    `permutation` the rows come out in that order.  `basis`: the record's cleaning_basis, when the caller keeps it.
+    None when there is nothing to clean."""
+    if not (detrend or standardize or confounds is not None):
+        return None
+    if isinstance(data, torch.Tensor) and data.is_cuda:
+        return clean(data, detrend, standardize, confounds, permutation, basis=basis)
+    was_tensor = isinstance(data, torch.Tensor)
+    out = clean_host(data.numpy() if was_tensor else np.asarray(data), detrend, standardize, confounds, permutation,
+                     basis=basis)
+    return torch.from_numpy(out) if was_tensor else out
 
 
 def _flip(components):
@@ -93,15 +122,24 @@ class _RecordStager:
 
 
 class fMRIDictFact(BaseEstimator):
-    """Constructor arguments follow fmri.py:273-291 (masking arguments dropped)."""
+    """Constructor arguments follow fmri.py:273-291 (masking arguments dropped).
+
+    `standardize`, `detrend`: clean every record before it is fitted, coded or scored (modl_amd.signal.clean: z-score
+    every voxel's series / remove its mean and linear trend), together with the per-record `confounds` that fit,
+    transform and score take.  The reference defaults to True / True (fmri.py:281-296); the defaults here are
+    False / False, so that an estimator built without these arguments keeps computing what it computed before they
+    existed (records handed over as they are, e.g. cleaned by the caller) - pass True / True for the reference's
+    pipeline."""
 
     _dict_fact_class = DictFact
     _coder_class = Coder
 
     def __init__(self, method='masked', step_size=1, n_components=20, n_epochs=1, alpha=0.1, dict_init=None,
                  random_state=None, batch_size=20, reduction=1, learning_rate=1, positive=False, verbose=0,
-                 callback=None, n_jobs=1, intended_schedules=False):
+                 callback=None, n_jobs=1, intended_schedules=False, standardize=False, detrend=False):
         self.intended_schedules = intended_schedules
+        self.standardize = standardize
+        self.detrend = detrend
         self.method = method
         self.step_size = step_size
         self.n_components = n_components
@@ -117,10 +155,14 @@ class fMRIDictFact(BaseEstimator):
         self.callback = callback
         self.n_jobs = n_jobs
 
-    def fit(self, records, y=None):
-        """records: list of 2-D arrays / .npy paths.  fmri.py:423-546."""
+    def fit(self, records, y=None, confounds=None):
+        """records: list of 2-D arrays / .npy paths.  fmri.py:423-546.  confounds: None, or a list with one entry per
+        record (None, a (time points, c) array, or the path of a .npy / .csv file).  With `standardize`, `detrend` or
+        confounds the staged record is cleaned on the device and its rows are written in the epoch's permuted order by
+        the same launch; the draws of `random_state` are those of a fit without cleaning."""
         if records is None:
             raise ValueError('records is None, use Coder instead')
+        confounds = _check_confounds(confounds, records)
         n_components = self.n_components
         dict_init = self.dict_init
         if dict_init is not None:                                    # fmri.py:415-416, 468-469
@@ -139,6 +181,10 @@ class fMRIDictFact(BaseEstimator):
             arr = _load(rec, mmap=True)
             lengths.append(arr.shape[0])
             dtype, n_voxels = arr.dtype, arr.shape[1]
+        # the basis of a record depends on its length, the flags and its confounds alone: built (confound files read, the
+        # host QR run) once per record here, not once per record and epoch inside the timed loop
+        bases = [cleaning_basis(n, self.detrend, self.standardize, c) if (self.detrend or self.standardize or c is not None)
+                 else None for n, c in zip(lengths, confounds)]
         indices_list = np.zeros(n_records + 1, dtype='int')
         indices_list[1:] = np.cumsum(lengths)
         n_samples = int(indices_list[-1]) + 1                        # fmri.py:476 (the + 1 is the reference's)
@@ -182,7 +228,11 @@ class fMRIDictFact(BaseEstimator):
                         sample_indices = np.arange(indices_list[record], indices_list[record + 1])[permutation]
                     else:
                         sample_indices = None
-                    dict_fact.partial_fit(stager.rows(data, permutation), sample_indices=sample_indices)
+                    rows = _clean_staged(data, self.detrend, self.standardize, confounds[record], permutation,
+                                         basis=bases[record])
+                    if rows is None:
+                        rows = stager.rows(data, permutation)
+                    dict_fact.partial_fit(rows, sample_indices=sample_indices)
                     current_n_records += 1
                     self.cpu_time_ += time.perf_counter() - t0
         stager.close()
@@ -191,28 +241,51 @@ class fMRIDictFact(BaseEstimator):
         self.coder_ = self._coder_class(dictionary=self.components_, code_alpha=self.alpha, code_l1_ratio=0).fit()
         return self
 
-    def transform(self, records):
-        """Loadings of each record on the learned maps (fmri.py:131-164)."""
-        return [self.coder_.transform(np.asarray(_load(r))) for r in records]
+    def _cleaned(self, records, confounds):
+        return _cleaned_records(self.coder_, records, confounds, self.detrend, self.standardize)
 
-    def score(self, records):
-        """Length-weighted mean objective (fmri.py:95-129)."""
-        arrays = [np.asarray(_load(r)) for r in records]
+    def transform(self, records, confounds=None):
+        """Loadings of each record on the learned maps (fmri.py:131-164); the records are cleaned first with the
+        estimator's `standardize` / `detrend` and their `confounds` (one entry per record)."""
+        return [self.coder_.transform(a) for a in self._cleaned(records, confounds)]
+
+    def score(self, records, confounds=None):
+        """Length-weighted mean objective (fmri.py:95-129), of the records cleaned as in `transform`."""
+        arrays = self._cleaned(records, confounds)
         scores = np.array([self.coder_.score(a) for a in arrays])
         lens = np.array([a.shape[0] for a in arrays])
         return np.sum(scores * lens) / np.sum(lens)
+
+
+def _cleaned_records(coder, records, confounds, detrend, standardize):
+    """the records as the coder takes them: untouched host arrays when nothing is cleaned, otherwise staged on the coder's
+    device in its dtype and cleaned there"""
+    confounds = _check_confounds(confounds, records)
+    out = []
+    for rec, conf in zip(records, confounds):
+        arr = np.asarray(_load(rec))
+        if detrend or standardize or conf is not None:
+            be = coder._backend
+            arr = _clean_staged(be.stage_X(np.ascontiguousarray(arr, dtype=be.dtype)), detrend, standardize, conf)
+        out.append(arr)
+    return out
 
 
 class fMRICoder(BaseEstimator):
     """Loadings / objective of raw records on a FIXED set of maps: the reference's fMRICoder (fmri.py:371-402 over
     fMRICoderMixin.fit / score / transform, :76-164) on masked 2-D records (arrays or .npy paths, the MultiRawMasker
     contract of input_data/fmri/unmask.py:37-55) - the masking arguments are dropped as for fMRIDictFact, the rest of
-    the constructor is the reference's.  `dictionary`: (n_components, n_voxels) array, or a .npy path."""
+    the constructor is the reference's.  `dictionary`: (n_components, n_voxels) array, or a .npy path.
+    `standardize`, `detrend` (False / False as in the reference, fmri.py:375-376) and the `confounds` of transform / score:
+    the records are cleaned on the device before they are coded (modl_amd.signal.clean)."""
 
     _coder_class = Coder
 
-    def __init__(self, dictionary, alpha=0.1, transform_batch_size=None, n_components=None, n_jobs=1, verbose=0):
+    def __init__(self, dictionary, alpha=0.1, transform_batch_size=None, n_components=None, n_jobs=1, verbose=0,
+                 standardize=False, detrend=False):
         self.dictionary = dictionary
+        self.standardize = standardize
+        self.detrend = detrend
         self.alpha = alpha
         self.transform_batch_size = transform_batch_size
         self.n_components = n_components
@@ -238,30 +311,43 @@ class fMRICoder(BaseEstimator):
             records = [records]                                      # one record (fmri.py:117, :150)
         return records
 
-    def _rows(self, record):
+    def _rows(self, record, confounds=None):
         X = np.asarray(_load(record))
         if X.shape[1] != self.components_.shape[1]:
             raise ValueError('record has %d voxels, the maps have %d' % (X.shape[1], self.components_.shape[1]))
-        return np.ascontiguousarray(X, dtype=self.components_.dtype)
+        X = np.ascontiguousarray(X, dtype=self.components_.dtype)
+        if self.detrend or self.standardize or confounds is not None:
+            X = _clean_staged(self.coder_._backend.stage_X(X), self.detrend, self.standardize, confounds)
+        return X
 
-    def transform(self, records):
+    def _confounds(self, confounds, records):
+        if len(records) == 1 and confounds is not None and (isinstance(confounds, str) or (
+                isinstance(confounds, np.ndarray) and confounds.ndim == 2)):
+            confounds = [confounds]                                  # one record, its confounds as they are
+        return _check_confounds(confounds, records)
+
+    def transform(self, records, confounds=None):
         """Loadings of each record, one (n_samples, n_components) array per record (fmri.py:131-164).  A record is
-        coded in slices of transform_batch_size rows when that is set (the codes of a row do not depend on the others)."""
+        coded in slices of transform_batch_size rows when that is set (the codes of a row do not depend on the others).
+        `confounds`: one entry per record, regressed out of it (with `standardize` / `detrend`) before it is coded."""
         if not hasattr(self, 'coder_'):
             raise ValueError('fMRICoder is not fitted: call fit() first')
         out = []
-        for rec in self._records(records):
-            X = self._rows(rec)
+        records = self._records(records)
+        for rec, conf in zip(records, self._confounds(confounds, records)):
+            X = self._rows(rec, conf)
             step = self.transform_batch_size or X.shape[0] or 1
             parts = [self.coder_.transform(X[a:a + step]) for a in range(0, X.shape[0], step)]
             out.append(np.concatenate(parts) if parts else np.zeros((0, self.components_.shape[0]), dtype=X.dtype))
         return out
 
-    def score(self, records):
-        """Length-weighted mean of the objective over the records (fmri.py:95-129); lower is a better fit."""
+    def score(self, records, confounds=None):
+        """Length-weighted mean of the objective over the records (fmri.py:95-129), cleaned as in `transform`; lower is a
+        better fit."""
         if not hasattr(self, 'coder_'):
             raise ValueError('fMRICoder is not fitted: call fit() first')
-        arrays = [self._rows(r) for r in self._records(records)]
+        records = self._records(records)
+        arrays = [self._rows(r, c) for r, c in zip(records, self._confounds(confounds, records))]
         scores = np.array([self.coder_.score(a) for a in arrays])
         lens = np.array([a.shape[0] for a in arrays])
         return float(np.sum(scores * lens) / np.sum(lens))
@@ -274,14 +360,16 @@ class rfMRIDictionaryScorer:
     every later call scores them where they are - codes from the current dictionary (`DictFact.score`: transform +
     the three sums of the objective on the device), so neither the test set nor the dictionary crosses the host
     link again; three doubles per record come back.  Signature of the reference: `scorer(masker, dict_fact,
-    cpu_time, io_time)`; the first argument (the masker there, the fMRIDictFact here) is not used for raw records.
+    cpu_time, io_time)`; the first argument (the masker there, the fMRIDictFact here) plays the masker's part: its
+    `standardize` / `detrend` and `test_confounds` (one entry per test record) say how the test records are cleaned -
+    once, on the device, when they are staged (modl_amd.signal.clean).
     `artifact_dir`: `info.pkl` as in the reference (:621-625) and the flipped maps as `components_<n_iter>.npy`
     (the reference writes a NIfTI image through the masker, which is out of scope)."""
 
     def __init__(self, test_records, test_confounds=None, info=None, artifact_dir=None):
         self.start_time = time.perf_counter()
         self.test_records = test_records
-        self.test_confounds = test_confounds             # kept for signature compatibility; raw records carry none
+        self.test_confounds = test_confounds             # one entry per test record (None, array or path), or None
         self.test_time = 0
         self.score = []
         self.iter = []
@@ -291,15 +379,20 @@ class rfMRIDictionaryScorer:
         self.info = info
         self.artifact_dir = artifact_dir
 
-    def _stage(self, dict_fact):
+    def _stage(self, masker, dict_fact):
         be = dict_fact._backend
-        self.data = [be.stage_X(np.ascontiguousarray(np.asarray(_load(r)), dtype=be.dtype)) for r in self.test_records]
+        detrend, standardize = bool(getattr(masker, 'detrend', False)), bool(getattr(masker, 'standardize', False))
+        self.data = []
+        for rec, conf in zip(self.test_records, _check_confounds(self.test_confounds, self.test_records)):
+            data = be.stage_X(np.ascontiguousarray(np.asarray(_load(rec)), dtype=be.dtype))
+            cleaned = _clean_staged(data, detrend, standardize, conf)
+            self.data.append(data if cleaned is None else cleaned)
         self.lengths = np.array([d.shape[0] for d in self.data])
 
     def __call__(self, masker, dict_fact, cpu_time, io_time):
         test_time = time.perf_counter()
         if not hasattr(self, 'data'):
-            self._stage(dict_fact)
+            self._stage(masker, dict_fact)
         scores = np.array([dict_fact.score(data) for data in self.data])
         score = np.sum(scores * self.lengths) / np.sum(self.lengths)
         self.test_time += time.perf_counter() - test_time

@@ -1,0 +1,264 @@
+"""Signal cleaning of fMRI records on the device: linear detrending, confound regression and standardization, the
+arithmetic of `nilearn.signal.clean` that the reference's masker applies to every record before `partial_fit`
+(modl/decomposition/fmri.py:281-296 the defaults, :525-526 and :577-585 the calls).  DESIGN.md section 20.
+
+The three steps are ONE orthogonal projection.  `cleaning_basis` builds, on the host in f64, a matrix Q (T x q) with
+orthonormal columns that spans the constant, the linear ramp and the confounds; per column x of a record (T time points x
+V voxels) `clean` then computes
+
+    r = x - Q (Q^T x),        out = r sqrt(T) / |r|  when standardizing (population variance 1),  r  otherwise.
+
+When standardizing, a column is FLAT and comes out as exact zeros if |r|^2 <= (q T eps64)^2 |x|^2: that factor is the
+worst-case f64 rounding of the projection, so what is left of such a column is rounding noise and not signal.  Without
+standardization nothing is zeroed.  A NaN or Inf poisons its own column only, which comes out as NaN throughout.
+
+Not implemented (arguments of nilearn.signal.clean that need more than this projection): `low_pass` / `high_pass`
+(Butterworth filtering), `smoothing_fwhm` (needs the 3-D volume, i.e. the masker), `sessions` (clean each session with a
+call of its own) and `standardize='psc'`."""
+import numpy as np
+import scipy.linalg
+import torch
+
+from ._lib import lib, check
+
+_EPS = float(np.finfo(np.float64).eps)
+CLEAN_MAX_REGRESSORS = lib.modl_clean_max_regressors()     # 64: the coefficients a thread of the kernel keeps
+
+__all__ = ['cleaning_basis', 'clean', 'clean_host']
+
+
+def _load_confounds(confounds, T):
+    if confounds is None:
+        return None
+    if isinstance(confounds, str):
+        confounds = np.load(confounds) if confounds.endswith('.npy') else np.loadtxt(
+            confounds, delimiter=',' if confounds.endswith('.csv') else None, ndmin=2)
+    if isinstance(confounds, torch.Tensor):
+        confounds = confounds.detach().cpu().numpy()
+    conf = np.asarray(confounds, dtype=np.float64)
+    if conf.ndim == 1:
+        conf = conf[:, None]
+    if conf.ndim != 2:
+        raise ValueError('confounds must be (n_time_points, n_confounds), got shape %s' % (conf.shape,))
+    if conf.shape[0] != T:
+        raise ValueError('confounds have %d time points, the signals have %d' % (conf.shape[0], T))
+    if not np.all(np.isfinite(conf)):
+        raise ValueError('confounds contain NaN or Inf')
+    return conf
+
+
+def _residualise(A, Q):
+    for _ in range(2):                                   # twice is enough (classical Gram-Schmidt, repeated)
+        A = A - Q.dot(Q.T.dot(A))
+    return A
+
+
+def cleaning_basis(T, detrend=True, standardize=True, confounds=None):
+    """Q (T, q), f64, orthonormal columns: what `clean` projects out of every column.
+
+    The constant 1/sqrt(T) is in Q when detrending or standardizing, the centred and normalised linear ramp when
+    detrending (not for T = 1, where it vanishes).  Confounds (array (T, c), or the path of a .npy / .csv file) are
+    centred in every case, as nilearn does, residualised on what is already in Q and scaled to unit norm; a column whose
+    residual norm is at most 100 eps sqrt(T) times its centred norm is dropped, the rest goes through a pivoted QR where
+    columns with |R_ii| <= 100 eps are dropped (nilearn's rank rule).  With neither `detrend` nor `standardize` the
+    constant is taken out of Q again: only the confounds are removed and the mean of the record is kept.
+    ValueError: more than modl_clean_max_regressors() = 64 columns are left, or bad confounds."""
+    T = int(T)
+    if T < 1:
+        raise ValueError('T must be at least 1, got %d' % T)
+    conf = _load_confounds(confounds, T)
+    Q = np.full((T, 1), 1.0 / np.sqrt(T))
+    if detrend:
+        ramp = np.arange(T, dtype=np.float64) - (T - 1) / 2.0
+        norm = np.linalg.norm(ramp)
+        if norm > 0:
+            Q = np.column_stack([Q, ramp / norm])
+    if conf is not None and conf.shape[1] > 0:
+        centred = conf - conf.mean(axis=0)
+        centred_norm = np.linalg.norm(centred, axis=0)
+        res = _residualise(centred, Q)
+        res_norm = np.linalg.norm(res, axis=0)
+        keep = res_norm > 100 * _EPS * np.sqrt(T) * centred_norm
+        if np.any(keep):
+            res = res[:, keep] / res_norm[keep]
+            Qc, R, _ = scipy.linalg.qr(res, mode='economic', pivoting=True)
+            rank = int(np.sum(np.abs(np.diag(R)) > 100 * _EPS))
+            Qc = _residualise(Qc[:, :rank], Q)
+            Q = np.column_stack([Q, Qc / np.linalg.norm(Qc, axis=0)])
+    if not (detrend or standardize):
+        Q = Q[:, 1:]
+    if Q.shape[1] > min(T, CLEAN_MAX_REGRESSORS):
+        raise ValueError('%d regressors are left after the rank rule, at most %d are supported'
+                         % (Q.shape[1], min(T, CLEAN_MAX_REGRESSORS)))
+    return np.ascontiguousarray(Q)
+
+
+def _destination_rows(permutation, T):
+    """result == cleaned[permutation]  <=>  cleaned row t goes to row dst[t], dst the inverse permutation"""
+    if permutation is None:
+        return None
+    perm = np.asarray(permutation)
+    if perm.ndim != 1 or perm.shape[0] != T or perm.dtype.kind not in 'iu' or \
+            not np.array_equal(np.sort(perm), np.arange(T)):
+        raise ValueError('permutation must be a permutation of 0 .. %d' % (T - 1))
+    dst = np.empty(T, dtype=np.int64)
+    dst[perm] = np.arange(T, dtype=np.int64)
+    return dst
+
+
+def _project_host(X, Q, standardize):
+    """the projection in f64 numpy: (T, V) f64"""
+    T, q = Q.shape
+    x = np.asarray(X, dtype=np.float64)
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        r = x - Q.dot(Q.T.dot(x))
+        xx = np.sum(x * x, axis=0)
+        if standardize:
+            rr = np.sum(r * r, axis=0)
+            flat = rr <= (q * T * _EPS) ** 2 * xx
+            r = r * (np.sqrt(T) / np.sqrt(rr))
+            r[:, flat] = 0.0
+        r[:, ~np.isfinite(xx)] = np.nan                  # a NaN or Inf in a column: NaN throughout
+    return r
+
+
+def _check_signals(signals):
+    if signals.ndim != 2:
+        raise ValueError('signals must be (n_time_points, n_voxels), got shape %s' % (tuple(signals.shape),))
+    if signals.shape[0] < 1 or signals.shape[1] < 1:
+        raise ValueError('signals must not be empty, got shape %s' % (tuple(signals.shape),))
+
+
+def _rows_ok(t):
+    return t.shape[1] == 1 or t.stride(1) == 1
+
+
+def _overlap(a, b):
+    """do two 2-D tensors with unit column stride touch the same bytes (as address ranges)"""
+    es = a.element_size()
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    a1 = a0 + ((a.shape[0] - 1) * a.stride(0) + a.shape[1]) * es
+    b1 = b0 + ((b.shape[0] - 1) * b.stride(0) + b.shape[1]) * es
+    return a0 < b1 and b0 < a1
+
+
+def _prepare(signals, detrend, standardize, confounds, permutation, out, basis):
+    """The one validator of `clean` and `clean_host`: (X, Q, dst) - the signals as they will be read (numpy array or CUDA
+    tensor, float32 / float64, unit column stride), the basis and the kernel's destination rows.  Raises ValueError."""
+    cuda = isinstance(signals, torch.Tensor)
+    if cuda and not signals.is_cuda:
+        raise ValueError('signals must be a numpy array or a CUDA tensor, got a tensor on %s' % signals.device)
+    X = signals if cuda else np.asarray(signals)
+    _check_signals(X)
+    if cuda:
+        if X.dtype not in (torch.float32, torch.float64):
+            raise ValueError('a CUDA tensor of float32 or float64 is expected, got %s' % X.dtype)
+        if not _rows_ok(X):
+            X = X.contiguous()
+    elif X.dtype not in (np.float32, np.float64):
+        X = X.astype(np.float64)
+    T = X.shape[0]
+    if basis is None:
+        Q = cleaning_basis(T, detrend, standardize, confounds)
+    else:
+        Q = np.ascontiguousarray(basis, dtype=np.float64)
+        if Q.ndim != 2 or Q.shape[0] != T or Q.shape[1] > min(T, CLEAN_MAX_REGRESSORS):
+            raise ValueError('basis must be (%d, q) with q <= %d, got shape %s' % (T, min(T, CLEAN_MAX_REGRESSORS), Q.shape))
+    dst = _destination_rows(permutation, T)
+    if out is not None:
+        if cuda:
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == X.device and out.dtype == X.dtype
+                    and tuple(out.shape) == tuple(X.shape) and _rows_ok(out)):
+                raise ValueError('out must be a CUDA tensor of the shape, dtype and device of signals with contiguous rows')
+            same = out.data_ptr() == X.data_ptr() and out.stride(0) == X.stride(0)
+            aliased = _overlap(out, X) and (dst is not None or not same)
+        else:
+            if not isinstance(out, np.ndarray) or out.shape != X.shape or out.dtype != X.dtype:
+                raise ValueError('out must be a numpy array of the shape and dtype of signals')
+            aliased = dst is not None and np.may_share_memory(out, X)
+        if aliased:
+            raise ValueError('out may alias signals only as the same view, and not together with a permutation')
+    return X, Q, dst
+
+
+def _finish_host(X, Q, standardize, permutation, out):
+    res = X if Q.shape[1] == 0 else _project_host(X, Q, standardize).astype(X.dtype)
+    if permutation is not None:
+        res = res[np.asarray(permutation)]
+    if out is None:
+        return res
+    if out is not res:
+        out[...] = res
+    return out
+
+
+def clean_host(signals, detrend=True, standardize=True, confounds=None, permutation=None, out=None, basis=None):
+    """`clean` in f64 numpy on the host, same semantics (the flat rule included), result rounded once to the dtype of
+    `signals`: what `clean` runs without a GPU, and the CPU baseline of scripts/bench_clean.py."""
+    if isinstance(signals, torch.Tensor):
+        raise ValueError('clean_host takes a numpy array')
+    X, Q, _ = _prepare(signals, detrend, standardize, confounds, permutation, out, basis)
+    return _finish_host(X, Q, standardize, permutation, out)
+
+
+def _clean_device(X, Q, standardize, dst, out):
+    """X: CUDA tensor (T, V) with unit column stride; Q: f64 numpy (T, q), q >= 1; dst: int64 numpy or None"""
+    from .device import ptr, stream_ptr
+    T, V = X.shape
+    q = Q.shape[1]
+    sx = 'f32' if X.dtype == torch.float32 else 'f64'
+    dtype_id = 0 if X.dtype == torch.float32 else 1
+    if out is None:
+        out = torch.empty((T, V), dtype=X.dtype, device=X.device)
+    need = lib.modl_clean_workspace(dtype_id, T, V, q)
+    if need == 0:
+        raise ValueError('modl_clean: unsupported shape T = %d, V = %d, q = %d' % (T, V, q))
+    with torch.cuda.device(X.device):
+        d_Q = torch.from_numpy(np.ascontiguousarray(Q)).to(X.device)
+        d_dst = None if dst is None else torch.from_numpy(dst).to(X.device)
+        ws = torch.empty(need, dtype=torch.uint8, device=X.device)
+        check(getattr(lib, 'modl_clean_' + sx)(ptr(X), X.stride(0), T, V, ptr(d_Q), q, int(bool(standardize)), ptr(d_dst),
+                                               ptr(out), out.stride(0), ptr(ws), need, stream_ptr(X.device)), 'modl_clean')
+    return out
+
+
+def clean(signals, detrend=True, standardize=True, confounds=None, permutation=None, out=None, basis=None):
+    """Detrend, regress confounds out of and standardize one record (module docstring), on the device.
+
+    signals      (T, V) time points x voxels, float32 or float64: a numpy array (a numpy array comes back) or a CUDA
+                 tensor (a CUDA tensor comes back, nothing crosses the host link but the small basis).  A view with a row
+                 stride is used as it stands.
+    detrend      remove the mean and the linear trend of every column
+    standardize  scale every column to zero mean and population variance 1; flat columns become exact zeros
+    confounds    None, (T, c) array, or the path of a .npy / .csv file: regressed out of every column
+    permutation  None or a permutation of 0 .. T-1: the result is clean(...)[permutation], written in that order by the
+                 kernel itself (fMRIDictFact.fit folds the row permutation of every record into its cleaning)
+    out          None, or where to write: same kind, shape and dtype as `signals`.  `out is signals` cleans in place;
+                 together with a permutation `out` must not alias `signals`.
+    basis        None, or what cleaning_basis(T, detrend, standardize, confounds) returned for this record: it is used
+                 instead of building it again (`detrend` and `confounds` are then not looked at) - for a record that
+                 is cleaned more than once, as in every epoch of a fit.
+
+    With nothing to remove (detrend = standardize = False, no confounds left) the input itself is returned, no launch.
+    Every column is computed on its own with sums in f64 in an order that depends on T alone: clean(X[:, a:b]) has the
+    bits of clean(X)[:, a:b].  Without a GPU a numpy input goes through `clean_host`.
+    ValueError: wrong ranks, a T mismatch between signals and confounds, non-finite confounds, more than 64 regressors,
+    a `permutation` that is none, an `out` that does not fit or aliases the input together with a permutation."""
+    X, Q, dst = _prepare(signals, detrend, standardize, confounds, permutation, out, basis)
+    if isinstance(X, torch.Tensor):
+        if Q.shape[1] > 0:
+            return _clean_device(X, Q, standardize, dst, out)
+        res = X if permutation is None else X[torch.from_numpy(np.asarray(permutation, dtype=np.int64)).to(X.device)]
+        if out is None:
+            return res
+        if not (out.data_ptr() == res.data_ptr() and out.stride(0) == res.stride(0)):
+            out.copy_(res)
+        return out
+    if Q.shape[1] == 0 or lib.modl_device_count() <= 0:
+        return _finish_host(X, Q, standardize, permutation, out)
+    device = torch.device('cuda', torch.cuda.current_device())
+    res = _clean_device(torch.from_numpy(np.ascontiguousarray(X)).to(device), Q, standardize, dst, None).cpu().numpy()
+    if out is None:
+        return res
+    out[...] = res
+    return out
