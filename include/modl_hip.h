@@ -854,6 +854,37 @@ int modl_clean_f32(const float *d_X, int64_t ldx, int64_t T, int64_t V, const do
 int modl_clean_f64(const double *d_X, int64_t ldx, int64_t T, int64_t V, const double *d_Q, int q, int standardize,
                    const int64_t *d_dst_row, double *d_out, int64_t ldo, void *d_ws, size_t ws_bytes, void *stream);
 
+/* Zero-phase Butterworth filtering of a record (csrc/filtfilt.hip; the low_pass / high_pass of
+ * nilearn.signal.clean that the reference's masker takes, modl/decomposition/fmri.py:281-299).  d_X[T][ldx] holds T time
+ * points of V voxels (ldx >= V, the padding is never read); every column x is treated on its own:
+ *   out[d_dst_row[t]] = filtfilt(b, a, detrend ? x - line(x) : x)[t]
+ * which is scipy.signal.filtfilt(b, a, x) with its defaults: padlen = 3 n_taps, odd extension at both ends (left
+ * 2 x[0] - x[padlen .. 1], right 2 x[T-1] - x[T-2 .. T-padlen-1]), a forward pass in direct form II transposed started
+ * from zi ext[0], the same over the reversed forward output started from zi times its first element, the pads trimmed.
+ * line(x) is the least-squares line of the column (mean and ramp), summed in f64 in ascending t.
+ * b, a (n_taps each, a[0] == 1) and zi (n_taps - 1; scipy.signal.lfilter_zi(b, a)) are HOST pointers, f64: they travel as
+ * kernel arguments (modl_amd/signal.py: butterworth_coefficients builds them with scipy.signal.butter).  The filter state
+ * is kept in f64 for both dtypes, the forward output crosses the workspace as f64, the result is rounded once on store.
+ * The arithmetic order of a column depends on T and the taps alone - not on V, on the column's place in the call, on ldx /
+ * ldo or on d_dst_row - so a column has the same bits wherever it stands and from run to run.  A column that holds a NaN
+ * or Inf comes out as NaN throughout and touches no other column; an all-zero column comes out as exact zeros.
+ * d_dst_row (int64[T], device, may be NULL): filtered row t is written to row d_dst_row[t] of d_out[T][ldo]; it has to be
+ * a permutation of 0 .. T-1, which the CALLER checks (an entry outside 0 .. T-1 is skipped on the device, nothing more).
+ * d_out == d_X (in place) is legal with d_dst_row == NULL and ldo == ldx only; any other overlap of the address ranges of
+ * d_X[T][ldx] and d_out[T][ldo] is refused.  Asynchronous on `stream`: one launch, no atomics.
+ * MODL_EINVAL before any device work: a NULL d_X / d_out / b / a / zi, n_taps outside 2 .. modl_filtfilt_max_taps() = 12,
+ * a[0] != 1, a non-finite coefficient, T <= 3 n_taps, V < 1, ldx < V, ldo < V, the in-place / overlap rule.  d_ws NULL or
+ * ws_bytes below modl_filtfilt_workspace(...) = (T + 3 n_taps) V 8 bytes: MODL_ENOMEM; no device: MODL_ENOGPU.
+ * modl_filtfilt_workspace: bytes of scratch (0 for bad arguments). */
+int modl_filtfilt_max_taps(void);
+size_t modl_filtfilt_workspace(int dtype, int64_t T, int64_t V, int n_taps);
+int modl_filtfilt_f32(const float *d_X, int64_t ldx, int64_t T, int64_t V, const double *b, const double *a,
+                      const double *zi, int n_taps, int detrend, const int64_t *d_dst_row, float *d_out, int64_t ldo,
+                      void *d_ws, size_t ws_bytes, void *stream);
+int modl_filtfilt_f64(const double *d_X, int64_t ldx, int64_t T, int64_t V, const double *b, const double *a,
+                      const double *zi, int n_taps, int detrend, const int64_t *d_dst_row, double *d_out, int64_t ldo,
+                      void *d_ws, size_t ws_bytes, void *stream);
+
 /* Amari discrepancy between dictionaries (modl/decomposition/stability.py:7-31: amari_discrepency,
  * mean_amari_discrepency).  For the n dictionaries h_d_dicts[i] (device, row-major k_i x p, atoms in rows), every pair
  * a < b in the reference's generator order (a outer, b inner) gets

@@ -183,6 +183,10 @@ def bind(lib):
         _sig('modl_csr_fill_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp)
         _sig('modl_csr_decode_' + _sfx, C.c_int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp)
         _sig('modl_clean_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _vp, _vp, _i64, _vp, _sz, _vp)
+        _sig('modl_filtfilt_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _i64, _vp, _sz,
+             _vp)
+    _sig('modl_filtfilt_max_taps', C.c_int)
+    _sig('modl_filtfilt_workspace', _sz, C.c_int, _i64, _i64, C.c_int)
     _sig('modl_clean_max_regressors', C.c_int)
     _sig('modl_clean_workspace', _sz, C.c_int, _i64, _i64, C.c_int)
     _sig('modl_csr_compact_workspace', _sz, _i64)

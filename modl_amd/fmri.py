@@ -14,7 +14,9 @@ tests/golden/fmri.npz); `intended_schedules=True` runs what the code was written
 Signal cleaning.  In the reference every record passes through the masker's nilearn.signal.clean before it is fitted or
 coded (fmri.py:525-526, :577-585), steered by `standardize`, `detrend` and per-record `confounds`.  That arithmetic -
 unlike the masking - is not IO: it runs here on the device (modl_amd/signal.py) on the record
-that `_RecordStager` has already uploaded, with the epoch's row permutation folded into the cleaning's write."""
+that `_RecordStager` has already uploaded, with the epoch's row permutation folded into the cleaning's write.  The
+masker's temporal filter (`low_pass`, `high_pass`, `t_r`, fmri.py:46-61: a zero-phase Butterworth band-pass) runs there
+too (csrc/filtfilt.hip)."""
 import time
 from concurrent.futures import ThreadPoolExecutor
 from math import sqrt
@@ -51,17 +53,24 @@ def _check_confounds(confounds, records):
     return list(confounds)
 
 
-def _clean_staged(data, detrend, standardize, confounds, permutation=None, basis=None):
+def _cleans(detrend, standardize, confounds, low_pass, high_pass):
+    """is there anything to clean"""
+    return bool(detrend or standardize or confounds is not None or low_pass is not None or high_pass is not None)
+
+
+def _clean_staged(data, detrend, standardize, confounds, permutation=None, basis=None, low_pass=None, high_pass=None,
+                  t_r=None):
     """A staged record (a CUDA tensor, or a numpy array on a backend without a GPU) cleaned where it is; with
     `permutation` the rows come out in that order.  `basis`: the record's cleaning_basis, when the caller keeps it.
     None when there is nothing to clean."""
-    if not (detrend or standardize or confounds is not None):
+    if not _cleans(detrend, standardize, confounds, low_pass, high_pass):
         return None
+    filt = dict(low_pass=low_pass, high_pass=high_pass, t_r=t_r)
     if isinstance(data, torch.Tensor) and data.is_cuda:
-        return clean(data, detrend, standardize, confounds, permutation, basis=basis)
+        return clean(data, detrend, standardize, confounds, permutation, basis=basis, **filt)
     was_tensor = isinstance(data, torch.Tensor)
     out = clean_host(data.numpy() if was_tensor else np.asarray(data), detrend, standardize, confounds, permutation,
-                     basis=basis)
+                     basis=basis, **filt)
     return torch.from_numpy(out) if was_tensor else out
 
 
@@ -129,15 +138,22 @@ class fMRIDictFact(BaseEstimator):
     transform and score take.  The reference defaults to True / True (fmri.py:281-296); the defaults here are
     False / False, so that an estimator built without these arguments keeps computing what it computed before they
     existed (records handed over as they are, e.g. cleaned by the caller) - pass True / True for the reference's
-    pipeline."""
+    pipeline.
+    `low_pass`, `high_pass`, `t_r` (None / None / None as in the reference, fmri.py:46-61): cut-off frequencies in Hz and
+    repetition time in seconds of the zero-phase Butterworth filter (order 5) that every record passes before the
+    confounds are regressed out (modl_amd.signal.clean); a record needs more than 3 * 6 (3 * 11 for a band) time points."""
 
     _dict_fact_class = DictFact
     _coder_class = Coder
 
     def __init__(self, method='masked', step_size=1, n_components=20, n_epochs=1, alpha=0.1, dict_init=None,
                  random_state=None, batch_size=20, reduction=1, learning_rate=1, positive=False, verbose=0,
-                 callback=None, n_jobs=1, intended_schedules=False, standardize=False, detrend=False):
+                 callback=None, n_jobs=1, intended_schedules=False, standardize=False, detrend=False, low_pass=None,
+                 high_pass=None, t_r=None):
         self.intended_schedules = intended_schedules
+        self.low_pass = low_pass
+        self.high_pass = high_pass
+        self.t_r = t_r
         self.standardize = standardize
         self.detrend = detrend
         self.method = method
@@ -183,8 +199,10 @@ class fMRIDictFact(BaseEstimator):
             dtype, n_voxels = arr.dtype, arr.shape[1]
         # the basis of a record depends on its length, the flags and its confounds alone: built (confound files read, the
         # host QR run) once per record here, not once per record and epoch inside the timed loop
-        bases = [cleaning_basis(n, self.detrend, self.standardize, c) if (self.detrend or self.standardize or c is not None)
-                 else None for n, c in zip(lengths, confounds)]
+        filt = dict(low_pass=self.low_pass, high_pass=self.high_pass, t_r=self.t_r)
+        bases = [cleaning_basis(n, self.detrend, self.standardize, c, **filt)
+                 if _cleans(self.detrend, self.standardize, c, self.low_pass, self.high_pass) else None
+                 for n, c in zip(lengths, confounds)]
         indices_list = np.zeros(n_records + 1, dtype='int')
         indices_list[1:] = np.cumsum(lengths)
         n_samples = int(indices_list[-1]) + 1                        # fmri.py:476 (the + 1 is the reference's)
@@ -229,7 +247,7 @@ class fMRIDictFact(BaseEstimator):
                     else:
                         sample_indices = None
                     rows = _clean_staged(data, self.detrend, self.standardize, confounds[record], permutation,
-                                         basis=bases[record])
+                                         basis=bases[record], **filt)
                     if rows is None:
                         rows = stager.rows(data, permutation)
                     dict_fact.partial_fit(rows, sample_indices=sample_indices)
@@ -242,7 +260,8 @@ class fMRIDictFact(BaseEstimator):
         return self
 
     def _cleaned(self, records, confounds):
-        return _cleaned_records(self.coder_, records, confounds, self.detrend, self.standardize)
+        return _cleaned_records(self.coder_, records, confounds, self.detrend, self.standardize, self.low_pass,
+                                self.high_pass, self.t_r)
 
     def transform(self, records, confounds=None):
         """Loadings of each record on the learned maps (fmri.py:131-164); the records are cleaned first with the
@@ -257,16 +276,17 @@ class fMRIDictFact(BaseEstimator):
         return np.sum(scores * lens) / np.sum(lens)
 
 
-def _cleaned_records(coder, records, confounds, detrend, standardize):
+def _cleaned_records(coder, records, confounds, detrend, standardize, low_pass=None, high_pass=None, t_r=None):
     """the records as the coder takes them: untouched host arrays when nothing is cleaned, otherwise staged on the coder's
     device in its dtype and cleaned there"""
     confounds = _check_confounds(confounds, records)
     out = []
     for rec, conf in zip(records, confounds):
         arr = np.asarray(_load(rec))
-        if detrend or standardize or conf is not None:
+        if _cleans(detrend, standardize, conf, low_pass, high_pass):
             be = coder._backend
-            arr = _clean_staged(be.stage_X(np.ascontiguousarray(arr, dtype=be.dtype)), detrend, standardize, conf)
+            arr = _clean_staged(be.stage_X(np.ascontiguousarray(arr, dtype=be.dtype)), detrend, standardize, conf,
+                                low_pass=low_pass, high_pass=high_pass, t_r=t_r)
         out.append(arr)
     return out
 
@@ -277,13 +297,17 @@ class fMRICoder(BaseEstimator):
     contract of input_data/fmri/unmask.py:37-55) - the masking arguments are dropped as for fMRIDictFact, the rest of
     the constructor is the reference's.  `dictionary`: (n_components, n_voxels) array, or a .npy path.
     `standardize`, `detrend` (False / False as in the reference, fmri.py:375-376) and the `confounds` of transform / score:
-    the records are cleaned on the device before they are coded (modl_amd.signal.clean)."""
+    the records are cleaned on the device before they are coded (modl_amd.signal.clean); `low_pass`, `high_pass`, `t_r`
+    (None as in the reference, fmri.py:375-395): its zero-phase Butterworth filter, as for fMRIDictFact."""
 
     _coder_class = Coder
 
     def __init__(self, dictionary, alpha=0.1, transform_batch_size=None, n_components=None, n_jobs=1, verbose=0,
-                 standardize=False, detrend=False):
+                 standardize=False, detrend=False, low_pass=None, high_pass=None, t_r=None):
         self.dictionary = dictionary
+        self.low_pass = low_pass
+        self.high_pass = high_pass
+        self.t_r = t_r
         self.standardize = standardize
         self.detrend = detrend
         self.alpha = alpha
@@ -316,8 +340,9 @@ class fMRICoder(BaseEstimator):
         if X.shape[1] != self.components_.shape[1]:
             raise ValueError('record has %d voxels, the maps have %d' % (X.shape[1], self.components_.shape[1]))
         X = np.ascontiguousarray(X, dtype=self.components_.dtype)
-        if self.detrend or self.standardize or confounds is not None:
-            X = _clean_staged(self.coder_._backend.stage_X(X), self.detrend, self.standardize, confounds)
+        if _cleans(self.detrend, self.standardize, confounds, self.low_pass, self.high_pass):
+            X = _clean_staged(self.coder_._backend.stage_X(X), self.detrend, self.standardize, confounds,
+                              low_pass=self.low_pass, high_pass=self.high_pass, t_r=self.t_r)
         return X
 
     def _confounds(self, confounds, records):
@@ -361,7 +386,7 @@ class rfMRIDictionaryScorer:
     the three sums of the objective on the device), so neither the test set nor the dictionary crosses the host
     link again; three doubles per record come back.  Signature of the reference: `scorer(masker, dict_fact,
     cpu_time, io_time)`; the first argument (the masker there, the fMRIDictFact here) plays the masker's part: its
-    `standardize` / `detrend` and `test_confounds` (one entry per test record) say how the test records are cleaned -
+    `standardize` / `detrend`, `low_pass` / `high_pass` / `t_r` and `test_confounds` (one entry per test record) say how the test records are cleaned -
     once, on the device, when they are staged (modl_amd.signal.clean).
     `artifact_dir`: `info.pkl` as in the reference (:621-625) and the flipped maps as `components_<n_iter>.npy`
     (the reference writes a NIfTI image through the masker, which is out of scope)."""
@@ -385,7 +410,8 @@ class rfMRIDictionaryScorer:
         self.data = []
         for rec, conf in zip(self.test_records, _check_confounds(self.test_confounds, self.test_records)):
             data = be.stage_X(np.ascontiguousarray(np.asarray(_load(rec)), dtype=be.dtype))
-            cleaned = _clean_staged(data, detrend, standardize, conf)
+            cleaned = _clean_staged(data, detrend, standardize, conf, low_pass=getattr(masker, 'low_pass', None),
+                                    high_pass=getattr(masker, 'high_pass', None), t_r=getattr(masker, 't_r', None))
             self.data.append(data if cleaned is None else cleaned)
         self.lengths = np.array([d.shape[0] for d in self.data])
 
