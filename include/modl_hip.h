@@ -885,6 +885,48 @@ int modl_filtfilt_f64(const double *d_X, int64_t ldx, int64_t T, int64_t V, cons
                       const double *zi, int n_taps, int detrend, const int64_t *d_dst_row, double *d_out, int64_t ldo,
                       void *d_ws, size_t ws_bytes, void *stream);
 
+/* Spatial smoothing and masking of a volume (csrc/masker.hip; what the reference's masker does to
+ * a 4-D image before signal.clean: nilearn's _smooth_array, i.e. scipy.ndimage.gaussian_filter1d per spatial axis, then the
+ * mask).  d_vol holds T frames of a contiguous box [n0][n1][n2] (n2 fastest), frame t at d_vol + t * frame_stride
+ * (frame_stride >= n0 n1 n2, in elements; every offset is 64-bit).  Per frame:
+ *   1. every non-finite element counts as 0;
+ *   2. per axis a with r_a > 0 the frame is correlated with the 2 r_a + 1 weights w_a (HOST, f64, non-negative, sum 1),
+ *      boundary 'reflect' of scipy (d c b a | a b c d | d c b a, period 2 n_a: a short axis is reflected repeatedly);
+ *      r_a == 0 or w_a == NULL leaves the axis untouched, bit for bit;
+ *   3. d_out[dst(t)][d_col[v]] = the smoothed value of voxel v, for every v with d_col[v] >= 0.
+ * d_col[n0][n1][n2] (int32) is the output column of a voxel, -1 outside the mask; the caller builds it once per mask, its
+ * values lie in 0 .. V-1 and carry the voxel order (the kernel knows three axes of a box and nothing of x / y / z).
+ * d_dst_row (int64[T], may be NULL): frame t goes to row d_dst_row[t] of d_out[T][ldo]; the CALLER checks that it is a
+ * permutation, an entry outside 0 .. T-1 is skipped on the device.
+ * Every axis sum runs in f64 in ascending tap order for both dtypes and is rounded once to the dtype; the bits of an
+ * element depend on the volume and the weights alone - not on the mask, V, the voxel's place in its tile, T or d_dst_row.
+ * One launch (after the copy of the weights into d_ws), no intermediate volume: a workgroup smooths one tile of one frame
+ * in LDS, and a tile without a masked voxel reads no volume data.  All radii 0: the plain masking gather of 1 and 3,
+ * exact.  Asynchronous on `stream`, no atomics.
+ * MODL_EINVAL before any device work: a NULL d_vol / d_col / d_out, T / n_a / V < 1, n0 n1 n2 > INT32_MAX, V > n0 n1 n2,
+ * frame_stride < n0 n1 n2, ldo < V, a radius outside 0 .. modl_smooth_max_radius() = 8, a non-finite or negative weight,
+ * weights whose sum differs from 1 by more than 1e-12, any overlap of d_vol and d_out.  d_ws NULL or ws_bytes below
+ * modl_smooth_mask_workspace(...): MODL_ENOMEM; no device: MODL_ENOGPU.  modl_smooth_mask_workspace returns 0 for bad
+ * arguments.  modl_smooth_tile: the tile (3 ints) that the kernel uses for these radii and this dtype. */
+int modl_smooth_max_radius(void);
+int modl_smooth_tile(int dtype, int r0, int r1, int r2, int *tile);
+size_t modl_smooth_mask_workspace(int dtype, int64_t T, int64_t n0, int64_t n1, int64_t n2, int r0, int r1, int r2);
+int modl_smooth_mask_f32(const float *d_vol, int64_t frame_stride, int64_t T, int64_t n0, int64_t n1, int64_t n2,
+                         const double *w0, int r0, const double *w1, int r1, const double *w2, int r2, const int32_t *d_col,
+                         int64_t V, const int64_t *d_dst_row, float *d_out, int64_t ldo, void *d_ws, size_t ws_bytes,
+                         void *stream);
+int modl_smooth_mask_f64(const double *d_vol, int64_t frame_stride, int64_t T, int64_t n0, int64_t n1, int64_t n2,
+                         const double *w0, int r0, const double *w1, int r1, const double *w2, int r2, const int32_t *d_col,
+                         int64_t V, const int64_t *d_dst_row, double *d_out, int64_t ldo, void *d_ws, size_t ws_bytes,
+                         void *stream);
+/* The inverse of the masking: d_out[n][n0 n1 n2] is zero-filled by the call, then d_out[i][d_vox[c]] = d_rows[i][c] for the
+ * V flat voxel indices d_vox (int64, distinct; an index outside the box is skipped).  Asynchronous on `stream`.
+ * MODL_EINVAL: a NULL pointer, n / V / n_a < 1, V > n0 n1 n2, ldr < V, any overlap of d_rows and d_out; MODL_ENOGPU. */
+int modl_unmask_f32(const float *d_rows, int64_t ldr, int64_t n, int64_t V, const int64_t *d_vox, int64_t n0, int64_t n1,
+                    int64_t n2, float *d_out, void *stream);
+int modl_unmask_f64(const double *d_rows, int64_t ldr, int64_t n, int64_t V, const int64_t *d_vox, int64_t n0, int64_t n1,
+                    int64_t n2, double *d_out, void *stream);
+
 /* Amari discrepancy between dictionaries (modl/decomposition/stability.py:7-31: amari_discrepency,
  * mean_amari_discrepency).  For the n dictionaries h_d_dicts[i] (device, row-major k_i x p, atoms in rows), every pair
  * a < b in the reference's generator order (a outer, b inner) gets

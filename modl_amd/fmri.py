@@ -16,7 +16,13 @@ coded (fmri.py:525-526, :577-585), steered by `standardize`, `detrend` and per-r
 unlike the masking - is not IO: it runs here on the device (modl_amd/signal.py) on the record
 that `_RecordStager` has already uploaded, with the epoch's row permutation folded into the cleaning's write.  The
 masker's temporal filter (`low_pass`, `high_pass`, `t_r`, fmri.py:46-61: a zero-phase Butterworth band-pass) runs there
-too (csrc/filtfilt.hip)."""
+too (csrc/filtfilt.hip).
+
+Smoothing and masking.  The masker's order is smooth the 4-D volume, apply the mask, clean.  With `mask` (and
+`smoothing_fwhm`, `voxel_size`) a record may be a 4-D array (X, Y, Z, T) or the path of a .npy file holding one: the
+staged volume is smoothed and masked on the device by one launch (modl_amd/masker.py, csrc/masker.hip, DESIGN.md section
+23) and then cleaned as above; the learned maps go back to a volume as `components_img_`.  Reading NIfTI files stays out
+of scope."""
 import time
 from concurrent.futures import ThreadPoolExecutor
 from math import sqrt
@@ -29,7 +35,8 @@ from sklearn.utils import check_random_state
 
 from .device import gather_rows
 from .dict_fact import DictFact, Coder
-from .signal import clean, clean_host, cleaning_basis
+from .masker import ArrayMasker, unmask
+from .signal import clean, clean_host, cleaning_basis, _destination_rows
 
 METHODS = {'masked': {'G_agg': 'masked', 'Dx_agg': 'masked'},           # fmri.py:440-445
            'dictionary only': {'G_agg': 'full', 'Dx_agg': 'full'},
@@ -74,6 +81,47 @@ def _clean_staged(data, detrend, standardize, confounds, permutation=None, basis
     return torch.from_numpy(out) if was_tensor else out
 
 
+def _make_masker(mask, smoothing_fwhm, voxel_size):
+    """the fitted ArrayMasker of an estimator's masking arguments (it only smooths and masks; the estimator cleans), None
+    without a mask"""
+    if mask is None:
+        if smoothing_fwhm is not None:
+            raise ValueError('smoothing_fwhm = %r needs the volume: pass `mask` and 4-D records' % (smoothing_fwhm,))
+        return None
+    return ArrayMasker(mask, voxel_size=(1, 1, 1) if voxel_size is None else voxel_size, smoothing_fwhm=smoothing_fwhm).fit()
+
+
+def _record_shape(arr, masker):
+    """(time points, voxels) of a record: a 2-D record, or a 4-D volume (X, Y, Z, T) under a mask"""
+    if arr.ndim == 4:
+        if masker is None:
+            raise ValueError('a 4-D record of shape %s needs the `mask` argument' % (tuple(arr.shape),))
+        return arr.shape[3], masker.n_voxels_
+    return arr.shape[0], arr.shape[1]
+
+
+def _fortran(arr):
+    return arr.ndim == 4 and arr.flags.f_contiguous and not arr.flags.c_contiguous
+
+
+def _mask_record(arr, masker, be):
+    """A loaded record as time points x voxels: a 2-D record as it is; a 4-D volume smoothed and masked by `masker` - on
+    the backend's device, where the result stays, or through smooth_mask's own dispatch on a backend without a GPU."""
+    if arr.ndim != 4:
+        return arr
+    _record_shape(arr, masker)
+    device = getattr(be, 'device', None)
+    if device is not None and device.type == 'cuda':
+        fortran = _fortran(arr)                                      # (its transpose is C-ordered: uploaded as it lies)
+        t = torch.from_numpy(np.ascontiguousarray(arr.T if fortran else arr, dtype=be.dtype)).to(device)
+        return masker.mask_volume(t.permute(3, 2, 1, 0) if fortran else t)
+    return masker.mask_volume(np.asarray(arr, dtype=be.dtype))
+
+
+def _staged_2d(arr, be):
+    return arr if isinstance(arr, torch.Tensor) else be.stage_X(np.ascontiguousarray(arr, dtype=be.dtype))
+
+
 def _flip(components):
     """Flip a map when its negative part is larger (fmri.py:549-556)."""
     components = components.copy()
@@ -87,7 +135,11 @@ class _RecordStager:
     """Double-buffered record streaming: while a record is being fitted, a worker thread loads the
     next one (np.load of the .npy file, the dtype conversion of fmri.py:533) into pinned host memory and copies it to
     HBM on a side stream; the row permutation of fmri.py:535-541 is then a gather on the device.  Backends without a
-    GPU (the oracle-backed test backend) get the plain host path."""
+    GPU (the oracle-backed test backend) get the plain host path.
+    Ownership: the staged tensor is allocated on the side stream and consumed on the caller's stream.  `take` makes the
+    caller's stream wait for the copy and marks the tensor as used on it (`record_stream`), so the caller may drop it
+    right after launching a kernel that reads it - as the 4-D path does once the volume is smoothed and masked - and
+    the allocator hands its memory to a later prefetch only after that work has finished."""
 
     def __init__(self, dict_fact, dtype):
         be = dict_fact._backend
@@ -100,12 +152,18 @@ class _RecordStager:
 
     def _stage(self, record):
         arr = np.asarray(_load(record))
+        fortran = _fortran(arr)                                      # a 4-D volume in nibabel's layout: staged as it
+        if fortran:                                                  # lies, as the C-ordered (T, Z, Y, X)
+            arr = arr.T
         if not self.on_gpu:
-            return arr.astype(self.dtype)
+            arr = arr.astype(self.dtype)
+            return arr.T if fortran else arr
         host = torch.empty(arr.shape, dtype=torch.float32 if self.dtype == np.float32 else torch.float64, pin_memory=True)
         np.copyto(host.numpy(), arr, casting='unsafe')               # load + dtype conversion straight into pinned memory
         with torch.cuda.stream(self.stream):
             dev = host.to(self.device, non_blocking=True)
+            if fortran:
+                dev = dev.permute(3, 2, 1, 0)
             done = torch.cuda.Event()
             done.record(self.stream)
         return dev, done, host                                       # (host kept alive until the copy is consumed)
@@ -117,7 +175,9 @@ class _RecordStager:
         if not self.on_gpu:
             return self._stage(self.pending)
         dev, done, _host = self.pending.result()
-        torch.cuda.current_stream(self.device).wait_event(done)
+        current = torch.cuda.current_stream(self.device)
+        current.wait_event(done)
+        dev.record_stream(current)                                   # (see the class docstring: ownership)
         return dev
 
     def rows(self, data, permutation):
@@ -141,7 +201,15 @@ class fMRIDictFact(BaseEstimator):
     pipeline.
     `low_pass`, `high_pass`, `t_r` (None / None / None as in the reference, fmri.py:46-61): cut-off frequencies in Hz and
     repetition time in seconds of the zero-phase Butterworth filter (order 5) that every record passes before the
-    confounds are regressed out (modl_amd.signal.clean); a record needs more than 3 * 6 (3 * 11 for a band) time points."""
+    confounds are regressed out (modl_amd.signal.clean); a record needs more than 3 * 6 (3 * 11 for a band) time points.
+    `mask` (X, Y, Z) boolean, `smoothing_fwhm` (mm; a number or one per axis), `voxel_size` (mm, (1, 1, 1) when None): with a
+    mask a record may be a 4-D array (X, Y, Z, T) or the path of a .npy file holding one; it is smoothed and masked on the
+    device (modl_amd.masker.smooth_mask) before it is cleaned, `dict_init` may be (X, Y, Z, k) (masked, not smoothed), and
+    `components_img_` holds the maps as an (X, Y, Z, n_components) array.  2-D records still pass as they are: they are
+    taken as masked AND smoothed already, so `smoothing_fwhm` does not touch them (ArrayMasker.transform raises for such
+    an input; here the MultiRawMasker contract wins).  All three None (the default): nothing changes.  `smoothing_fwhm`
+    without `mask` is a ValueError.  `dict_init` may also be the path of a .npy file.  `fit` sets `masker_`, the fitted
+    ArrayMasker that smooths and masks (None without a mask)."""
 
     _dict_fact_class = DictFact
     _coder_class = Coder
@@ -149,8 +217,11 @@ class fMRIDictFact(BaseEstimator):
     def __init__(self, method='masked', step_size=1, n_components=20, n_epochs=1, alpha=0.1, dict_init=None,
                  random_state=None, batch_size=20, reduction=1, learning_rate=1, positive=False, verbose=0,
                  callback=None, n_jobs=1, intended_schedules=False, standardize=False, detrend=False, low_pass=None,
-                 high_pass=None, t_r=None):
+                 high_pass=None, t_r=None, mask=None, smoothing_fwhm=None, voxel_size=None):
         self.intended_schedules = intended_schedules
+        self.mask = mask
+        self.smoothing_fwhm = smoothing_fwhm
+        self.voxel_size = voxel_size
         self.low_pass = low_pass
         self.high_pass = high_pass
         self.t_r = t_r
@@ -179,10 +250,15 @@ class fMRIDictFact(BaseEstimator):
         if records is None:
             raise ValueError('records is None, use Coder instead')
         confounds = _check_confounds(confounds, records)
+        masker = self.masker_ = _make_masker(self.mask, self.smoothing_fwhm, self.voxel_size)
         n_components = self.n_components
         dict_init = self.dict_init
         if dict_init is not None:                                    # fmri.py:415-416, 468-469
-            dict_init = np.asarray(dict_init)[:n_components]
+            dict_init = np.asarray(_load(dict_init))
+            if masker is not None and dict_init.ndim == 4:           # maps given as a volume: masked, never smoothed
+                _record_shape(dict_init, masker)
+                dict_init = np.ascontiguousarray(dict_init[masker.maps_.mask].T)
+            dict_init = dict_init[:n_components]
             n_components = dict_init.shape[0]
         random_state = check_random_state(self.random_state)
         reduction = self.reduction
@@ -195,8 +271,9 @@ class fMRIDictFact(BaseEstimator):
         lengths, dtype, n_voxels = [], None, None
         for rec in records:                                          # _lazy_scan, fmri.py:559-575
             arr = _load(rec, mmap=True)
-            lengths.append(arr.shape[0])
-            dtype, n_voxels = arr.dtype, arr.shape[1]
+            n_rows, n_voxels = _record_shape(arr, masker)
+            lengths.append(n_rows)
+            dtype = arr.dtype
         # the basis of a record depends on its length, the flags and its confounds alone: built (confound files read, the
         # host QR run) once per record here, not once per record and epoch inside the timed loop
         filt = dict(low_pass=self.low_pass, high_pass=self.high_pass, t_r=self.t_r)
@@ -241,13 +318,21 @@ class fMRIDictFact(BaseEstimator):
                         stager.prefetch(records[record_list[pos + 1]])
                     self.io_time_ += time.perf_counter() - t0
                     t0 = time.perf_counter()
-                    permutation = random_state.permutation(data.shape[0])
+                    permutation = random_state.permutation(_record_shape(data, masker)[0])
                     if named in ['average', 'gram']:
                         sample_indices = np.arange(indices_list[record], indices_list[record + 1])[permutation]
                     else:
                         sample_indices = None
-                    rows = _clean_staged(data, self.detrend, self.standardize, confounds[record], permutation,
-                                         basis=bases[record], **filt)
+                    rows = None
+                    if data.ndim == 4:                               # smooth and mask the staged volume where it is
+                        fold = bases[record] is None                 # nothing to clean: this launch permutes the rows
+                        data = masker.mask_volume(data, dst_row=_destination_rows(permutation, len(permutation))
+                                                  if fold else None)
+                        if fold:
+                            rows = data
+                    if rows is None:
+                        rows = _clean_staged(data, self.detrend, self.standardize, confounds[record], permutation,
+                                             basis=bases[record], **filt)
                     if rows is None:
                         rows = stager.rows(data, permutation)
                     dict_fact.partial_fit(rows, sample_indices=sample_indices)
@@ -257,11 +342,13 @@ class fMRIDictFact(BaseEstimator):
         self.dict_fact_ = dict_fact
         self.components_ = _flip(dict_fact.components_)
         self.coder_ = self._coder_class(dictionary=self.components_, code_alpha=self.alpha, code_l1_ratio=0).fit()
+        if masker is not None:                                       # components_img_ of the reference
+            self.components_img_ = unmask(self.components_, masker.maps_)
         return self
 
     def _cleaned(self, records, confounds):
         return _cleaned_records(self.coder_, records, confounds, self.detrend, self.standardize, self.low_pass,
-                                self.high_pass, self.t_r)
+                                self.high_pass, self.t_r, getattr(self, 'masker_', None))
 
     def transform(self, records, confounds=None):
         """Loadings of each record on the learned maps (fmri.py:131-164); the records are cleaned first with the
@@ -276,16 +363,16 @@ class fMRIDictFact(BaseEstimator):
         return np.sum(scores * lens) / np.sum(lens)
 
 
-def _cleaned_records(coder, records, confounds, detrend, standardize, low_pass=None, high_pass=None, t_r=None):
+def _cleaned_records(coder, records, confounds, detrend, standardize, low_pass=None, high_pass=None, t_r=None,
+                     masker=None):
     """the records as the coder takes them: untouched host arrays when nothing is cleaned, otherwise staged on the coder's
-    device in its dtype and cleaned there"""
+    device in its dtype and cleaned there; a 4-D record is smoothed and masked first (`masker`)"""
     confounds = _check_confounds(confounds, records)
     out = []
     for rec, conf in zip(records, confounds):
-        arr = np.asarray(_load(rec))
+        arr = _mask_record(np.asarray(_load(rec)), masker, coder._backend)
         if _cleans(detrend, standardize, conf, low_pass, high_pass):
-            be = coder._backend
-            arr = _clean_staged(be.stage_X(np.ascontiguousarray(arr, dtype=be.dtype)), detrend, standardize, conf,
+            arr = _clean_staged(_staged_2d(arr, coder._backend), detrend, standardize, conf,
                                 low_pass=low_pass, high_pass=high_pass, t_r=t_r)
         out.append(arr)
     return out
@@ -298,13 +385,19 @@ class fMRICoder(BaseEstimator):
     the constructor is the reference's.  `dictionary`: (n_components, n_voxels) array, or a .npy path.
     `standardize`, `detrend` (False / False as in the reference, fmri.py:375-376) and the `confounds` of transform / score:
     the records are cleaned on the device before they are coded (modl_amd.signal.clean); `low_pass`, `high_pass`, `t_r`
-    (None as in the reference, fmri.py:375-395): its zero-phase Butterworth filter, as for fMRIDictFact."""
+    (None as in the reference, fmri.py:375-395): its zero-phase Butterworth filter, as for fMRIDictFact.
+    `mask`, `smoothing_fwhm`, `voxel_size` as for fMRIDictFact: with a mask a record may be a 4-D volume, `dictionary` may
+    be (X, Y, Z, k), and `components_img_` holds the maps as a volume."""
 
     _coder_class = Coder
 
     def __init__(self, dictionary, alpha=0.1, transform_batch_size=None, n_components=None, n_jobs=1, verbose=0,
-                 standardize=False, detrend=False, low_pass=None, high_pass=None, t_r=None):
+                 standardize=False, detrend=False, low_pass=None, high_pass=None, t_r=None, mask=None,
+                 smoothing_fwhm=None, voxel_size=None):
         self.dictionary = dictionary
+        self.mask = mask
+        self.smoothing_fwhm = smoothing_fwhm
+        self.voxel_size = voxel_size
         self.low_pass = low_pass
         self.high_pass = high_pass
         self.t_r = t_r
@@ -319,7 +412,11 @@ class fMRICoder(BaseEstimator):
     def fit(self, records=None, y=None):
         """fmri.py:76-93: the maps are `dictionary` (its first n_components rows, _check_dict_init :405-420); nothing is
         learned.  Returns self (the reference's mixin returns None: a slip, sklearn's contract kept here)."""
+        masker = self.masker_ = _make_masker(self.mask, self.smoothing_fwhm, self.voxel_size)
         D = np.asarray(_load(self.dictionary))
+        if masker is not None and D.ndim == 4:
+            _record_shape(D, masker)
+            D = D[masker.maps_.mask].T
         if D.ndim != 2:
             raise ValueError('dictionary must be (n_components, n_voxels), got shape %s' % (D.shape,))
         if self.n_components is not None:
@@ -328,18 +425,21 @@ class fMRICoder(BaseEstimator):
             D = D.astype(np.float64)
         self.components_ = np.ascontiguousarray(D)
         self.coder_ = self._coder_class(dictionary=self.components_, code_alpha=self.alpha, code_l1_ratio=0).fit()
+        if masker is not None:
+            self.components_img_ = unmask(self.components_, masker.maps_)
         return self
 
     def _records(self, records):
-        if isinstance(records, str) or (isinstance(records, np.ndarray) and records.ndim == 2):
+        if isinstance(records, str) or (isinstance(records, np.ndarray) and records.ndim in (2, 4)):
             records = [records]                                      # one record (fmri.py:117, :150)
         return records
 
     def _rows(self, record, confounds=None):
-        X = np.asarray(_load(record))
+        X = _mask_record(np.asarray(_load(record)), self.masker_, self.coder_._backend)
         if X.shape[1] != self.components_.shape[1]:
             raise ValueError('record has %d voxels, the maps have %d' % (X.shape[1], self.components_.shape[1]))
-        X = np.ascontiguousarray(X, dtype=self.components_.dtype)
+        if not isinstance(X, torch.Tensor):
+            X = np.ascontiguousarray(X, dtype=self.components_.dtype)
         if _cleans(self.detrend, self.standardize, confounds, self.low_pass, self.high_pass):
             X = _clean_staged(self.coder_._backend.stage_X(X), self.detrend, self.standardize, confounds,
                               low_pass=self.low_pass, high_pass=self.high_pass, t_r=self.t_r)
@@ -409,7 +509,7 @@ class rfMRIDictionaryScorer:
         detrend, standardize = bool(getattr(masker, 'detrend', False)), bool(getattr(masker, 'standardize', False))
         self.data = []
         for rec, conf in zip(self.test_records, _check_confounds(self.test_confounds, self.test_records)):
-            data = be.stage_X(np.ascontiguousarray(np.asarray(_load(rec)), dtype=be.dtype))
+            data = _staged_2d(_mask_record(np.asarray(_load(rec)), getattr(masker, 'masker_', None), be), be)
             cleaned = _clean_staged(data, detrend, standardize, conf, low_pass=getattr(masker, 'low_pass', None),
                                     high_pass=getattr(masker, 'high_pass', None), t_r=getattr(masker, 't_r', None))
             self.data.append(data if cleaned is None else cleaned)

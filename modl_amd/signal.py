@@ -28,8 +28,10 @@ This is the order of current nilearn (signals and confounds filtered alike, then
 unfiltered confounds before filtering.  nilearn is not installed where this was written, so nothing is pinned to a run of
 it: the steps are judged against scipy (tests/test_filter.py).  Without a filter nothing changes, bit for bit.
 
-Not implemented (arguments of nilearn.signal.clean that need more than this): `smoothing_fwhm` (needs the 3-D volume,
-i.e. the masker), `sessions` (clean each session with a call of its own) and `standardize='psc'`."""
+`smoothing_fwhm` needs the 3-D volume and so belongs to the masker: modl_amd/masker.py (`smooth_mask`, `ArrayMasker`,
+DESIGN.md section 23) smooths and masks a 4-D volume on the device before this cleaning.
+Not implemented (arguments of nilearn.signal.clean that need more than this): `sessions` (clean each session with a call
+of its own) and `standardize='psc'`."""
 import functools
 
 import numpy as np
