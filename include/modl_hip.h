@@ -927,6 +927,56 @@ int modl_unmask_f32(const float *d_rows, int64_t ldr, int64_t n, int64_t V, cons
 int modl_unmask_f64(const double *d_rows, int64_t ldr, int64_t n, int64_t V, const int64_t *d_vox, int64_t n0, int64_t n1,
                     int64_t n2, double *d_out, void *stream);
 
+/* Resampling of a volume onto another grid (csrc/resample.hip; the masker's first step: nilearn's
+ * resample_img, i.e. per frame scipy.ndimage.affine_transform(frame, A, offset=b, output_shape, order, mode='constant',
+ * cval=fill)).  d_vol as for modl_smooth_mask: T frames of a box [n0][n1][n2], n2 fastest, frame_stride >= n0 n1 n2.
+ * A (9 doubles, row-major) and b (3 doubles) are HOST arrays IN THIS AXIS ORDER: the locus o = (o0, o1, o2) of the target
+ * box [m0][m1][m2] reads the source at x_a = b_a + sum_j A[a][j] o_j, formed in f64 with scipy's bits.  (A caller whose
+ * arrays are (X, Y, Z) hands over the reversed box, P A P and P b, P the reversal of the axes.)
+ *   - non-finite source elements count as 0;
+ *   - a locus with any x_a < 0 or x_a > n_a - 1 receives `fill`;
+ *   - order 0: the element at floor(x + 0.5), bit for bit;
+ *   - order 1: taps floor(x), floor(x) + 1 per axis, weights 1 - t and t;
+ *   - order 3: the frame is replaced by its cubic B-spline coefficients first (modl_spline_prefilter: scipy's
+ *     spline_filter(order=3, mode='mirror'), separable, state in f64, one rounding to the dtype per axis), then four taps
+ *     per axis at floor(x) - 1 .. floor(x) + 2 with the cubic B-spline weights of t;
+ *   - tap indices outside 0 .. n - 1 are mirrored (d c b | a b c d | c b a);
+ *   - A exactly the identity and b integer: the shifted crop, through the order-0 path whatever `order` says.
+ * The taps are summed along n2, then n1, then n0, in f64 for both dtypes, and rounded once.
+ * Box mode (d_vox NULL; V is not looked at): d_out holds T frames [m0][m1][m2] with the frame stride ldo >= m0 m1 m2.
+ * Rows mode: d_vox (int64[V], device) lists loci as flat indices with AXIS 0 FASTEST, (o2 m1 + o1) m0 + o0 - the C index
+ * in the caller's reversed box, the list that modl_unmask takes; locus c goes to d_out[dst(t)][c], ldo >= V; an index
+ * outside the box is skipped.  The value of a locus is the same bits in both modes.  d_dst_row as for modl_smooth_mask.
+ * d_order (int64[V], device, may be NULL; rows mode only): thread i of the launch takes column d_order[i] (an entry outside
+ * 0 .. V-1 is skipped; the CALLER checks that it is a permutation).  It changes no bit of the result, only which loci a
+ * wavefront works on together: with the columns sorted by (o0, o1, o2) - np.argsort of the loci's flat indices with axis
+ * 2 fastest - neighbouring threads read neighbouring source elements, as they do in box mode.
+ * Order 3 needs d_ws of modl_resample_workspace(dtype, T, n0, n1, n2, 3) bytes: the coefficients and the f64 values of
+ * the causal walk, T n0 n1 n2 (sizeof(dtype) + 8) bytes (the caller bounds it by calling with chunks of frames); orders
+ * 0 and 1 need none, the function returns 0 for them and for bad arguments.  Asynchronous on `stream`, no atomics.
+ * MODL_EINVAL before any device work: a NULL d_vol / A / b / d_out, T or an extent < 1, a box above INT32_MAX elements,
+ * a non-finite A, b or fill, an order other than 0, 1, 3, V < 1 or V > m0 m1 m2 or ldo < V (rows), ldo < m0 m1 m2 (box),
+ * frame_stride < n0 n1 n2, any overlap of d_vol, d_out and d_ws.  Order 3 with d_ws NULL or ws_bytes too small:
+ * MODL_ENOMEM; no device: MODL_ENOGPU.
+ * modl_spline_prefilter: the coefficients alone, into d_coef with its own frame stride coef_stride >= n0 n1 n2; d_ws as
+ * for order 3.  modl_resample_lds_line(): the longest n2 whose lines the prefilter stages in LDS (longer ones are walked
+ * in global memory); modl_resample_frames(): the frames one thread of the gather takes, its grid has ceil(T / that) rows. */
+int modl_resample_lds_line(void);
+int modl_resample_frames(void);
+size_t modl_resample_workspace(int dtype, int64_t T, int64_t n0, int64_t n1, int64_t n2, int order);
+int modl_spline_prefilter_f32(const float *d_vol, int64_t frame_stride, int64_t T, int64_t n0, int64_t n1, int64_t n2,
+                              float *d_coef, int64_t coef_stride, void *d_ws, size_t ws_bytes, void *stream);
+int modl_spline_prefilter_f64(const double *d_vol, int64_t frame_stride, int64_t T, int64_t n0, int64_t n1, int64_t n2,
+                              double *d_coef, int64_t coef_stride, void *d_ws, size_t ws_bytes, void *stream);
+int modl_resample_f32(const float *d_vol, int64_t frame_stride, int64_t T, int64_t n0, int64_t n1, int64_t n2, const double *A,
+                      const double *b, int order, double fill, int64_t m0, int64_t m1, int64_t m2, const int64_t *d_vox, int64_t V,
+                      const int64_t *d_order, const int64_t *d_dst_row, float *d_out, int64_t ldo, void *d_ws, size_t ws_bytes,
+                      void *stream);
+int modl_resample_f64(const double *d_vol, int64_t frame_stride, int64_t T, int64_t n0, int64_t n1, int64_t n2, const double *A,
+                      const double *b, int order, double fill, int64_t m0, int64_t m1, int64_t m2, const int64_t *d_vox, int64_t V,
+                      const int64_t *d_order, const int64_t *d_dst_row, double *d_out, int64_t ldo, void *d_ws, size_t ws_bytes,
+                      void *stream);
+
 /* Amari discrepancy between dictionaries (modl/decomposition/stability.py:7-31: amari_discrepency,
  * mean_amari_discrepency).  For the n dictionaries h_d_dicts[i] (device, row-major k_i x p, atoms in rows), every pair
  * a < b in the reference's generator order (a outer, b inner) gets

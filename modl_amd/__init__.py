@@ -6,7 +6,8 @@ from .stability import amari_discrepency, mean_amari_discrepency  # noqa: F401
 from .image import grid_origins, grid_patches, reconstruct_from_patches  # noqa: F401
 from .signal import clean, cleaning_basis, butterworth  # noqa: F401
 from .masker import ArrayMasker, smooth_mask, unmask, gaussian_weights  # noqa: F401
+from .masker import resample, resample_mask, resample_host, voxel_size_of  # noqa: F401
 
 __all__ = ['DictFact', 'Coder', 'SparseCodes', 'amari_discrepency', 'mean_amari_discrepency', 'grid_origins', 'grid_patches',
            'reconstruct_from_patches', 'clean', 'cleaning_basis', 'butterworth', 'ArrayMasker', 'smooth_mask', 'unmask',
-           'gaussian_weights']
+           'gaussian_weights', 'resample', 'resample_mask', 'resample_host', 'voxel_size_of']

@@ -188,6 +188,12 @@ def bind(lib):
         _sig('modl_smooth_mask_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int,
              _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp)
         _sig('modl_unmask_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp)
+        _sig('modl_spline_prefilter_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _sz, _vp)
+        _sig('modl_resample_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, C.c_int, C.c_double, _i64, _i64,
+             _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _sz, _vp)
+    _sig('modl_resample_lds_line', C.c_int)
+    _sig('modl_resample_frames', C.c_int)
+    _sig('modl_resample_workspace', _sz, C.c_int, _i64, _i64, _i64, _i64, C.c_int)
     _sig('modl_smooth_max_radius', C.c_int)
     _sig('modl_smooth_tile', C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp)
     _sig('modl_smooth_mask_workspace', _sz, C.c_int, _i64, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int)

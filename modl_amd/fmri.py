@@ -22,7 +22,13 @@ Smoothing and masking.  The masker's order is smooth the 4-D volume, apply the m
 `smoothing_fwhm`, `voxel_size`) a record may be a 4-D array (X, Y, Z, T) or the path of a .npy file holding one: the
 staged volume is smoothed and masked on the device by one launch (modl_amd/masker.py, csrc/masker.hip, DESIGN.md section
 23) and then cleaned as above; the learned maps go back to a volume as `components_img_`.  Reading NIfTI files stays out
-of scope."""
+of scope.
+
+Resampling.  The masker's very first step puts a record onto the mask's grid.  With `mask_affine` (the mask's 4 x 4
+voxel-to-world matrix) fit / transform / score take `affines`, the matrix of every 4-D record: a record on another grid
+is resampled on the device first (cubic spline; csrc/resample.hip) - straight into the masked rows
+when nothing is smoothed, into the mask's box when there is smoothing.  `dict_init` / `dictionary` may be a pair
+(maps (x, y, z, k), affine) on any grid, e.g. an atlas: resampled into rows, never smoothed."""
 import time
 from concurrent.futures import ThreadPoolExecutor
 from math import sqrt
@@ -60,6 +66,17 @@ def _check_confounds(confounds, records):
     return list(confounds)
 
 
+def _check_affines(affines, records):
+    """one 4 x 4 matrix (or None) per record: None, one matrix for all records, or a list with one entry per record"""
+    if affines is None:
+        return [None] * len(records)
+    if isinstance(affines, (np.ndarray, torch.Tensor)) and affines.ndim == 2:
+        return [affines] * len(records)
+    if isinstance(affines, str) or len(affines) != len(records):
+        raise ValueError('affines must be one 4 x 4 matrix or a list with one entry (None or a matrix) per record')
+    return list(affines)
+
+
 def _cleans(detrend, standardize, confounds, low_pass, high_pass):
     """is there anything to clean"""
     return bool(detrend or standardize or confounds is not None or low_pass is not None or high_pass is not None)
@@ -81,14 +98,37 @@ def _clean_staged(data, detrend, standardize, confounds, permutation=None, basis
     return torch.from_numpy(out) if was_tensor else out
 
 
-def _make_masker(mask, smoothing_fwhm, voxel_size):
-    """the fitted ArrayMasker of an estimator's masking arguments (it only smooths and masks; the estimator cleans), None
-    without a mask"""
+def _make_masker(mask, smoothing_fwhm, voxel_size, mask_affine=None):
+    """the fitted ArrayMasker of an estimator's masking arguments (it only resamples, smooths and masks; the estimator
+    cleans), None without a mask"""
     if mask is None:
         if smoothing_fwhm is not None:
             raise ValueError('smoothing_fwhm = %r needs the volume: pass `mask` and 4-D records' % (smoothing_fwhm,))
+        if mask_affine is not None:
+            raise ValueError('mask_affine was given without `mask`')
         return None
-    return ArrayMasker(mask, voxel_size=(1, 1, 1) if voxel_size is None else voxel_size, smoothing_fwhm=smoothing_fwhm).fit()
+    return ArrayMasker(mask, voxel_size=(1, 1, 1) if voxel_size is None else voxel_size, smoothing_fwhm=smoothing_fwhm,
+                       mask_affine=mask_affine).fit()
+
+
+def _is_atlas_pair(maps):
+    """(maps (x, y, z, k), affine (4, 4)): maps on a grid of their own"""
+    return (isinstance(maps, (tuple, list)) and len(maps) == 2 and np.ndim(maps[0]) == 4
+            and np.shape(maps[1]) == (4, 4))
+
+
+def _masked_maps(maps, masker):
+    """`dict_init` / `dictionary` as (k, V) rows: 2-D rows as they are; a volume (x, y, z, k) masked, never smoothed; a pair
+    (volume, affine) resampled onto the mask's grid first ('continuous', straight into the rows)"""
+    if _is_atlas_pair(maps):
+        if masker is None:
+            raise ValueError('maps given as (volume, affine) need the `mask` and `mask_affine` arguments')
+        return np.ascontiguousarray(masker.mask_maps(np.asarray(_load(maps[0])), affine=maps[1]))
+    maps = np.asarray(_load(maps))
+    if masker is not None and maps.ndim == 4:
+        _record_shape(maps, masker)
+        maps = maps[masker.maps_.mask].T
+    return maps
 
 
 def _record_shape(arr, masker):
@@ -104,9 +144,10 @@ def _fortran(arr):
     return arr.ndim == 4 and arr.flags.f_contiguous and not arr.flags.c_contiguous
 
 
-def _mask_record(arr, masker, be):
-    """A loaded record as time points x voxels: a 2-D record as it is; a 4-D volume smoothed and masked by `masker` - on
-    the backend's device, where the result stays, or through smooth_mask's own dispatch on a backend without a GPU."""
+def _mask_record(arr, masker, be, affine=None):
+    """A loaded record as time points x voxels: a 2-D record as it is; a 4-D volume (resampled with its `affine`,) smoothed
+    and masked by `masker` - on the backend's device, where the result stays, or through the masker's own dispatch on a
+    backend without a GPU."""
     if arr.ndim != 4:
         return arr
     _record_shape(arr, masker)
@@ -114,8 +155,8 @@ def _mask_record(arr, masker, be):
     if device is not None and device.type == 'cuda':
         fortran = _fortran(arr)                                      # (its transpose is C-ordered: uploaded as it lies)
         t = torch.from_numpy(np.ascontiguousarray(arr.T if fortran else arr, dtype=be.dtype)).to(device)
-        return masker.mask_volume(t.permute(3, 2, 1, 0) if fortran else t)
-    return masker.mask_volume(np.asarray(arr, dtype=be.dtype))
+        return masker.mask_volume(t.permute(3, 2, 1, 0) if fortran else t, affine=affine)
+    return masker.mask_volume(np.asarray(arr, dtype=be.dtype), affine=affine)
 
 
 def _staged_2d(arr, be):
@@ -209,7 +250,13 @@ class fMRIDictFact(BaseEstimator):
     taken as masked AND smoothed already, so `smoothing_fwhm` does not touch them (ArrayMasker.transform raises for such
     an input; here the MultiRawMasker contract wins).  All three None (the default): nothing changes.  `smoothing_fwhm`
     without `mask` is a ValueError.  `dict_init` may also be the path of a .npy file.  `fit` sets `masker_`, the fitted
-    ArrayMasker that smooths and masks (None without a mask)."""
+    ArrayMasker that smooths and masks (None without a mask).
+    `mask_affine` (None): the mask's 4 x 4 voxel-to-world matrix.  With it `fit`, `transform` and `score` take `affines`
+    (one matrix for all 4-D records, or one per record; None: the record lies on the mask's grid): a record whose affine is
+    not allclose to `mask_affine`, or whose shape is not the mask's, is resampled onto the mask's grid on the device
+    before everything else (modl_amd.masker.resample, 'continuous'); `voxel_size` left at None is then read off
+    `mask_affine`; and `dict_init` may be a pair (maps (x, y, z, k), affine) on a grid of its own - an atlas - which is
+    resampled straight into the mask's rows and never smoothed.  `affines` left at None: nothing changes."""
 
     _dict_fact_class = DictFact
     _coder_class = Coder
@@ -217,9 +264,10 @@ class fMRIDictFact(BaseEstimator):
     def __init__(self, method='masked', step_size=1, n_components=20, n_epochs=1, alpha=0.1, dict_init=None,
                  random_state=None, batch_size=20, reduction=1, learning_rate=1, positive=False, verbose=0,
                  callback=None, n_jobs=1, intended_schedules=False, standardize=False, detrend=False, low_pass=None,
-                 high_pass=None, t_r=None, mask=None, smoothing_fwhm=None, voxel_size=None):
+                 high_pass=None, t_r=None, mask=None, smoothing_fwhm=None, voxel_size=None, mask_affine=None):
         self.intended_schedules = intended_schedules
         self.mask = mask
+        self.mask_affine = mask_affine
         self.smoothing_fwhm = smoothing_fwhm
         self.voxel_size = voxel_size
         self.low_pass = low_pass
@@ -242,22 +290,22 @@ class fMRIDictFact(BaseEstimator):
         self.callback = callback
         self.n_jobs = n_jobs
 
-    def fit(self, records, y=None, confounds=None):
+    def fit(self, records, y=None, confounds=None, affines=None):
         """records: list of 2-D arrays / .npy paths.  fmri.py:423-546.  confounds: None, or a list with one entry per
         record (None, a (time points, c) array, or the path of a .npy / .csv file).  With `standardize`, `detrend` or
         confounds the staged record is cleaned on the device and its rows are written in the epoch's permuted order by
-        the same launch; the draws of `random_state` are those of a fit without cleaning."""
+        the same launch; the draws of `random_state` are those of a fit without cleaning.
+        affines: None, one 4 x 4 voxel-to-world matrix for all 4-D records or one per record (None: on the mask's grid);
+        a record on another grid than the mask (`mask_affine`) is resampled onto it on the device first."""
         if records is None:
             raise ValueError('records is None, use Coder instead')
         confounds = _check_confounds(confounds, records)
-        masker = self.masker_ = _make_masker(self.mask, self.smoothing_fwhm, self.voxel_size)
+        affines = _check_affines(affines, records)
+        masker = self.masker_ = _make_masker(self.mask, self.smoothing_fwhm, self.voxel_size, self.mask_affine)
         n_components = self.n_components
         dict_init = self.dict_init
         if dict_init is not None:                                    # fmri.py:415-416, 468-469
-            dict_init = np.asarray(_load(dict_init))
-            if masker is not None and dict_init.ndim == 4:           # maps given as a volume: masked, never smoothed
-                _record_shape(dict_init, masker)
-                dict_init = np.ascontiguousarray(dict_init[masker.maps_.mask].T)
+            dict_init = np.ascontiguousarray(_masked_maps(dict_init, masker))    # a volume: masked, never smoothed
             dict_init = dict_init[:n_components]
             n_components = dict_init.shape[0]
         random_state = check_random_state(self.random_state)
@@ -327,7 +375,7 @@ class fMRIDictFact(BaseEstimator):
                     if data.ndim == 4:                               # smooth and mask the staged volume where it is
                         fold = bases[record] is None                 # nothing to clean: this launch permutes the rows
                         data = masker.mask_volume(data, dst_row=_destination_rows(permutation, len(permutation))
-                                                  if fold else None)
+                                                  if fold else None, affine=affines[record])
                         if fold:
                             rows = data
                     if rows is None:
@@ -346,31 +394,31 @@ class fMRIDictFact(BaseEstimator):
             self.components_img_ = unmask(self.components_, masker.maps_)
         return self
 
-    def _cleaned(self, records, confounds):
+    def _cleaned(self, records, confounds, affines=None):
         return _cleaned_records(self.coder_, records, confounds, self.detrend, self.standardize, self.low_pass,
-                                self.high_pass, self.t_r, getattr(self, 'masker_', None))
+                                self.high_pass, self.t_r, getattr(self, 'masker_', None), affines)
 
-    def transform(self, records, confounds=None):
+    def transform(self, records, confounds=None, affines=None):
         """Loadings of each record on the learned maps (fmri.py:131-164); the records are cleaned first with the
-        estimator's `standardize` / `detrend` and their `confounds` (one entry per record)."""
-        return [self.coder_.transform(a) for a in self._cleaned(records, confounds)]
+        estimator's `standardize` / `detrend` and their `confounds` (one entry per record); `affines` as for `fit`."""
+        return [self.coder_.transform(a) for a in self._cleaned(records, confounds, affines)]
 
-    def score(self, records, confounds=None):
+    def score(self, records, confounds=None, affines=None):
         """Length-weighted mean objective (fmri.py:95-129), of the records cleaned as in `transform`."""
-        arrays = self._cleaned(records, confounds)
+        arrays = self._cleaned(records, confounds, affines)
         scores = np.array([self.coder_.score(a) for a in arrays])
         lens = np.array([a.shape[0] for a in arrays])
         return np.sum(scores * lens) / np.sum(lens)
 
 
 def _cleaned_records(coder, records, confounds, detrend, standardize, low_pass=None, high_pass=None, t_r=None,
-                     masker=None):
+                     masker=None, affines=None):
     """the records as the coder takes them: untouched host arrays when nothing is cleaned, otherwise staged on the coder's
-    device in its dtype and cleaned there; a 4-D record is smoothed and masked first (`masker`)"""
+    device in its dtype and cleaned there; a 4-D record is (resampled,) smoothed and masked first (`masker`)"""
     confounds = _check_confounds(confounds, records)
     out = []
-    for rec, conf in zip(records, confounds):
-        arr = _mask_record(np.asarray(_load(rec)), masker, coder._backend)
+    for rec, conf, aff in zip(records, confounds, _check_affines(affines, records)):
+        arr = _mask_record(np.asarray(_load(rec)), masker, coder._backend, aff)
         if _cleans(detrend, standardize, conf, low_pass, high_pass):
             arr = _clean_staged(_staged_2d(arr, coder._backend), detrend, standardize, conf,
                                 low_pass=low_pass, high_pass=high_pass, t_r=t_r)
@@ -386,16 +434,18 @@ class fMRICoder(BaseEstimator):
     `standardize`, `detrend` (False / False as in the reference, fmri.py:375-376) and the `confounds` of transform / score:
     the records are cleaned on the device before they are coded (modl_amd.signal.clean); `low_pass`, `high_pass`, `t_r`
     (None as in the reference, fmri.py:375-395): its zero-phase Butterworth filter, as for fMRIDictFact.
-    `mask`, `smoothing_fwhm`, `voxel_size` as for fMRIDictFact: with a mask a record may be a 4-D volume, `dictionary` may
-    be (X, Y, Z, k), and `components_img_` holds the maps as a volume."""
+    `mask`, `smoothing_fwhm`, `voxel_size`, `mask_affine` as for fMRIDictFact: with a mask a record may be a 4-D volume,
+    `dictionary` may be (X, Y, Z, k) or a pair (maps, affine) on another grid, `components_img_` holds the maps as a
+    volume, and transform / score take the `affines` of the records."""
 
     _coder_class = Coder
 
     def __init__(self, dictionary, alpha=0.1, transform_batch_size=None, n_components=None, n_jobs=1, verbose=0,
                  standardize=False, detrend=False, low_pass=None, high_pass=None, t_r=None, mask=None,
-                 smoothing_fwhm=None, voxel_size=None):
+                 smoothing_fwhm=None, voxel_size=None, mask_affine=None):
         self.dictionary = dictionary
         self.mask = mask
+        self.mask_affine = mask_affine
         self.smoothing_fwhm = smoothing_fwhm
         self.voxel_size = voxel_size
         self.low_pass = low_pass
@@ -412,11 +462,8 @@ class fMRICoder(BaseEstimator):
     def fit(self, records=None, y=None):
         """fmri.py:76-93: the maps are `dictionary` (its first n_components rows, _check_dict_init :405-420); nothing is
         learned.  Returns self (the reference's mixin returns None: a slip, sklearn's contract kept here)."""
-        masker = self.masker_ = _make_masker(self.mask, self.smoothing_fwhm, self.voxel_size)
-        D = np.asarray(_load(self.dictionary))
-        if masker is not None and D.ndim == 4:
-            _record_shape(D, masker)
-            D = D[masker.maps_.mask].T
+        masker = self.masker_ = _make_masker(self.mask, self.smoothing_fwhm, self.voxel_size, self.mask_affine)
+        D = _masked_maps(self.dictionary, masker)
         if D.ndim != 2:
             raise ValueError('dictionary must be (n_components, n_voxels), got shape %s' % (D.shape,))
         if self.n_components is not None:
@@ -434,8 +481,8 @@ class fMRICoder(BaseEstimator):
             records = [records]                                      # one record (fmri.py:117, :150)
         return records
 
-    def _rows(self, record, confounds=None):
-        X = _mask_record(np.asarray(_load(record)), self.masker_, self.coder_._backend)
+    def _rows(self, record, confounds=None, affine=None):
+        X = _mask_record(np.asarray(_load(record)), self.masker_, self.coder_._backend, affine)
         if X.shape[1] != self.components_.shape[1]:
             raise ValueError('record has %d voxels, the maps have %d' % (X.shape[1], self.components_.shape[1]))
         if not isinstance(X, torch.Tensor):
@@ -451,28 +498,30 @@ class fMRICoder(BaseEstimator):
             confounds = [confounds]                                  # one record, its confounds as they are
         return _check_confounds(confounds, records)
 
-    def transform(self, records, confounds=None):
+    def transform(self, records, confounds=None, affines=None):
         """Loadings of each record, one (n_samples, n_components) array per record (fmri.py:131-164).  A record is
         coded in slices of transform_batch_size rows when that is set (the codes of a row do not depend on the others).
-        `confounds`: one entry per record, regressed out of it (with `standardize` / `detrend`) before it is coded."""
+        `confounds`: one entry per record, regressed out of it (with `standardize` / `detrend`) before it is coded.
+        `affines`: one 4 x 4 matrix for all 4-D records or one per record, as for fMRIDictFact.fit."""
         if not hasattr(self, 'coder_'):
             raise ValueError('fMRICoder is not fitted: call fit() first')
         out = []
         records = self._records(records)
-        for rec, conf in zip(records, self._confounds(confounds, records)):
-            X = self._rows(rec, conf)
+        for rec, conf, aff in zip(records, self._confounds(confounds, records), _check_affines(affines, records)):
+            X = self._rows(rec, conf, aff)
             step = self.transform_batch_size or X.shape[0] or 1
             parts = [self.coder_.transform(X[a:a + step]) for a in range(0, X.shape[0], step)]
             out.append(np.concatenate(parts) if parts else np.zeros((0, self.components_.shape[0]), dtype=X.dtype))
         return out
 
-    def score(self, records, confounds=None):
+    def score(self, records, confounds=None, affines=None):
         """Length-weighted mean of the objective over the records (fmri.py:95-129), cleaned as in `transform`; lower is a
         better fit."""
         if not hasattr(self, 'coder_'):
             raise ValueError('fMRICoder is not fitted: call fit() first')
         records = self._records(records)
-        arrays = [self._rows(r, c) for r, c in zip(records, self._confounds(confounds, records))]
+        arrays = [self._rows(r, c, a) for r, c, a in zip(records, self._confounds(confounds, records),
+                                                         _check_affines(affines, records))]
         scores = np.array([self.coder_.score(a) for a in arrays])
         lens = np.array([a.shape[0] for a in arrays])
         return float(np.sum(scores * lens) / np.sum(lens))
@@ -487,14 +536,16 @@ class rfMRIDictionaryScorer:
     link again; three doubles per record come back.  Signature of the reference: `scorer(masker, dict_fact,
     cpu_time, io_time)`; the first argument (the masker there, the fMRIDictFact here) plays the masker's part: its
     `standardize` / `detrend`, `low_pass` / `high_pass` / `t_r` and `test_confounds` (one entry per test record) say how the test records are cleaned -
-    once, on the device, when they are staged (modl_amd.signal.clean).
+    once, on the device, when they are staged (modl_amd.signal.clean).  `test_affines`: the affines of 4-D test records
+    (one for all, or one per record), resampled onto the mask's grid as in `fMRIDictFact.fit`.
     `artifact_dir`: `info.pkl` as in the reference (:621-625) and the flipped maps as `components_<n_iter>.npy`
     (the reference writes a NIfTI image through the masker, which is out of scope)."""
 
-    def __init__(self, test_records, test_confounds=None, info=None, artifact_dir=None):
+    def __init__(self, test_records, test_confounds=None, info=None, artifact_dir=None, test_affines=None):
         self.start_time = time.perf_counter()
         self.test_records = test_records
         self.test_confounds = test_confounds             # one entry per test record (None, array or path), or None
+        self.test_affines = test_affines                 # one 4 x 4 matrix for all test records, one per record, or None
         self.test_time = 0
         self.score = []
         self.iter = []
@@ -508,8 +559,9 @@ class rfMRIDictionaryScorer:
         be = dict_fact._backend
         detrend, standardize = bool(getattr(masker, 'detrend', False)), bool(getattr(masker, 'standardize', False))
         self.data = []
-        for rec, conf in zip(self.test_records, _check_confounds(self.test_confounds, self.test_records)):
-            data = _staged_2d(_mask_record(np.asarray(_load(rec)), getattr(masker, 'masker_', None), be), be)
+        for rec, conf, aff in zip(self.test_records, _check_confounds(self.test_confounds, self.test_records),
+                                  _check_affines(self.test_affines, self.test_records)):
+            data = _staged_2d(_mask_record(np.asarray(_load(rec)), getattr(masker, 'masker_', None), be, aff), be)
             cleaned = _clean_staged(data, detrend, standardize, conf, low_pass=getattr(masker, 'low_pass', None),
                                     high_pass=getattr(masker, 'high_pass', None), t_r=getattr(masker, 't_r', None))
             self.data.append(data if cleaned is None else cleaned)

@@ -17,8 +17,19 @@ The smoothing sees the whole volume, so voxels outside the mask bleed in.  On th
 works on frames (T, Z, Y, X) - the bytes of a Fortran-ordered (X, Y, Z, T) array, nibabel's layout, which is handed over
 as it is; a C-ordered volume is permuted to that layout on the device first, so both give the same bits.
 
-nilearn is not installed where this was written: the steps are judged against scipy (tests/test_masker.py).
-Out of scope: computing a mask, resampling, NIfTI reading and writing, fwhm='fast'."""
+Resampling (csrc/resample.hip) precedes all of this when a volume lies on another grid than the
+mask: `resample`, `resample_mask`, and the `affine` argument of ArrayMasker.  With `affine` the source's 4 x 4 voxel-to-world
+matrix and `target_affine` / `target_shape` the target grid, A = inv(affine)[:3, :3] @ target_affine[:3, :3] and
+b = inv(affine)[:3, :3] @ target_affine[:3, 3] + inv(affine)[:3, 3] are formed in f64 on the host, the target voxel o reads
+the source at x = A o + b, and every frame is scipy.ndimage.affine_transform(frame, A, offset=b, output_shape=target_shape,
+order=ORDER, mode='constant', cval=fill_value), ORDER = 3 / 1 / 0 for interpolation = 'continuous' / 'linear' / 'nearest' -
+the arithmetic of nilearn's resample_img.  Non-finite source elements count as 0 before anything else: that is this
+library's rule (step 1 above), NOT nilearn's, which extrapolates around them.  When A is exactly the identity and b is
+exactly integer the result is the shifted crop of the source, bit for bit, whatever the interpolation (nilearn's shortcut).
+
+nilearn is not installed where this was written: the steps are judged against scipy (tests/test_masker.py,
+tests/test_resample.py).
+Out of scope: computing a mask, NIfTI reading and writing, fwhm='fast', resampling with `clip` or a non-numeric fill."""
 import numpy as np
 import scipy.ndimage
 import torch
@@ -29,8 +40,11 @@ from .signal import clean
 
 SMOOTH_MAX_RADIUS = lib.modl_smooth_max_radius()           # 8: fwhm 8 mm at 2 mm voxels, 6 mm at 1.5 mm
 _FWHM_TO_SIGMA = float(np.sqrt(8.0 * np.log(2.0)))
+RESAMPLE_WORKSPACE_BYTES = 1 << 28                          # order 3: frames are resampled in chunks within this workspace
+_ORDERS = {'continuous': 3, 'linear': 1, 'nearest': 0}
 
-__all__ = ['smooth_mask', 'unmask', 'gaussian_weights', 'smooth_mask_host', 'unmask_host', 'ArrayMasker']
+__all__ = ['smooth_mask', 'unmask', 'gaussian_weights', 'smooth_mask_host', 'unmask_host', 'ArrayMasker', 'resample',
+           'resample_mask', 'resample_host', 'voxel_size_of']
 
 
 def gaussian_weights(sigma):
@@ -107,6 +121,17 @@ class _Maps:
         self.col = np.ascontiguousarray(col.transpose(2, 1, 0))
         self.vox = np.flatnonzero(self.mask.ravel()).astype(np.int64)
         self._dev = {}
+        self._order = {}
+
+    def order_on(self, device):
+        """(V,) int64 on `device`: the columns sorted by their voxel's place in a (Z, Y, X) frame - the order in which the
+        resampling kernel walks the mask's loci, so that a wavefront reads neighbouring source elements"""
+        key = str(device)
+        if key not in self._order:
+            x, y, z = np.unravel_index(self.vox, self.mask.shape)
+            frame_index = (z * self.mask.shape[1] + y) * self.mask.shape[0] + x
+            self._order[key] = torch.from_numpy(np.argsort(frame_index, kind='stable').astype(np.int64)).to(device)
+        return self._order[key]
 
     def on(self, device):
         key = str(device)
@@ -129,7 +154,7 @@ def _check_volume(volume, maps):
         vol = vol[..., None]
     if vol.ndim != 4 or vol.shape[3] < 1:
         raise ValueError('volume must be (X, Y, Z, T) or (X, Y, Z), got shape %s' % (tuple(volume.shape),))
-    if tuple(vol.shape[:3]) != maps.mask.shape:
+    if maps is not None and tuple(vol.shape[:3]) != maps.mask.shape:
         raise ValueError('the volume has spatial shape %s, the mask %s' % (tuple(vol.shape[:3]), maps.mask.shape))
     if cuda:
         if vol.dtype not in (torch.float32, torch.float64):
@@ -294,6 +319,191 @@ def unmask(rows, mask):
     return _unmask_device(torch.from_numpy(np.ascontiguousarray(r)).to(device), maps).cpu().numpy()
 
 
+def _check_affine(affine, name):
+    """the 4 x 4 voxel-to-world matrix as f64.  ValueError naming `name`: a wrong shape, a non-finite entry, a last row
+    that is not (0, 0, 0, 1), a singular 3 x 3 part."""
+    if isinstance(affine, torch.Tensor):
+        affine = affine.detach().cpu().numpy()
+    try:
+        a = np.asarray(affine, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a 4 x 4 matrix, got %r' % (name, affine))
+    if a.shape != (4, 4):
+        raise ValueError('%s must be a 4 x 4 matrix, got shape %s' % (name, a.shape))
+    if not np.all(np.isfinite(a)):
+        raise ValueError('%s has non-finite entries: %r' % (name, a.tolist()))
+    if not np.array_equal(a[3], [0.0, 0.0, 0.0, 1.0]):
+        raise ValueError('%s must have the last row (0, 0, 0, 1), got %r' % (name, a[3].tolist()))
+    if np.linalg.matrix_rank(a[:3, :3]) < 3:
+        raise ValueError('%s is singular: %r' % (name, a[:3, :3].tolist()))
+    return a
+
+
+def voxel_size_of(affine):
+    """(vx, vy, vz) in mm of a 4 x 4 voxel-to-world matrix: sqrt((affine[:3, :3] ** 2).sum(0)), nilearn's rule"""
+    a = _check_affine(affine, 'affine')
+    return tuple(float(v) for v in np.sqrt((a[:3, :3] ** 2).sum(axis=0)))
+
+
+def _grid_transform(affine, target_affine, target_name='target_affine'):
+    """(A, b) of the module docstring, f64, in the axis order x, y, z"""
+    inv = np.linalg.inv(_check_affine(affine, 'affine'))
+    ta = _check_affine(target_affine, target_name)
+    return inv[:3, :3] @ ta[:3, :3], inv[:3, :3] @ ta[:3, 3] + inv[:3, 3]
+
+
+def _check_grid(target_shape, interpolation, fill_value):
+    try:
+        shape = tuple(int(n) for n in target_shape)
+        bad = len(shape) != 3 or any(n < 1 for n in shape) or any(n != m for n, m in zip(shape, target_shape))
+    except (TypeError, ValueError):
+        bad = True
+    if bad:
+        raise ValueError('target_shape must be three positive integers, got %r' % (target_shape,))
+    if not isinstance(interpolation, str) or interpolation not in _ORDERS:
+        raise ValueError("interpolation must be 'continuous', 'linear' or 'nearest', got %r" % (interpolation,))
+    if isinstance(fill_value, (str, bytes)) or np.ndim(fill_value) != 0 or not np.isfinite(float(fill_value)):
+        raise ValueError('fill_value must be a finite number, got %r' % (fill_value,))
+    return shape, _ORDERS[interpolation], float(fill_value)
+
+
+def _is_shift(A, b):
+    return bool(np.array_equal(A, np.eye(3)) and np.array_equal(b, np.floor(b)))
+
+
+def _resample_host(vol, A, b, shape, order, fill):
+    """(X, Y, Z, T) numpy -> (X', Y', Z', T), Fortran-ordered, through scipy: what the kernels are judged against"""
+    arr = np.where(np.isfinite(vol), vol, 0).astype(vol.dtype, copy=False)
+    if _is_shift(A, b):
+        order = 0
+    out = np.empty(shape + (vol.shape[3],), dtype=vol.dtype, order='F')
+    for t in range(vol.shape[3]):
+        out[..., t] = scipy.ndimage.affine_transform(arr[..., t], A, offset=b, output_shape=shape, output=vol.dtype,
+                                                     order=order, mode='constant', cval=fill)
+    return out
+
+
+def _rows_host(box, maps, dst):
+    rows = np.ascontiguousarray(box[maps.mask].T)
+    if dst is None:
+        return rows
+    out = np.empty_like(rows)
+    out[dst] = rows
+    return out
+
+
+def _resample_device(frames, A, b, shape, order, fill, maps=None, dst=None):
+    """frames: contiguous CUDA tensor (T, Z, Y, X).  Box mode (maps None): (T, Z', Y', X'); rows mode: (T, V).  At order 3 the
+    frames go through in chunks whose workspace stays within RESAMPLE_WORKSPACE_BYTES (one frame at least)."""
+    from .device import ptr, stream_ptr
+    T, n0, n1, n2 = frames.shape
+    m0, m1, m2 = shape[2], shape[1], shape[0]
+    sx = 'f32' if frames.dtype == torch.float32 else 'f64'
+    dt = 0 if sx == 'f32' else 1
+    if _is_shift(A, b):
+        order = 0
+    Ak = np.ascontiguousarray(A[::-1, ::-1], dtype=np.float64)           # P A P and P b: the kernel's axes are z, y, x
+    bk = np.ascontiguousarray(b[::-1], dtype=np.float64)
+    box = n0 * n1 * n2
+    chunk = T
+    if order == 3:
+        per_frame = lib.modl_resample_workspace(dt, 1, n0, n1, n2, 3)
+        if per_frame == 0:
+            raise ValueError('modl_resample: unsupported shape %s' % (tuple(frames.shape),))
+        chunk = max(1, min(T, RESAMPLE_WORKSPACE_BYTES // per_frame))
+    fn = getattr(lib, 'modl_resample_' + sx)
+    with torch.cuda.device(frames.device):
+        if maps is None:
+            out = torch.empty((T, m0, m1, m2), dtype=frames.dtype, device=frames.device)
+            d_vox, d_order, V, ldo = None, None, 0, m0 * m1 * m2
+        else:
+            _, d_vox = maps.on(frames.device)
+            d_order = maps.order_on(frames.device) if order > 0 else None        # (order 0: one read per store, no gain)
+            V = ldo = maps.n_voxels
+            out = torch.empty((T, V), dtype=frames.dtype, device=frames.device)
+        fold = dst is not None and chunk >= T                            # one call: the kernel permutes the rows itself
+        d_dst = None if dst is None else torch.from_numpy(dst).to(frames.device)
+        target = out if dst is None or fold else torch.empty_like(out)
+        ws = None
+        for t0 in range(0, T, chunk):
+            n = min(chunk, T - t0)
+            need = lib.modl_resample_workspace(dt, n, n0, n1, n2, order)
+            if need and (ws is None or ws.numel() < need):
+                ws = torch.empty(need, dtype=torch.uint8, device=frames.device)
+            check(fn(ptr(frames[t0:t0 + n]), box, n, n0, n1, n2, Ak.ctypes.data, bk.ctypes.data, order, fill, m0, m1, m2,
+                     ptr(d_vox), V, ptr(d_order), ptr(d_dst) if fold else None, ptr(target[t0:t0 + n]), ldo, ptr(ws), need,
+                     stream_ptr(frames.device)), 'modl_resample')
+        if target is not out:
+            out[d_dst] = target
+    return out
+
+
+def _resample(vol, A, b, shape, order, fill, maps=None, dst=None):
+    """vol: what _check_volume returned.  Box mode: (X', Y', Z', T); rows mode (maps given): (T, V)."""
+    def finish(res):
+        return res if maps is not None else res.permute(3, 2, 1, 0)
+
+    if isinstance(vol, torch.Tensor):
+        return finish(_resample_device(_to_frames(vol), A, b, shape, order, fill, maps, dst))
+    if lib.modl_device_count() <= 0:
+        res = _resample_host(vol, A, b, shape, order, fill)
+        return res if maps is None else _rows_host(res, maps, dst)
+    return finish(_resample_device(_to_frames(_upload(vol)), A, b, shape, order, fill, maps, dst)).cpu().numpy()
+
+
+def _upload(vol):
+    """numpy (X, Y, Z, T) -> CUDA tensor of that shape on the current device; a Fortran-ordered volume keeps its bytes (its
+    frames (T, Z, Y, X) are then a view)"""
+    device = torch.device('cuda', torch.cuda.current_device())
+    if vol.flags.f_contiguous:
+        return torch.from_numpy(vol.T).to(device).permute(3, 2, 1, 0)
+    return torch.from_numpy(np.ascontiguousarray(vol)).to(device)
+
+
+def resample_host(volume, affine, target_affine, target_shape, interpolation='continuous', fill_value=0):
+    """`resample` through scipy.ndimage.affine_transform on the host, same semantics (the spline arithmetic in f64, one
+    rounding to the volume's dtype): what `resample` runs without a GPU, and the CPU baseline of
+    scripts/bench_resample.py.  The result is Fortran-ordered."""
+    if isinstance(volume, torch.Tensor):
+        raise ValueError('resample_host takes a numpy array')
+    shape, order, fill = _check_grid(target_shape, interpolation, fill_value)
+    A, b = _grid_transform(affine, target_affine)
+    return _resample_host(_check_volume(volume, None), A, b, shape, order, fill)
+
+
+def resample(volume, affine, target_affine, target_shape, interpolation='continuous', fill_value=0):
+    """Resample a volume onto another grid (module docstring) on the device: (X', Y', Z', T).
+
+    volume          (X, Y, Z, T) or (X, Y, Z), float32 or float64 (anything else is converted to float64): a numpy array
+                    (a numpy array comes back) or a CUDA tensor (a CUDA tensor comes back, a view with the frame axis last
+                    of a frame-major array).  A C-ordered and a Fortran-ordered volume give the same bits.
+    affine          4 x 4, voxel to world, of the volume
+    target_affine   4 x 4 of the target grid; target_shape its (X', Y', Z')
+    interpolation   'continuous' (cubic spline), 'linear' or 'nearest'
+    fill_value      what a target voxel outside the source box 0 <= x_a <= n_a - 1 receives
+
+    Non-finite elements of the volume count as 0 - this library's rule, not nilearn's (module docstring).
+    'continuous' keeps the spline coefficients of the frames in flight in a workspace of (itemsize + 8) bytes per source
+    element: the frames go through in chunks so that it stays within RESAMPLE_WORKSPACE_BYTES = 256 MiB (one frame at
+    least).  Without a GPU a numpy input goes through `resample_host`.
+    ValueError, naming the offender: an affine that is not 4 x 4, not finite, without the last row (0, 0, 0, 1) or
+    singular, a bad target_shape, interpolation or fill_value."""
+    shape, order, fill = _check_grid(target_shape, interpolation, fill_value)
+    A, b = _grid_transform(affine, target_affine)
+    return _resample(_check_volume(volume, None), A, b, shape, order, fill)
+
+
+def resample_mask(volume, affine, mask, mask_affine, interpolation='continuous', dst_row=None):
+    """Resample a volume onto a mask's grid and keep the mask's voxels: (T, V), column c being the c-th true voxel of `mask`
+    in C order - `resample(volume, affine, mask_affine, mask.shape, interpolation)[mask].T` to the bit, but the target
+    volume is never formed: only the V masked loci are gathered.  `dst_row` as for `smooth_mask`; fill value 0."""
+    maps = _maps(mask)
+    shape, order, fill = _check_grid(maps.mask.shape, interpolation, 0)
+    A, b = _grid_transform(affine, mask_affine, 'mask_affine')
+    vol = _check_volume(volume, None)
+    return _resample(vol, A, b, shape, order, fill, maps, _check_dst(dst_row, vol.shape[3]))
+
+
 class ArrayMasker(BaseEstimator):
     """The reference's masker on arrays: smooth, mask, clean - and back.
 
@@ -305,11 +515,20 @@ class ArrayMasker(BaseEstimator):
     fit() builds the column map and the voxel list of the mask and the Gaussian weights once (`n_voxels_`).  transform(volume, confounds=None):
     (T, V), smoothed and masked by one launch, then cleaned.  A 2-D (T, V) input is taken as already masked and is only
     cleaned (the reference's MultiRawMasker contract); with `smoothing_fwhm` set that is a ValueError, since nothing can
-    be smoothed any more.  inverse_transform(rows): (X, Y, Z, n)."""
+    be smoothed any more.  inverse_transform(rows): (X, Y, Z, n).
+
+    mask_affine     None, or the mask's 4 x 4 voxel-to-world matrix.  With it, `transform` and `mask_volume` take the
+                    `affine` of the volume: when that is allclose to `mask_affine` and the volume has the mask's shape the
+                    volume is on the mask's grid and takes the path above, bit for bit; otherwise it is resampled onto the
+                    mask's grid first ('continuous', fill 0; module docstring) - into the mask's box and then smoothed when
+                    there is smoothing, straight into the (T, V) rows (no target volume) when there is none.  With
+                    `voxel_size` left at (1, 1, 1) or None the voxel size is `voxel_size_of(mask_affine)` (`voxel_size_`).
+                    An `affine` without `mask_affine`, or a singular one, is a ValueError."""
 
     def __init__(self, mask, voxel_size=(1, 1, 1), smoothing_fwhm=None, standardize=False, detrend=False, low_pass=None,
-                 high_pass=None, t_r=None):
+                 high_pass=None, t_r=None, mask_affine=None):
         self.mask = mask
+        self.mask_affine = mask_affine
         self.voxel_size = voxel_size
         self.smoothing_fwhm = smoothing_fwhm
         self.standardize = standardize
@@ -320,10 +539,38 @@ class ArrayMasker(BaseEstimator):
 
     def fit(self, X=None, y=None):
         self.maps_ = _Maps(self.mask)
-        self.sigmas_ = _sigmas(self.smoothing_fwhm, self.voxel_size)         # (the arguments are checked here)
-        self.weights_ = _weights(self.smoothing_fwhm, self.voxel_size)       # built once, used by every transform
+        self.mask_affine_ = None if self.mask_affine is None else _check_affine(self.mask_affine, 'mask_affine')
+        voxel_size = (1, 1, 1) if self.voxel_size is None else self.voxel_size
+        if self.mask_affine_ is not None and np.array_equal(np.asarray(voxel_size, dtype=object), (1, 1, 1)):
+            voxel_size = voxel_size_of(self.mask_affine_)                    # (left at its default: the affine says it)
+        self.voxel_size_ = voxel_size
+        self.sigmas_ = _sigmas(self.smoothing_fwhm, voxel_size)              # (the arguments are checked here)
+        self.weights_ = _weights(self.smoothing_fwhm, voxel_size)            # built once, used by every transform
         self.n_voxels_ = self.maps_.n_voxels
         return self
+
+    def _other_grid(self, volume, affine):
+        """None when the volume lies on the mask's grid, else (A, b) of the resampling onto it"""
+        if affine is None:
+            return None
+        if self.mask_affine_ is None:
+            raise ValueError('affine = %r was given, but the masker has no mask_affine to resample onto'
+                             % (np.asarray(affine).tolist(),))
+        a = _check_affine(affine, 'affine')
+        if tuple(volume.shape[:3]) == self.maps_.mask.shape and np.allclose(a, self.mask_affine_):
+            return None
+        return _grid_transform(a, self.mask_affine_, 'mask_affine')
+
+    def mask_maps(self, volume, affine=None):
+        """maps given as a volume (X, Y, Z, k), e.g. an atlas: masked, NEVER smoothed: (k, V).  On another grid (`affine`)
+        they are resampled ('continuous') straight into the rows."""
+        maps = self._fitted()
+        if not isinstance(volume, torch.Tensor):
+            volume = np.asarray(volume)
+        grid = self._other_grid(volume, affine) if volume.ndim in (3, 4) else None
+        if grid is None:
+            return _smooth_mask(volume, maps, [(np.ones(1), 0)] * 3, (0.0, 0.0, 0.0), None)
+        return _resample(_check_volume(volume, None), grid[0], grid[1], maps.mask.shape, 3, 0.0, maps, None)
 
     def _fitted(self):
         if not hasattr(self, 'maps_'):
@@ -333,8 +580,8 @@ class ArrayMasker(BaseEstimator):
     def _smooths(self):
         return any(r > 0 for _, r in self.weights_)
 
-    def mask_volume(self, volume, dst_row=None):
-        """the smoothing and masking alone: (T, V); a 2-D input passes as it is"""
+    def mask_volume(self, volume, dst_row=None, affine=None):
+        """the (resampling,) smoothing and masking alone: (T, V); a 2-D input passes as it is"""
         maps = self._fitted()
         if not isinstance(volume, torch.Tensor):
             volume = np.asarray(volume)
@@ -349,10 +596,19 @@ class ArrayMasker(BaseEstimator):
             inv = np.empty(len(dst_row), dtype=np.int64)
             inv[np.asarray(dst_row)] = np.arange(len(dst_row))
             return volume[torch.from_numpy(inv).to(volume.device) if isinstance(volume, torch.Tensor) else inv]
-        return _smooth_mask(volume, maps, self.weights_, self.sigmas_, dst_row)
+        grid = self._other_grid(volume, affine) if volume.ndim in (3, 4) else None
+        if grid is None:
+            return _smooth_mask(volume, maps, self.weights_, self.sigmas_, dst_row)
+        vol = _check_volume(volume, None)
+        if self._smooths():                                                  # into the mask's box, then the launch of before
+            if not isinstance(vol, torch.Tensor) and lib.modl_device_count() > 0:
+                return self.mask_volume(_upload(vol), dst_row, affine).cpu().numpy()     # (one upload for both steps)
+            return _smooth_mask(_resample(vol, grid[0], grid[1], maps.mask.shape, 3, 0.0), maps, self.weights_, self.sigmas_,
+                                dst_row)
+        return _resample(vol, grid[0], grid[1], maps.mask.shape, 3, 0.0, maps, _check_dst(dst_row, vol.shape[3]))
 
-    def transform(self, volume, confounds=None):
-        rows = self.mask_volume(volume)
+    def transform(self, volume, confounds=None, affine=None):
+        rows = self.mask_volume(volume, affine=affine)
         if not (self.detrend or self.standardize or confounds is not None or self.low_pass is not None
                 or self.high_pass is not None):
             return rows
