@@ -927,6 +927,57 @@ int modl_unmask_f32(const float *d_rows, int64_t ldr, int64_t n, int64_t V, cons
 int modl_unmask_f64(const double *d_rows, int64_t ldr, int64_t n, int64_t V, const int64_t *d_vox, int64_t n0, int64_t n1,
                     int64_t n2, double *d_out, void *stream);
 
+/* Computing a mask (csrc/compute_mask.hip): the steps of nilearn's compute_epi_mask /
+ * compute_background_mask that touch every voxel.  A mask on the device is uint8[n0][n1][n2], n2 fastest (the frame order
+ * (Z, Y, X) of modl_smooth_mask); any nonzero byte reads as true, the calls write 0 or 1.  n0 n1 n2 <= INT32_MAX.
+ * All calls are asynchronous on `stream`; argument checks return MODL_EINVAL before any device work; a NULL or short
+ * workspace is MODL_ENOMEM; no device: MODL_ENOGPU.  Workspace and outputs are written only where the call says.
+ *
+ * modl_frame_mean: d_mean[v] = (sum over t of d_frames[t * ld_frame + v]) / T for v < n.  The sum runs in f64 in ascending
+ * t inside one thread, the division is in f64, the result is rounded once to the dtype; plain IEEE, so NaN and inf
+ * propagate; with zero_nonfinite = 1 a non-finite RESULT (after the rounding) is stored as 0.  One thread owns 8 bytes
+ * of neighbouring voxels (two f32, one f64) and loads them with one instruction per frame, 512 contiguous bytes per
+ * wavefront, whatever the alignment of d_frames and ld_frame (frames of an odd box start anywhere); a last single f32
+ * voxel loads on its own.  No atomics, no workspace.
+ * MODL_EINVAL: a NULL pointer, T / n < 1, ld_frame < n, zero_nonfinite not 0 / 1, a pointer that is not aligned to an
+ * element, any overlap of d_frames and d_mean. */
+int modl_frame_mean_f32(const float *d_frames, int64_t ld_frame, int64_t T, int64_t n, int zero_nonfinite, float *d_mean,
+                        void *stream);
+int modl_frame_mean_f64(const double *d_frames, int64_t ld_frame, int64_t T, int64_t n, int zero_nonfinite, double *d_mean,
+                        void *stream);
+/* scipy.ndimage.binary_erosion (dilate = 0) / binary_dilation (dilate = 1) with the default cross structure,
+ * border_value = 0 and `iterations` >= 1 passes: a voxel survives erosion iff every locus within L1 distance `iterations`
+ * lies inside the box and is true, it is set by dilation iff a true voxel lies within that distance.  One launch per
+ * pass, alternating between d_ws and d_out; passes that can change nothing any more (erosion past (shortest axis + 1) / 2,
+ * dilation past n0 + n1 + n2) are not launched, so any `iterations` is legal.  d_in is not written.
+ * d_ws: modl_morph_workspace(n0, n1, n2, iterations) bytes (0 for bad arguments).
+ * MODL_EINVAL: a NULL d_in / d_out, an extent < 1, a box above INT32_MAX, iterations < 1, dilate not 0 / 1, any overlap of
+ * d_in, d_out and d_ws (d_out aliasing d_in included). */
+size_t modl_morph_workspace(int64_t n0, int64_t n1, int64_t n2, int64_t iterations);
+int modl_binary_morph(const uint8_t *d_in, int64_t n0, int64_t n1, int64_t n2, int64_t iterations, int dilate, uint8_t *d_out,
+                      void *d_ws, size_t ws_bytes, void *stream);
+/* 6-connected components (scipy.ndimage.label with the default structure) by union-find in global memory: labels within
+ * tiles of modl_label_tile() voxels in LDS, a merge across the tile faces (atomicMin links, agent-scope atomic reads, no
+ * workgroup waits for another), a flattening pass.  Every loop descends a chain of strictly decreasing indices, so it is
+ * bounded by the box.  d_root (int32[n0][n1][n2]): for a true voxel THE SMALLEST FLAT MEMORY INDEX (i0 n1 + i1) n2 + i2 OF
+ * ITS COMPONENT - the same for exactly the voxels of one component; -1 for a false voxel.  The result depends on the
+ * mask alone.
+ * modl_largest_component: d_out = the component with the most voxels; among components of equal size the one whose first
+ * voxel comes first in the C order of the caller's (X, Y, Z) = (n2, n1, n0) array, index (i2 n1 + i1) n0 + i0 - that is
+ * labels == np.bincount(labels.ravel())[1:].argmax() + 1 of scipy's labels of the (X, Y, Z) array.  d_info (int64[3], device):
+ * the number of components, the winner's size, the winner's first voxel as that C index.  No true voxel: zeros in d_info,
+ * an all-false d_out, MODL_OK.  Sizes are counted with one integer add per wavefront and distinct root; all atomics are
+ * integer min / max / add, so the bits do not depend on the order of arrival.
+ * d_ws: modl_label_workspace(n0, n1, n2) bytes for both calls (0 for bad arguments).
+ * MODL_EINVAL: a NULL pointer, an extent < 1, a box above INT32_MAX, n0 or n1 above 65535 tiles, any overlap of the
+ * arrays. */
+int modl_label_tile(int *tile);
+size_t modl_label_workspace(int64_t n0, int64_t n1, int64_t n2);
+int modl_label_components(const uint8_t *d_mask, int64_t n0, int64_t n1, int64_t n2, int32_t *d_root, void *d_ws, size_t ws_bytes,
+                          void *stream);
+int modl_largest_component(const uint8_t *d_mask, int64_t n0, int64_t n1, int64_t n2, uint8_t *d_out, int64_t *d_info, void *d_ws,
+                           size_t ws_bytes, void *stream);
+
 /* Resampling of a volume onto another grid (csrc/resample.hip; the masker's first step: nilearn's
  * resample_img, i.e. per frame scipy.ndimage.affine_transform(frame, A, offset=b, output_shape, order, mode='constant',
  * cval=fill)).  d_vol as for modl_smooth_mask: T frames of a box [n0][n1][n2], n2 fastest, frame_stride >= n0 n1 n2.

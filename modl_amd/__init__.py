@@ -7,7 +7,11 @@ from .image import grid_origins, grid_patches, reconstruct_from_patches  # noqa:
 from .signal import clean, cleaning_basis, butterworth  # noqa: F401
 from .masker import ArrayMasker, smooth_mask, unmask, gaussian_weights  # noqa: F401
 from .masker import resample, resample_mask, resample_host, voxel_size_of  # noqa: F401
+from .masker import (compute_epi_mask, compute_background_mask, compute_multi_epi_mask,  # noqa: F401
+                     compute_multi_background_mask, intersect_masks, largest_connected_component)
 
 __all__ = ['DictFact', 'Coder', 'SparseCodes', 'amari_discrepency', 'mean_amari_discrepency', 'grid_origins', 'grid_patches',
            'reconstruct_from_patches', 'clean', 'cleaning_basis', 'butterworth', 'ArrayMasker', 'smooth_mask', 'unmask',
-           'gaussian_weights', 'resample', 'resample_mask', 'resample_host', 'voxel_size_of']
+           'gaussian_weights', 'resample', 'resample_mask', 'resample_host', 'voxel_size_of', 'compute_epi_mask',
+           'compute_background_mask', 'compute_multi_epi_mask', 'compute_multi_background_mask', 'intersect_masks',
+           'largest_connected_component']

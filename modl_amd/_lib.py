@@ -191,6 +191,13 @@ def bind(lib):
         _sig('modl_spline_prefilter_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _sz, _vp)
         _sig('modl_resample_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, C.c_int, C.c_double, _i64, _i64,
              _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _sz, _vp)
+        _sig('modl_frame_mean_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp)
+    _sig('modl_morph_workspace', _sz, _i64, _i64, _i64, _i64)
+    _sig('modl_binary_morph', C.c_int, _vp, _i64, _i64, _i64, _i64, C.c_int, _vp, _vp, _sz, _vp)
+    _sig('modl_label_tile', C.c_int, _vp)
+    _sig('modl_label_workspace', _sz, _i64, _i64, _i64)
+    _sig('modl_label_components', C.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp)
+    _sig('modl_largest_component', C.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp)
     _sig('modl_resample_lds_line', C.c_int)
     _sig('modl_resample_frames', C.c_int)
     _sig('modl_resample_workspace', _sz, C.c_int, _i64, _i64, _i64, _i64, C.c_int)

@@ -21,8 +21,9 @@ too (csrc/filtfilt.hip).
 Smoothing and masking.  The masker's order is smooth the 4-D volume, apply the mask, clean.  With `mask` (and
 `smoothing_fwhm`, `voxel_size`) a record may be a 4-D array (X, Y, Z, T) or the path of a .npy file holding one: the
 staged volume is smoothed and masked on the device by one launch (modl_amd/masker.py, csrc/masker.hip, DESIGN.md section
-23) and then cleaned as above; the learned maps go back to a volume as `components_img_`.  Reading NIfTI files stays out
-of scope.
+23) and then cleaned as above; the learned maps go back to a volume as `components_img_`.  The mask itself may be computed
+from the records (`mask='background'` / `'epi'`, csrc/compute_mask.hip).  Reading NIfTI files stays
+out of scope.
 
 Resampling.  The masker's very first step puts a record onto the mask's grid.  With `mask_affine` (the mask's 4 x 4
 voxel-to-world matrix) fit / transform / score take `affines`, the matrix of every 4-D record: a record on another grid
@@ -41,7 +42,7 @@ from sklearn.utils import check_random_state
 
 from .device import gather_rows
 from .dict_fact import DictFact, Coder
-from .masker import ArrayMasker, unmask
+from .masker import ArrayMasker, unmask, compute_strategy_mask, _check_strategy
 from .signal import clean, clean_host, cleaning_basis, _destination_rows
 
 METHODS = {'masked': {'G_agg': 'masked', 'Dx_agg': 'masked'},           # fmri.py:440-445
@@ -101,6 +102,9 @@ def _clean_staged(data, detrend, standardize, confounds, permutation=None, basis
 def _make_masker(mask, smoothing_fwhm, voxel_size, mask_affine=None):
     """the fitted ArrayMasker of an estimator's masking arguments (it only resamples, smooths and masks; the estimator
     cleans), None without a mask"""
+    if isinstance(mask, str):
+        raise ValueError('mask = %r is a strategy that only fMRIDictFact.fit computes; pass the mask the estimator computed: '
+                         '`est.mask_`' % (mask,))
     if mask is None:
         if smoothing_fwhm is not None:
             raise ValueError('smoothing_fwhm = %r needs the volume: pass `mask` and 4-D records' % (smoothing_fwhm,))
@@ -109,6 +113,16 @@ def _make_masker(mask, smoothing_fwhm, voxel_size, mask_affine=None):
         return None
     return ArrayMasker(mask, voxel_size=(1, 1, 1) if voxel_size is None else voxel_size, smoothing_fwhm=smoothing_fwhm,
                        mask_affine=mask_affine).fit()
+
+
+def _strategy_volumes(records):
+    """the records of a fit under a mask strategy, loaded one at a time: each must be a 4-D volume"""
+    for i, rec in enumerate(records):
+        arr = np.asarray(_load(rec))
+        if arr.ndim != 4:
+            raise ValueError('record %d has shape %s: a mask is computed from 4-D records (X, Y, Z, T); pass the mask of '
+                             '2-D records as an array' % (i, tuple(arr.shape)))
+        yield arr
 
 
 def _is_atlas_pair(maps):
@@ -256,7 +270,15 @@ class fMRIDictFact(BaseEstimator):
     not allclose to `mask_affine`, or whose shape is not the mask's, is resampled onto the mask's grid on the device
     before everything else (modl_amd.masker.resample, 'continuous'); `voxel_size` left at None is then read off
     `mask_affine`; and `dict_init` may be a pair (maps (x, y, z, k), affine) on a grid of its own - an atlas - which is
-    resampled straight into the mask's rows and never smoothed.  `affines` left at None: nothing changes."""
+    resampled straight into the mask's rows and never smoothed.  `affines` left at None: nothing changes.
+    `mask` may also be the strategy 'background' or 'epi', with `mask_args` (None or a dict of arguments of
+    modl_amd.masker.compute_multi_background_mask / compute_multi_epi_mask): before anything else `fit` then makes one pass
+    over the records - load, upload, temporal mean, per-record mask, running count, all on the device - intersects the
+    masks and goes on with the result as if it had been passed; `mask_` holds it (also for an array mask).  The pass draws
+    nothing from `random_state`.  Every record must then be 4-D and lie on one grid (an affine that is not allclose to
+    `mask_affine` is a ValueError: resample first).  NOTE: in the reference `mask=None` means "compute a mask with
+    mask_strategy"; here None is already taken - it keeps meaning 2-D records and no masker - so computing is asked for by
+    the strategy's name."""
 
     _dict_fact_class = DictFact
     _coder_class = Coder
@@ -264,9 +286,10 @@ class fMRIDictFact(BaseEstimator):
     def __init__(self, method='masked', step_size=1, n_components=20, n_epochs=1, alpha=0.1, dict_init=None,
                  random_state=None, batch_size=20, reduction=1, learning_rate=1, positive=False, verbose=0,
                  callback=None, n_jobs=1, intended_schedules=False, standardize=False, detrend=False, low_pass=None,
-                 high_pass=None, t_r=None, mask=None, smoothing_fwhm=None, voxel_size=None, mask_affine=None):
+                 high_pass=None, t_r=None, mask=None, smoothing_fwhm=None, voxel_size=None, mask_affine=None, mask_args=None):
         self.intended_schedules = intended_schedules
         self.mask = mask
+        self.mask_args = mask_args
         self.mask_affine = mask_affine
         self.smoothing_fwhm = smoothing_fwhm
         self.voxel_size = voxel_size
@@ -301,7 +324,15 @@ class fMRIDictFact(BaseEstimator):
             raise ValueError('records is None, use Coder instead')
         confounds = _check_confounds(confounds, records)
         affines = _check_affines(affines, records)
-        masker = self.masker_ = _make_masker(self.mask, self.smoothing_fwhm, self.voxel_size, self.mask_affine)
+        mask = self.mask
+        if isinstance(mask, str):                                    # one pass over the records, no draw from random_state
+            _check_strategy(mask, self.mask_args)
+            mask = compute_strategy_mask(mask, self.mask_args, _strategy_volumes(records), affines, self.mask_affine)
+        elif self.mask_args is not None:
+            raise ValueError("mask_args = %r goes with mask = 'background' or 'epi'" % (self.mask_args,))
+        masker = self.masker_ = _make_masker(mask, self.smoothing_fwhm, self.voxel_size, self.mask_affine)
+        if masker is not None:
+            self.mask_ = masker.maps_.mask
         n_components = self.n_components
         dict_init = self.dict_init
         if dict_init is not None:                                    # fmri.py:415-416, 468-469

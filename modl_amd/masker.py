@@ -29,7 +29,14 @@ exactly integer the result is the shifted crop of the source, bit for bit, whate
 
 nilearn is not installed where this was written: the steps are judged against scipy (tests/test_masker.py,
 tests/test_resample.py).
-Out of scope: computing a mask, NIfTI reading and writing, fwhm='fast', resampling with `clip` or a non-numeric fill."""
+
+Computing the mask (csrc/compute_mask.hip) is the step before all of this when none is given:
+`compute_epi_mask`, `compute_background_mask`, their `compute_multi_*` forms over several records and `intersect_masks`,
+`largest_connected_component` - the arithmetic of nilearn.masking on arrays, judged against scipy.ndimage (label,
+binary_erosion, binary_dilation); `ArrayMasker(mask='epi' | 'background')` and the fMRI estimators call them.  Every
+function has a `*_host` twin made of numpy and scipy.
+Out of scope: NIfTI reading and writing, fwhm='fast', resampling with `clip` or a non-numeric fill, computing a mask across
+grids (resample first), the 'template' strategies."""
 import numpy as np
 import scipy.ndimage
 import torch
@@ -44,7 +51,10 @@ RESAMPLE_WORKSPACE_BYTES = 1 << 28                          # order 3: frames ar
 _ORDERS = {'continuous': 3, 'linear': 1, 'nearest': 0}
 
 __all__ = ['smooth_mask', 'unmask', 'gaussian_weights', 'smooth_mask_host', 'unmask_host', 'ArrayMasker', 'resample',
-           'resample_mask', 'resample_host', 'voxel_size_of']
+           'resample_mask', 'resample_host', 'voxel_size_of', 'compute_epi_mask', 'compute_background_mask',
+           'compute_multi_epi_mask', 'compute_multi_background_mask', 'intersect_masks', 'largest_connected_component',
+           'compute_epi_mask_host', 'compute_background_mask_host', 'compute_multi_epi_mask_host',
+           'compute_multi_background_mask_host', 'intersect_masks_host', 'largest_connected_component_host']
 
 
 def gaussian_weights(sigma):
@@ -504,10 +514,507 @@ def resample_mask(volume, affine, mask, mask_affine, interpolation='continuous',
     return _resample(vol, A, b, shape, order, fill, maps, _check_dst(dst_row, vol.shape[3]))
 
 
+# ------------------------------------------------------------------------------------------- computing a mask (section 27)
+def _check_post(connected, opening):
+    if isinstance(opening, (str, bytes)) or np.ndim(opening) != 0 or int(opening) != opening or int(opening) < 0:
+        raise ValueError('opening must be False or an integer >= 0, got %r' % (opening,))
+    return bool(connected), int(opening)
+
+
+def _check_cutoffs(lower_cutoff, upper_cutoff):
+    lo, up = float(lower_cutoff), float(upper_cutoff)
+    if not (0 <= lo <= 1 and 0 <= up <= 1 and lo < up):
+        raise ValueError('the cutoffs must satisfy 0 <= lower_cutoff < upper_cutoff <= 1, got lower_cutoff = %r, '
+                         'upper_cutoff = %r' % (lower_cutoff, upper_cutoff))
+    return lo, up
+
+
+def _check_border(border_size):
+    if isinstance(border_size, (bool, np.bool_)) or not isinstance(border_size, (int, np.integer)) or border_size < 1:
+        raise ValueError('border_size must be an integer >= 1, got %r' % (border_size,))
+    return int(border_size)
+
+
+def _check_threshold(threshold):
+    t = float(threshold)
+    if not 0 <= t <= 1:
+        raise ValueError('threshold must lie in [0, 1], got %r' % (threshold,))
+    return t
+
+
+def _cut_indices(lo, up, n):
+    a, b = int(np.floor(lo * n)), min(int(np.floor(up * n)), n - 1)
+    if b <= a:
+        raise ValueError('lower_cutoff = %r and upper_cutoff = %r leave no interval among n = %d sorted values'
+                         % (lo, up, n))
+    return a, b
+
+
+def _warn_empty(empty, what):
+    if empty:
+        import warnings
+        warnings.warn('%s computed an empty mask' % what, UserWarning, stacklevel=3)
+
+
+def _bool_mask_host(mask, name='mask'):
+    if isinstance(mask, torch.Tensor):
+        raise ValueError('the *_host functions take numpy arrays')
+    mask = np.asarray(mask)
+    if mask.ndim != 3 or mask.dtype != np.bool_:
+        raise ValueError('%s must be a 3-D boolean array, got shape %s, dtype %s' % (name, mask.shape, mask.dtype))
+    return mask
+
+
+def largest_connected_component_host(mask):
+    """`largest_connected_component` through scipy.ndimage.label: 6-connectivity, the component with the most voxels, ties
+    to the one whose first voxel comes first in C order.  ValueError: no true voxel."""
+    mask = _bool_mask_host(mask)
+    labels, n = scipy.ndimage.label(mask)
+    if n == 0:
+        raise ValueError('the mask of shape %s has no true voxel: there is no connected component' % (mask.shape,))
+    if n == 1:
+        return mask.copy()
+    return labels == np.bincount(labels.ravel())[1:].argmax() + 1
+
+
+def _post_host(mask, opening, connected):
+    if opening:
+        mask = scipy.ndimage.binary_erosion(mask, iterations=opening)
+    if connected and mask.any():
+        mask = largest_connected_component_host(mask)
+    if opening:
+        mask = scipy.ndimage.binary_dilation(mask, iterations=2 * opening)
+        mask = scipy.ndimage.binary_erosion(mask, iterations=opening)
+    return mask
+
+
+def _mean_host(vol):
+    """contract item 1 on (X, Y, Z, T): the f64 sum over t, the f64 division, one rounding to the dtype"""
+    return (vol.sum(axis=3, dtype=np.float64) / vol.shape[3]).astype(vol.dtype)
+
+
+def _host_volume(volume):
+    if isinstance(volume, torch.Tensor):
+        raise ValueError('the *_host functions take numpy arrays')
+    return _check_volume(volume, None)
+
+
+def _epi_host(vol, lo, up, connected, opening, exclude_zeros):
+    mean = _mean_host(vol)
+    mean[~np.isfinite(mean)] = 0
+    s = np.sort(mean.ravel())
+    if exclude_zeros:
+        s = s[s != 0]
+    a, b = _cut_indices(lo, up, len(s))
+    ia = int(np.argmax(s[a + 1:b + 1] - s[a:b]))
+    threshold = mean.dtype.type(0.5) * (s[ia + a] + s[ia + a + 1])
+    return _post_host(mean >= threshold, opening, connected)
+
+
+def _border_host(d, b):
+    return np.concatenate([x.ravel() for x in (d[:b], d[-b:], d[:, :b], d[:, -b:], d[:, :, :b], d[:, :, -b:])])
+
+
+def _background_host(vol, border_size, connected, opening):
+    mean = _mean_host(vol)
+    border = _border_host(mean, border_size)
+    if np.isnan(border).any():
+        mask = ~np.isnan(mean)
+    else:
+        mask = mean != np.median(border)
+    return _post_host(mask, opening, connected)
+
+
+def compute_epi_mask_host(volume, lower_cutoff=0.2, upper_cutoff=0.85, connected=True, opening=2, exclude_zeros=False):
+    """`compute_epi_mask` composed of numpy and scipy.ndimage: what runs without a GPU, the judge of the kernels and the CPU
+    baseline of scripts/bench_mask.py"""
+    lo, up = _check_cutoffs(lower_cutoff, upper_cutoff)
+    connected, opening = _check_post(connected, opening)
+    mask = _epi_host(_host_volume(volume), lo, up, connected, opening, bool(exclude_zeros))
+    _warn_empty(not mask.any(), 'compute_epi_mask')
+    return mask
+
+
+def compute_background_mask_host(volume, border_size=2, connected=False, opening=False):
+    """`compute_background_mask` composed of numpy and scipy.ndimage (see compute_epi_mask_host)"""
+    border_size = _check_border(border_size)
+    connected, opening = _check_post(connected, opening)
+    mask = _background_host(_host_volume(volume), border_size, connected, opening)
+    _warn_empty(not mask.any(), 'compute_background_mask')
+    return mask
+
+
+def _check_masks(masks, name='masks'):
+    if isinstance(masks, (np.ndarray, torch.Tensor)) or masks is None:
+        raise ValueError('%s must be a list of (X, Y, Z) boolean arrays, got %s' % (name, type(masks).__name__))
+    masks = list(masks)
+    if not masks:
+        raise ValueError('%s is an empty list' % name)
+    return masks
+
+
+def _intersect_count(threshold, n):
+    return min(threshold, 1 - 1e-7) * n
+
+
+def intersect_masks_host(masks, threshold=0.5, connected=True):
+    """`intersect_masks` in numpy (the largest component through scipy)"""
+    threshold = _check_threshold(threshold)
+    masks = [_bool_mask_host(m, 'masks[%d]' % i) for i, m in enumerate(_check_masks(masks))]
+    count = np.zeros(masks[0].shape, dtype=np.int64)
+    for i, m in enumerate(masks):
+        if m.shape != masks[0].shape:
+            raise ValueError('masks[%d] has shape %s, masks[0] %s' % (i, m.shape, masks[0].shape))
+        count += m
+    keep = count > _intersect_count(threshold, len(masks))
+    if connected and keep.any():
+        keep = largest_connected_component_host(keep)
+    return keep
+
+
+def _check_volumes(volumes):
+    if isinstance(volumes, (np.ndarray, torch.Tensor)):
+        return [volumes]
+    if volumes is None or isinstance(volumes, (str, bytes)):
+        raise ValueError('volumes must be a list of (X, Y, Z, T) arrays, got %r' % (volumes,))
+    return volumes
+
+
+def _multi_host(volumes, single, threshold, connected, what):
+    masks, shape = [], None
+    for i, v in enumerate(_check_volumes(volumes)):
+        vol = _host_volume(v)
+        if shape is not None and vol.shape[:3] != shape:
+            raise ValueError('volumes[%d] has spatial shape %s, volumes[0] %s' % (i, vol.shape[:3], shape))
+        shape = vol.shape[:3]
+        masks.append(single(vol))
+    if not masks:
+        raise ValueError('volumes is an empty list')
+    mask = intersect_masks_host(masks, threshold, connected)
+    _warn_empty(not mask.any(), what)
+    return mask
+
+
+def compute_multi_epi_mask_host(volumes, lower_cutoff=0.2, upper_cutoff=0.85, connected=True, opening=2, threshold=0.5,
+                                exclude_zeros=False):
+    """`compute_multi_epi_mask` on the host: compute_epi_mask_host of every volume, then intersect_masks_host"""
+    lo, up = _check_cutoffs(lower_cutoff, upper_cutoff)
+    connected, opening = _check_post(connected, opening)
+    threshold = _check_threshold(threshold)
+    return _multi_host(volumes, lambda v: _epi_host(v, lo, up, connected, opening, bool(exclude_zeros)), threshold, connected,
+                       'compute_multi_epi_mask')
+
+
+def compute_multi_background_mask_host(volumes, border_size=2, connected=True, opening=2, threshold=0.5):
+    """`compute_multi_background_mask` on the host"""
+    border_size = _check_border(border_size)
+    connected, opening = _check_post(connected, opening)
+    threshold = _check_threshold(threshold)
+    return _multi_host(volumes, lambda v: _background_host(v, border_size, connected, opening), threshold, connected,
+                       'compute_multi_background_mask')
+
+
+# ---- the device: masks are uint8 tensors (Z, Y, X), the kernels' frame order
+def _frame_mean_device(frames, zero_nonfinite):
+    """frames: contiguous CUDA tensor (T, Z, Y, X) -> (Z, Y, X), contract item 1 (csrc/compute_mask.hip)"""
+    from .device import ptr, stream_ptr
+    T, n0, n1, n2 = frames.shape
+    box = n0 * n1 * n2
+    with torch.cuda.device(frames.device):
+        mean = torch.empty((n0, n1, n2), dtype=frames.dtype, device=frames.device)
+        check(getattr(lib, 'modl_frame_mean_' + ('f32' if frames.dtype == torch.float32 else 'f64'))(
+            ptr(frames), box, T, box, int(bool(zero_nonfinite)), ptr(mean), stream_ptr(frames.device)), 'modl_frame_mean')
+    return mean
+
+
+def _morph_device(m, iterations, dilate):
+    from .device import ptr, stream_ptr
+    n0, n1, n2 = m.shape
+    need = lib.modl_morph_workspace(n0, n1, n2, iterations)
+    if need == 0:
+        raise ValueError('modl_binary_morph: unsupported box %s, iterations %r' % (tuple(m.shape), iterations))
+    with torch.cuda.device(m.device):
+        out = torch.empty_like(m)
+        ws = torch.empty(need, dtype=torch.uint8, device=m.device)
+        check(lib.modl_binary_morph(ptr(m), n0, n1, n2, iterations, int(dilate), ptr(out), ptr(ws), need, stream_ptr(m.device)),
+              'modl_binary_morph')
+    return out
+
+
+def _largest_device(m):
+    """(the largest component (Z, Y, X) uint8, [components, size, first voxel]) - the three numbers come to the host"""
+    from .device import ptr, stream_ptr
+    n0, n1, n2 = m.shape
+    need = lib.modl_label_workspace(n0, n1, n2)
+    if need == 0:
+        raise ValueError('modl_largest_component: unsupported box %s' % (tuple(m.shape),))
+    with torch.cuda.device(m.device):
+        out = torch.empty_like(m)
+        info = torch.empty(3, dtype=torch.int64, device=m.device)
+        ws = torch.empty(need, dtype=torch.uint8, device=m.device)
+        check(lib.modl_largest_component(ptr(m), n0, n1, n2, ptr(out), ptr(info), ptr(ws), need, stream_ptr(m.device)),
+              'modl_largest_component')
+    return out, info.cpu().tolist()
+
+
+def _post_device(m, opening, connected):
+    if opening:
+        m = _morph_device(m, opening, False)
+    if connected:
+        out, info = _largest_device(m)                                       # (no true voxel: the empty mask stays)
+        if info[0] > 1:
+            m = out
+    if opening:
+        m = _morph_device(_morph_device(m, 2 * opening, True), opening, False)
+    return m
+
+
+def _epi_device(frames, lo, up, connected, opening, exclude_zeros):
+    mean = _frame_mean_device(frames, True)
+    s = torch.sort(mean.reshape(-1)).values
+    if exclude_zeros:
+        s = s[s != 0]
+    a, b = _cut_indices(lo, up, int(s.shape[0]))
+    delta = s[a + 1:b + 1] - s[a:b]
+    ia = int((delta == delta.max()).nonzero()[0, 0])                         # the FIRST argmax
+    pair = s[ia + a:ia + a + 2].cpu().numpy()
+    threshold = pair.dtype.type(0.5) * (pair[0] + pair[1])                   # numpy arithmetic in the dtype
+    return _post_device((mean >= threshold.item()).to(torch.uint8), opening, connected)
+
+
+def _background_device(frames, border_size, connected, opening):
+    mean = _frame_mean_device(frames, False)
+    d, b = mean.permute(2, 1, 0), border_size
+    border = torch.cat([x.reshape(-1) for x in (d[:b], d[-b:], d[:, :b], d[:, -b:], d[:, :, :b], d[:, :, -b:])])
+    if bool(torch.isnan(border).any()):
+        mask = ~torch.isnan(mean)
+    else:
+        s = torch.sort(border).values
+        h = s.shape[0] // 2
+        pair = s[h - 1:h + 1].cpu().numpy()
+        with np.errstate(all='ignore'):
+            median = pair.dtype.type(0.5) * (pair[0] + pair[1])              # np.median: the mean of the two middle values
+        mask = mean != median.item()
+    return _post_device(mask.to(torch.uint8), opening, connected)
+
+
+def _device_frames(volume):
+    """(frames (T, Z, Y, X) on the device, was the input a CUDA tensor) or (the checked numpy volume, None) without a GPU"""
+    vol = _check_volume(volume, None)
+    if isinstance(vol, torch.Tensor):
+        return _to_frames(vol), True
+    if lib.modl_device_count() <= 0:
+        return vol, None
+    return _to_frames(_upload(vol)), False
+
+
+def _mask_out(m, cuda):
+    """a device mask (Z, Y, X) uint8 as the caller's (X, Y, Z) boolean: a CUDA view, or a numpy array"""
+    out = m.to(torch.bool).permute(2, 1, 0)
+    return out if cuda else np.ascontiguousarray(out.cpu().numpy())
+
+
+def _mask_in(mask, name='mask'):
+    """an (X, Y, Z) boolean numpy array or CUDA tensor as (uint8 (Z, Y, X) on the device, was it a CUDA tensor)"""
+    cuda = isinstance(mask, torch.Tensor)
+    if cuda and not mask.is_cuda:
+        raise ValueError('%s must be a numpy array or a CUDA tensor, got a tensor on %s' % (name, mask.device))
+    if not cuda:
+        mask = np.asarray(mask)
+    if mask.ndim != 3 or mask.dtype not in (np.bool_, torch.bool):
+        raise ValueError('%s must be a 3-D boolean array, got shape %s, dtype %s' % (name, tuple(mask.shape), mask.dtype))
+    if not cuda:
+        mask = torch.from_numpy(np.ascontiguousarray(mask)).to(torch.device('cuda', torch.cuda.current_device()))
+    return mask.permute(2, 1, 0).contiguous().to(torch.uint8), cuda
+
+
+def largest_connected_component(mask):
+    """The largest 6-connected component of an (X, Y, Z) boolean mask (scipy.ndimage.label's default structure); among
+    components of equal size the one whose first voxel comes first in C order.  numpy in, numpy out; a CUDA tensor in, a
+    CUDA tensor out.  On the device: union-find labelling, csrc/compute_mask.hip.  Without a GPU:
+    `largest_connected_component_host`.  ValueError: a mask that is not 3-D boolean or has no true voxel."""
+    if not isinstance(mask, torch.Tensor) and lib.modl_device_count() <= 0:
+        return largest_connected_component_host(mask)
+    m, cuda = _mask_in(mask)
+    out, info = _largest_device(m)
+    if info[0] == 0:
+        raise ValueError('the mask of shape %s has no true voxel: there is no connected component' % (tuple(mask.shape),))
+    return _mask_out(out, cuda)
+
+
+def compute_epi_mask(volume, lower_cutoff=0.2, upper_cutoff=0.85, connected=True, opening=2, exclude_zeros=False):
+    """The brain mask of an EPI record, nilearn's compute_epi_mask on an array: (X, Y, Z) boolean.
+
+    The mean over t (f64 sum, rounded once to the dtype), non-finite elements of it set to 0; s = its sorted values (without
+    the zeros if `exclude_zeros`), n = len(s), lo = floor(lower_cutoff n), hi = min(floor(upper_cutoff n), n - 1), ia = the
+    first argmax of s[lo+1:hi+1] - s[lo:hi], threshold = (s[ia+lo] + s[ia+lo+1]) / 2 in the dtype; mean >= threshold, then
+    the post-processing: erosion by `opening` (cross structure, border 0), the largest 6-connected component if `connected`
+    and the mask is not empty, dilation by 2 `opening` and erosion by `opening`.
+    volume: (X, Y, Z, T) or (X, Y, Z), float32 / float64 (anything else is converted to float64), numpy (numpy comes back) or
+    a CUDA tensor (a CUDA tensor comes back, a permuted view); C and Fortran order give the same bits.  The mean, the
+    morphology and the labelling are kernels of csrc/compute_mask.hip; the sort runs on the device, two values of it come to
+    the host.  Without a GPU a numpy input goes through `compute_epi_mask_host`.
+    ValueError naming the offender: cutoffs outside [0, 1] or lower >= upper, hi <= lo, a negative opening.  An empty result
+    comes back with a UserWarning."""
+    lo, up = _check_cutoffs(lower_cutoff, upper_cutoff)
+    connected, opening = _check_post(connected, opening)
+    frames, cuda = _device_frames(volume)
+    if cuda is None:
+        mask = _epi_host(frames, lo, up, connected, opening, bool(exclude_zeros))
+        _warn_empty(not mask.any(), 'compute_epi_mask')
+        return mask
+    m = _epi_device(frames, lo, up, connected, opening, bool(exclude_zeros))
+    _warn_empty(not bool(m.any()), 'compute_epi_mask')
+    return _mask_out(m, cuda)
+
+
+def compute_background_mask(volume, border_size=2, connected=False, opening=False):
+    """The mask of a record whose background is constant (or NaN), nilearn's compute_background_mask on an array.
+
+    The mean over t; border = the `border_size` outermost planes of every face, as numpy slices them (edges and corners
+    count more than once); if it holds a NaN the mask is ~isnan(mean), otherwise mean != np.median(border); then the
+    post-processing of `compute_epi_mask`.  Input, output and dispatch as there.
+    ValueError: border_size that is not an integer >= 1, a negative opening."""
+    border_size = _check_border(border_size)
+    connected, opening = _check_post(connected, opening)
+    frames, cuda = _device_frames(volume)
+    if cuda is None:
+        mask = _background_host(frames, border_size, connected, opening)
+        _warn_empty(not mask.any(), 'compute_background_mask')
+        return mask
+    m = _background_device(frames, border_size, connected, opening)
+    _warn_empty(not bool(m.any()), 'compute_background_mask')
+    return _mask_out(m, cuda)
+
+
+def _intersect_device(masks, threshold, connected):
+    """masks: an iterable of uint8 (Z, Y, X) device tensors; the running count stays on the device"""
+    count, n = None, 0
+    for i, m in enumerate(masks):
+        if count is None:
+            count = torch.zeros(m.shape, dtype=torch.int32, device=m.device)
+        elif m.shape != count.shape:
+            raise ValueError('masks[%d] has shape %s, masks[0] %s' % (i, tuple(m.shape)[::-1], tuple(count.shape)[::-1]))
+        count += m != 0
+        n += 1
+    if count is None:
+        raise ValueError('masks is an empty list')
+    keep = (count.to(torch.float64) > _intersect_count(threshold, n)).to(torch.uint8)
+    if connected:
+        out, info = _largest_device(keep)
+        if info[0] > 1:
+            keep = out
+    return keep
+
+
+def intersect_masks(masks, threshold=0.5, connected=True):
+    """The voxels that are true in more than min(threshold, 1 - 1e-7) len(masks) of the (X, Y, Z) boolean `masks` (threshold 0:
+    the union, 1: the intersection), then the largest component if `connected` and any voxel is kept - nilearn's
+    intersect_masks.  A CUDA tensor comes back if any mask is one.  Without a GPU: `intersect_masks_host`.
+    ValueError: a threshold outside [0, 1], an empty list, shapes that differ."""
+    threshold = _check_threshold(threshold)
+    masks = _check_masks(masks)
+    if lib.modl_device_count() <= 0 and not any(isinstance(m, torch.Tensor) for m in masks):
+        return intersect_masks_host(masks, threshold, connected)
+    pairs = [_mask_in(m, 'masks[%d]' % i) for i, m in enumerate(masks)]
+    return _mask_out(_intersect_device([m for m, _ in pairs], threshold, connected), any(c for _, c in pairs))
+
+
+def _multi(volumes, single_device, single_host, threshold, connected, what):
+    state = {'cuda': False, 'shape': None}
+
+    def masks():
+        for i, v in enumerate(_check_volumes(volumes)):
+            frames, cuda = _device_frames(v)
+            shape = tuple(frames.shape[:3]) if cuda is None else tuple(frames.shape[1:])[::-1]
+            if state['shape'] is not None and shape != state['shape']:
+                raise ValueError('volumes[%d] has spatial shape %s, volumes[0] %s' % (i, shape, state['shape']))
+            state['shape'] = shape
+            state['cuda'] = state['cuda'] or bool(cuda)
+            yield single_host(frames) if cuda is None else single_device(frames)
+
+    if lib.modl_device_count() <= 0:
+        found = list(masks())
+        if not found:
+            raise ValueError('volumes is an empty list')
+        mask = intersect_masks_host(found, threshold, connected)
+        _warn_empty(not mask.any(), what)
+        return mask
+    try:
+        m = _intersect_device(masks(), threshold, connected)
+    except ValueError as e:
+        if str(e) == 'masks is an empty list':
+            raise ValueError('volumes is an empty list')
+        raise
+    _warn_empty(not bool(m.any()), what)
+    return _mask_out(m, state['cuda'])
+
+
+def compute_multi_epi_mask(volumes, lower_cutoff=0.2, upper_cutoff=0.85, connected=True, opening=2, threshold=0.5,
+                           exclude_zeros=False):
+    """`compute_epi_mask` of every volume of a list (or any iterable: they are taken one at a time) with these arguments, then
+    `intersect_masks(those, threshold, connected)`; the running count stays on the device.  All volumes must have one
+    spatial shape.  A CUDA tensor comes back if any volume is one.  ValueError: as `compute_epi_mask` and `intersect_masks`,
+    an empty list, shapes that differ."""
+    lo, up = _check_cutoffs(lower_cutoff, upper_cutoff)
+    connected, opening = _check_post(connected, opening)
+    threshold = _check_threshold(threshold)
+    ez = bool(exclude_zeros)
+    return _multi(volumes, lambda f: _epi_device(f, lo, up, connected, opening, ez),
+                  lambda v: _epi_host(v, lo, up, connected, opening, ez), threshold, connected, 'compute_multi_epi_mask')
+
+
+def compute_multi_background_mask(volumes, border_size=2, connected=True, opening=2, threshold=0.5):
+    """`compute_background_mask` of every volume with these arguments, then `intersect_masks(those, threshold, connected)`;
+    see `compute_multi_epi_mask`."""
+    border_size = _check_border(border_size)
+    connected, opening = _check_post(connected, opening)
+    threshold = _check_threshold(threshold)
+    return _multi(volumes, lambda f: _background_device(f, border_size, connected, opening),
+                  lambda v: _background_host(v, border_size, connected, opening), threshold, connected,
+                  'compute_multi_background_mask')
+
+
+MASK_STRATEGIES = {'epi': compute_multi_epi_mask, 'background': compute_multi_background_mask}
+
+
+def _check_strategy(mask, mask_args):
+    if mask not in MASK_STRATEGIES:
+        raise ValueError("mask must be a boolean array, 'background' or 'epi', got %r" % (mask,))
+    if mask_args is not None and not isinstance(mask_args, dict):
+        raise ValueError('mask_args must be None or a dict of arguments of compute_multi_%s_mask, got %r' % (mask, mask_args))
+    return MASK_STRATEGIES[mask], dict(mask_args or {})
+
+
+def _check_same_grid(affine, mask_affine, what):
+    """while a mask is computed every volume lies on one grid: an affine that says otherwise is refused"""
+    if affine is None:
+        return
+    a = _check_affine(affine, 'affine')
+    if mask_affine is None or not np.allclose(a, _check_affine(mask_affine, 'mask_affine')):
+        raise ValueError('%s has affine %r, which is not mask_affine = %r: a mask is computed on one grid - resample first '
+                         '(modl_amd.masker.resample)' % (what, a.tolist(),
+                                                         None if mask_affine is None else np.asarray(mask_affine).tolist()))
+
+
+def compute_strategy_mask(mask, mask_args, volumes, affines=None, mask_affine=None):
+    """the mask of the strategy `mask` ('background' / 'epi') over `volumes` (an iterable), as a numpy (X, Y, Z) boolean array"""
+    fn, args = _check_strategy(mask, mask_args)
+    if affines is not None:
+        for i, a in enumerate(affines):
+            _check_same_grid(a, mask_affine, 'volume %d' % i)
+    found = fn(volumes, **args)
+    return found.cpu().numpy() if isinstance(found, torch.Tensor) else found
+
+
 class ArrayMasker(BaseEstimator):
     """The reference's masker on arrays: smooth, mask, clean - and back.
 
-    mask            (X, Y, Z) boolean array
+    mask            (X, Y, Z) boolean array, or the strategy 'background' / 'epi': `fit(volumes)` then computes the mask from one
+                    volume or a list with compute_multi_background_mask / compute_multi_epi_mask (module docstring, section
+                    27) and `mask_args` (None or a dict of their arguments).  `mask_` is the boolean array either way.
+                    `fit()` without volumes is then a ValueError, and so is an `affine` of `fit` that is not allclose to
+                    `mask_affine`: a mask is computed on one grid, resample first.
     voxel_size      (vx, vy, vz) in mm, what the affine of an image says
     smoothing_fwhm  None, a number or one per axis, in mm
     standardize, detrend, low_pass, high_pass, t_r    the cleaning of every record (modl_amd.signal.clean)
@@ -526,8 +1033,9 @@ class ArrayMasker(BaseEstimator):
                     An `affine` without `mask_affine`, or a singular one, is a ValueError."""
 
     def __init__(self, mask, voxel_size=(1, 1, 1), smoothing_fwhm=None, standardize=False, detrend=False, low_pass=None,
-                 high_pass=None, t_r=None, mask_affine=None):
+                 high_pass=None, t_r=None, mask_affine=None, mask_args=None):
         self.mask = mask
+        self.mask_args = mask_args
         self.mask_affine = mask_affine
         self.voxel_size = voxel_size
         self.smoothing_fwhm = smoothing_fwhm
@@ -537,8 +1045,19 @@ class ArrayMasker(BaseEstimator):
         self.high_pass = high_pass
         self.t_r = t_r
 
-    def fit(self, X=None, y=None):
-        self.maps_ = _Maps(self.mask)
+    def fit(self, X=None, y=None, affine=None):
+        if isinstance(self.mask, str):
+            _check_strategy(self.mask, self.mask_args)
+            if X is None:
+                raise ValueError('mask = %r is computed from volumes: call fit(volumes)' % self.mask)
+            volumes = _check_volumes(X)
+            affines = None if affine is None else ([affine] * len(volumes) if np.ndim(affine) == 2 else list(affine))
+            self.mask_ = compute_strategy_mask(self.mask, self.mask_args, volumes, affines, self.mask_affine)
+        else:
+            if self.mask_args is not None:
+                raise ValueError('mask_args = %r goes with mask = \'background\' or \'epi\', not with an array' % (self.mask_args,))
+            self.mask_ = self.mask
+        self.maps_ = _Maps(self.mask_)
         self.mask_affine_ = None if self.mask_affine is None else _check_affine(self.mask_affine, 'mask_affine')
         voxel_size = (1, 1, 1) if self.voxel_size is None else self.voxel_size
         if self.mask_affine_ is not None and np.array_equal(np.asarray(voxel_size, dtype=object), (1, 1, 1)):
