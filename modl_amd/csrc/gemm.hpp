@@ -12,7 +12,9 @@
 // gfx950 mapping: 256-thread workgroups = 4 wavefronts in a 2x2 grid, each wave
 // owning RM x RN matrix-core tiles (f32: v_mfma_f32_32x32x2_f32, exact fp32 FMA
 // chains; f64: v_mfma_f64_16x16x4_f64).  Operand tiles are staged k-major in LDS
-// (+1 padding) so fragment reads are conflict-free 32-lane rows.  K can be split
+// (+1 padding) so fragment reads are conflict-free 32-lane rows; what a wavefront does
+// with a staged tile is sweep_zero / sweep_ktile / sweep_store below, shared with the
+// masked tile kernels.  K can be split
 // over gridDim.z; partial tiles are then summed in a fixed order by
 // gemm_reduce_kernel, so results are run-to-run deterministic.
 #pragma once
@@ -63,6 +65,62 @@ template <> struct Mma<double> {
     static __device__ __forceinline__ int acc_row(int lane, int r) { return (lane >> 4) + 4 * r; }
     static __device__ __forceinline__ int acc_col(int lane, int) { return lane & 15; }
 };
+// 16 x 16 x 4 tiles in either dtype
+template <typename T> struct Mma16 { typedef Mma<T> type; };
+template <> struct Mma16<float> { typedef Mma16f type; };
+
+// ---- the tile sweep -----------------------------------------------------------
+// What a wavefront does with operand tiles staged k-major in LDS (As[kk][row], Bs[kk][col]): it owns the RM x RN
+// matrix-core tiles at (row0, col0) of the workgroup's tile, one accumulator chain per tile, k ascending.  These three
+// functions are the only place where the lane map of the instruction (frag_k / frag_i, acc_row / acc_col) meets an LDS
+// index; gemm_kernel and the masked tile kernels (masked_gram, masked_stats, masked_objective) are built from them.
+template <class MT, int RM, int RN> __device__ __forceinline__ void sweep_zero(typename MT::acc_t (&acc)[RM][RN]) {
+#pragma unroll
+    for (int i = 0; i < RM; ++i)
+#pragma unroll
+        for (int j = 0; j < RN; ++j)
+#pragma unroll
+            for (int r = 0; r < MT::NACC; ++r) acc[i][j][r] = 0;
+}
+
+struct SweepNoHook {
+    template <typename T, int RN> __device__ __forceinline__ void operator()(int, const T (&)[RN]) const {}
+};
+// One staged K-tile of BK contraction indices.  After the tile products of a k-step, hook(kr, bf) sees the step's B
+// fragments (bf[j]: column col0 + j * TN + frag_i(lane) at contraction index kr = kk + frag_k(lane)) for a product of
+// its own on them.
+template <class MT, int BK, typename T, int RM, int RN, int LDA, int LDB, class Hook = SweepNoHook>
+__device__ __forceinline__ void sweep_ktile(typename MT::acc_t (&acc)[RM][RN], T (*As)[LDA], T (*Bs)[LDB], int row0,
+                                            int col0, int lane, Hook &&hook = Hook()) {
+#pragma unroll
+    for (int kk = 0; kk < BK; kk += MT::TK) {
+        T af[RM], bf[RN];
+        const int kr = kk + MT::frag_k(lane);
+#pragma unroll
+        for (int i = 0; i < RM; ++i) af[i] = As[kr][row0 + i * MT::TM + MT::frag_i(lane)];
+#pragma unroll
+        for (int j = 0; j < RN; ++j) bf[j] = Bs[kr][col0 + j * MT::TN + MT::frag_i(lane)];
+#pragma unroll
+        for (int i = 0; i < RM; ++i)
+#pragma unroll
+            for (int j = 0; j < RN; ++j) acc[i][j] = MT::mma(af[i], bf[j], acc[i][j]);
+        hook(kr, bf);
+    }
+}
+
+// the accumulators to an LDS tile Ct[row][col], times `scale` if SCALED
+template <class MT, bool SCALED = false, typename T, int RM, int RN, int LD>
+__device__ __forceinline__ void sweep_store(T (*Ct)[LD], const typename MT::acc_t (&acc)[RM][RN], int row0, int col0,
+                                            int lane, T scale = 1) {
+#pragma unroll
+    for (int i = 0; i < RM; ++i)
+#pragma unroll
+        for (int j = 0; j < RN; ++j)
+#pragma unroll
+            for (int r = 0; r < MT::NACC; ++r)
+                Ct[row0 + i * MT::TM + MT::acc_row(lane, r)][col0 + j * MT::TN + MT::acc_col(lane, r)] =
+                    SCALED ? scale * acc[i][j][r] : acc[i][j][r];
+}
 
 // an epilogue with `typedef ... Fetched; Fetched fetch(m, n) const; void finish(m, n, v, const Fetched &) const;` gets its
 // per-output operands requested for all outputs before any is consumed (see gemm_kernel)
@@ -149,12 +207,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(Operand A, Operand B, int64_t
     const int64_t k_end = (k_begin + k_per_split < K) ? k_begin + k_per_split : K;
 
     typename MT::acc_t acc[RM][RN];
-#pragma unroll
-    for (int i = 0; i < RM; ++i)
-#pragma unroll
-        for (int j = 0; j < RN; ++j)
-#pragma unroll
-            for (int r = 0; r < MT::NACC; ++r) acc[i][j][r] = 0;
+    sweep_zero<MT>(acc);
 
     // tall configuration (short products, one workgroup per 128 rows): tiles at least half full take the dense staging
     constexpr bool kTall = (WGM == 4 && WGN == 1);
@@ -163,19 +216,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(Operand A, Operand B, int64_t
         stage_tile<T, BM, BK>(As, A, m0, M, k0, k_end, denseA);
         stage_tile<T, BN, BK>(Bs, B, n0, N, k0, k_end, denseB);
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += MT::TK) {
-            T af[RM], bf[RN];
-            const int kr = kk + MT::frag_k(lane);
-#pragma unroll
-            for (int i = 0; i < RM; ++i) af[i] = As[kr][wm * WTM + i * MT::TM + MT::frag_i(lane)];
-#pragma unroll
-            for (int j = 0; j < RN; ++j) bf[j] = Bs[kr][wn * WTN + j * MT::TN + MT::frag_i(lane)];
-#pragma unroll
-            for (int i = 0; i < RM; ++i)
-#pragma unroll
-                for (int j = 0; j < RN; ++j) acc[i][j] = MT::mma(af[i], bf[j], acc[i][j]);
-        }
+        sweep_ktile<MT, BK>(acc, As, Bs, wm * WTM, wn * WTN, lane);
         __syncthreads();
     }
 

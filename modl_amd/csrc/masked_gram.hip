@@ -4,14 +4,15 @@
 // Gram matrix of its own - the input of _enet_regression_multi_gram (dict_fact_fast.pyx:33-113).
 //
 // One workgroup per (sample, 64 x 64 tile of the upper triangle of G): 4 wavefronts in a 2 x 2 grid, each owning a
-// 32 x 32 block of the tile (f32: one v_mfma_f32_32x32x2_f32 accumulator; f64: 2 x 2 v_mfma_f64_16x16x4_f64).  The rows
-// of Dt stream through LDS once per workgroup, 16 at a time, masked-out rows replaced by zeros on the way in (a select,
-// so nothing of X at an unobserved position - NaN included - reaches a product).  The tiles of the first tile row also
-// carry the sample's row of X as a 65th operand row: one more MFMA per K-step on their two upper wavefronts gives
-// Dx[c0 : c0 + 64].  After the K loop the tile, scaled by r, goes through LDS (the operand buffers are free by then) and
-// is written twice, both times with lanes walking a row of G: as G[a0 + m][c0 + n] and, off the diagonal, mirrored as
-// G[c0 + n][a0 + m].  A diagonal tile writes its upper half to both sides.  G is therefore symmetric bit for bit; no
-// atomics, no scratch: the result is the same bits from run to run.
+// 32 x 32 block of the tile (f32: one v_mfma_f32_32x32x2_f32 accumulator; f64: 2 x 2 v_mfma_f64_16x16x4_f64; the tile
+// sweep of gemm.hpp).  The rows of Dt stream through LDS once per workgroup, 16 at a time, masked-out rows replaced by
+// zeros on the way in (a select, so nothing of X at an unobserved position - NaN included - reaches a product).  The
+// tiles of the first tile row also carry the sample's row of X as a 65th operand row: one more MFMA per K-step on
+// their two upper wavefronts (the hook of sweep_ktile, on the B fragments the step has read anyway) gives
+// Dx[c0 : c0 + 64].  After the K loop the tile, scaled by r, goes through LDS (the operand buffers are free by then)
+// and is written twice, both times with lanes walking a row of G: as G[a0 + m][c0 + n] and, off the diagonal, mirrored
+// as G[c0 + n][a0 + m].  A diagonal tile writes its upper half to both sides.  G is therefore symmetric bit for bit;
+// no atomics, no scratch: the result is the same bits from run to run.
 // LDS: 64 * 65 elements (16.3 KB f32, 32.5 KB f64) + 16 of X.
 #include "gemm.hpp"
 #include "kernels.hpp"
@@ -56,15 +57,9 @@ __global__ __launch_bounds__(256) void masked_gram_kernel(const T *__restrict__ 
     cnt = (int)wave_sum((double)cnt);                         // (exact)
     if (lane == 0) s_cnt[wid] = cnt;
 
-    typename MT::acc_t acc[R][R], accx[R];
-#pragma unroll
-    for (int a = 0; a < R; ++a)
-#pragma unroll
-        for (int r = 0; r < MT::NACC; ++r) {
-            accx[a][r] = 0;
-#pragma unroll
-            for (int c = 0; c < R; ++c) acc[a][c][r] = 0;
-        }
+    typename MT::acc_t acc[R][R], accx[1][R];
+    sweep_zero<MT>(acc);
+    sweep_zero<MT>(accx);
 
     for (int64_t k0 = 0; k0 < p; k0 += BK) {
         // staging: lanes walk the atoms (contiguous in Dt), 4 rows of Dt per round
@@ -86,24 +81,13 @@ __global__ __launch_bounds__(256) void masked_gram_kernel(const T *__restrict__ 
             Xs[tid] = (e < p && o[ec] != 0) ? v : (T)0;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += MT::TK) {
-            const int kr = kk + MT::frag_k(lane);
-            T af[R], bf[R];
-#pragma unroll
-            for (int a = 0; a < R; ++a) af[a] = As[kr][wm * 32 + a * MT::TM + MT::frag_i(lane)];
-#pragma unroll
-            for (int c = 0; c < R; ++c) bf[c] = Bs[kr][wn * 32 + c * MT::TN + MT::frag_i(lane)];
-#pragma unroll
-            for (int a = 0; a < R; ++a)
-#pragma unroll
-                for (int c = 0; c < R; ++c) acc[a][c] = MT::mma(af[a], bf[c], acc[a][c]);
+        sweep_ktile<MT, BK>(acc, As, Bs, wm * 32, wn * 32, lane, [&](int kr, const T(&bf)[R]) {
             if (with_dx && wm == 0) {                         // the row of X as row 0 of one more operand tile
                 const T xf = MT::frag_i(lane) == 0 ? Xs[kr] : (T)0;
 #pragma unroll
-                for (int c = 0; c < R; ++c) accx[c] = MT::mma(xf, bf[c], accx[c]);
+                for (int c = 0; c < R; ++c) accx[0][c] = MT::mma(xf, bf[c], accx[0][c]);
             }
-        }
+        });
         __syncthreads();
     }
 
@@ -117,19 +101,12 @@ __global__ __launch_bounds__(256) void masked_gram_kernel(const T *__restrict__ 
 #pragma unroll
             for (int r = 0; r < MT::NACC; ++r) {
                 const int n = c0 + wn * 32 + c * MT::TN + MT::acc_col(lane, r);
-                if (MT::acc_row(lane, r) == 0 && n < k) Dx[ii * k + n] = r_i * accx[c][r];
+                if (MT::acc_row(lane, r) == 0 && n < k) Dx[ii * k + n] = r_i * accx[0][c][r];
             }
     }
 
     // the tile through LDS (free after the loop's last barrier), scaled
-#pragma unroll
-    for (int a = 0; a < R; ++a)
-#pragma unroll
-        for (int c = 0; c < R; ++c)
-#pragma unroll
-            for (int r = 0; r < MT::NACC; ++r)
-                Ct[wm * 32 + a * MT::TM + MT::acc_row(lane, r)][wn * 32 + c * MT::TN + MT::acc_col(lane, r)] =
-                    r_i * acc[a][c][r];
+    sweep_store<MT, true>(Ct, acc, wm * 32, wn * 32, lane, r_i);
     __syncthreads();
     T *Gi = G + ii * (int64_t)k * k;
     for (int el = tid; el < BT * BT; el += 256) {

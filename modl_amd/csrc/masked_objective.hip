@@ -2,11 +2,11 @@
 // rows completed by their reconstruction.  Both are one product code Dt^T whose n x p result never leaves the chip.
 //
 // masked_tile_kernel: one workgroup per tile of 64 rows x 64 features, K = k, on the matrix cores in the dtype (4
-// wavefronts in a 2 x 2 grid, 2 x 2 tiles of 16 x 16 x 4 each).  Both operands are k-contiguous, so lanes walk k when
-// staging.  The finished tile goes through LDS (the operand buffers, reused), from where lanes walk the features: the
-// epilogue's reads of X and of the selection bytes - their only reads - and the stores of the imputed rows are whole
-// cache lines, and the epilogue does not depend on the C/D lane map of the instruction (gemm.hpp's traits resolve it
-// once, where the tile is written to LDS).
+// wavefronts in a 2 x 2 grid, 2 x 2 tiles of 16 x 16 x 4 each: the tile sweep of gemm.hpp).  Both operands are
+// k-contiguous, so lanes walk k when staging.  The finished tile goes through LDS (the operand buffers, reused), from
+// where lanes walk the features: the epilogue's reads of X and of the selection bytes - their only reads - and the
+// stores of the imputed rows are whole cache lines, and the epilogue does not depend on the C/D lane map of the
+// instruction (sweep_store resolves it once, where the tile is written to LDS).
 //
 //   objective: res = X - (code Dt^T) in the dtype where sel is 1 or 2 - by a select, an entry that is not selected
 //     (NaN included) reaches no arithmetic -, the square and every sum in f64.  A workgroup leaves its eight partial
@@ -24,9 +24,6 @@ namespace {
 constexpr int kMoBT = 64, kMoBK = 32, kMoLD = kMoBT + 1;
 constexpr size_t kMoSlot = 8 * sizeof(double);                // a workgroup's partial sums
 
-template <typename T> struct MoMma { typedef Mma<T> type; };
-template <> struct MoMma<float> { typedef Mma16f type; };
-
 template <typename T, bool IMPUTE>
 __global__ __launch_bounds__(256) void masked_tile_kernel(const T *__restrict__ X, int64_t ldx,
                                                           const uint8_t *__restrict__ sel, int64_t lds, int64_t n,
@@ -34,7 +31,7 @@ __global__ __launch_bounds__(256) void masked_tile_kernel(const T *__restrict__ 
                                                           const T *__restrict__ code, const double *__restrict__ row_w,
                                                           double *__restrict__ part, T *__restrict__ out, int64_t ldout,
                                                           int64_t tiles_p) {
-    using MT = typename MoMma<T>::type;
+    using MT = typename Mma16<T>::type;
     static_assert(MT::TM == 16 && MT::TN == 16 && MT::TK == 4, "16 x 16 x 4 tiles");
     constexpr int BT = kMoBT, BK = kMoBK, LD = kMoLD, R = 2, WT = 16 * R;
     static_assert(BT * LD >= 2 * BK * LD, "the output tile reuses the operand buffers");
@@ -50,12 +47,7 @@ __global__ __launch_bounds__(256) void masked_tile_kernel(const T *__restrict__ 
     const bool norms = !IMPUTE && tile_e == 0;                // workgroup-uniform
 
     typename MT::acc_t acc[R][R];
-#pragma unroll
-    for (int a = 0; a < R; ++a)
-#pragma unroll
-        for (int c = 0; c < R; ++c)
-#pragma unroll
-            for (int r = 0; r < MT::NACC; ++r) acc[a][c][r] = 0;
+    sweep_zero<MT>(acc);
 
     double c_abs = 0.0, c_sq = 0.0;
     for (int k0 = 0; k0 < k; k0 += BK) {
@@ -82,29 +74,11 @@ __global__ __launch_bounds__(256) void masked_tile_kernel(const T *__restrict__ 
             }
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += MT::TK) {
-            const int kr = kk + MT::frag_k(lane);
-            T af[R], bf[R];
-#pragma unroll
-            for (int a = 0; a < R; ++a) af[a] = As[kr][wm * WT + a * 16 + MT::frag_i(lane)];
-#pragma unroll
-            for (int c = 0; c < R; ++c) bf[c] = Bs[kr][wn * WT + c * 16 + MT::frag_i(lane)];
-#pragma unroll
-            for (int a = 0; a < R; ++a)
-#pragma unroll
-                for (int c = 0; c < R; ++c) acc[a][c] = MT::mma(af[a], bf[c], acc[a][c]);
-        }
+        sweep_ktile<MT, BK>(acc, As, Bs, wm * WT, wn * WT, lane);
         __syncthreads();
     }
 
-#pragma unroll
-    for (int a = 0; a < R; ++a)
-#pragma unroll
-        for (int c = 0; c < R; ++c)
-#pragma unroll
-            for (int r = 0; r < MT::NACC; ++r)
-                Ct[wm * WT + a * 16 + MT::acc_row(lane, r)][wn * WT + c * 16 + MT::acc_col(lane, r)] = acc[a][c][r];
+    sweep_store<MT>(Ct, acc, wm * WT, wn * WT, lane);
     __syncthreads();
 
     // lanes walk the features: thread tid owns feature e0 + (tid & 63) of the rows i0 + (tid >> 6) + 4 t

@@ -7,8 +7,8 @@
 // and nothing at all for a feature nobody observes.
 //
 // Two launches.  masked_stats_kernel: one workgroup per tile of BT features x BT atoms of the product (X o obs)^T code,
-// K = b, on the matrix cores in the dtype (4 wavefronts in a 2 x 2 grid, R x R tiles of 16 x 16 x 4 each: BT = 32 for
-// small outputs - more workgroups -, 64 otherwise).  The rows of X and obs are staged with lanes walking the features,
+// K = b, on the matrix cores in the dtype (the tile sweep of gemm.hpp with R x R tiles of 16 x 16 x 4 per wavefront:
+// BT = 32 for small outputs - more workgroups -, 64 otherwise).  The rows of X and obs are staged with lanes walking the features,
 // the codes with lanes walking the atoms; an unobserved element is replaced by zero by a select on the way in (nothing
 // of X at an unobserved position - NaN included - reaches a product; no zero-filled copy of X exists).  Every workgroup
 // counts its own features' observers from the bytes it stages anyway (exact integers, the same in every workgroup of
@@ -25,16 +25,13 @@ namespace {
 
 constexpr int kMsBK = 16;
 
-template <typename T> struct MsMma { typedef Mma<T> type; };
-template <> struct MsMma<float> { typedef Mma16f type; };
-
 template <typename T, int R>
 __global__ __launch_bounds__(256) void masked_stats_kernel(const T *__restrict__ X, int64_t ldx,
                                                            const uint8_t *__restrict__ obs, int64_t ldo,
                                                            const int64_t *__restrict__ rows, int b, int64_t p, int k,
                                                            const T *__restrict__ code, T *__restrict__ Bt,
                                                            const int64_t *__restrict__ fni, double w, double n_iter) {
-    using MT = typename MsMma<T>::type;
+    using MT = typename Mma16<T>::type;
     static_assert(MT::TM == 16 && MT::TN == 16 && MT::TK == 4, "16 x 16 x 4 tiles");
     constexpr int BT = 32 * R, BK = kMsBK, LD = BT + 1, WT = 16 * R;
     static_assert(BT * LD >= 2 * BK * LD, "the output tile reuses the operand buffers");
@@ -63,12 +60,7 @@ __global__ __launch_bounds__(256) void masked_stats_kernel(const T *__restrict__
     }
 
     typename MT::acc_t acc[R][R];
-#pragma unroll
-    for (int a = 0; a < R; ++a)
-#pragma unroll
-        for (int c = 0; c < R; ++c)
-#pragma unroll
-            for (int r = 0; r < MT::NACC; ++r) acc[a][c][r] = 0;
+    sweep_zero<MT>(acc);
 
     for (int k0 = 0; k0 < b; k0 += BK) {
 #pragma unroll
@@ -85,19 +77,7 @@ __global__ __launch_bounds__(256) void masked_stats_kernel(const T *__restrict__
             Bs[kl][il] = (i < b && a < k) ? cv : (T)0;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += MT::TK) {
-            const int kr = kk + MT::frag_k(lane);
-            T af[R], bf[R];
-#pragma unroll
-            for (int a = 0; a < R; ++a) af[a] = As[kr][wm * WT + a * 16 + MT::frag_i(lane)];
-#pragma unroll
-            for (int c = 0; c < R; ++c) bf[c] = Bs[kr][wn * WT + c * 16 + MT::frag_i(lane)];
-#pragma unroll
-            for (int a = 0; a < R; ++a)
-#pragma unroll
-                for (int c = 0; c < R; ++c) acc[a][c] = MT::mma(af[a], bf[c], acc[a][c]);
-        }
+        sweep_ktile<MT, BK>(acc, As, Bs, wm * WT, wn * WT, lane);
         __syncthreads();
     }
 
@@ -116,13 +96,7 @@ __global__ __launch_bounds__(256) void masked_stats_kernel(const T *__restrict__
         s_alpha[tid] = (T)al;
         s_cnt[0][tid] = c;
     }
-#pragma unroll
-    for (int a = 0; a < R; ++a)
-#pragma unroll
-        for (int c = 0; c < R; ++c)
-#pragma unroll
-            for (int r = 0; r < MT::NACC; ++r)
-                Ct[wm * WT + a * 16 + MT::acc_row(lane, r)][wn * WT + c * 16 + MT::acc_col(lane, r)] = acc[a][c][r];
+    sweep_store<MT>(Ct, acc, wm * WT, wn * WT, lane);
     __syncthreads();
     for (int el = tid; el < BT * BT; el += 256) {
         const int m = el / BT, n = el % BT;                   // lanes walk the atoms

@@ -1,13 +1,14 @@
 // Ranks of held-out items for RecsysDictFact: where the targets of b queries stand among the items the query has not excluded.
 //
-//   score[ii][f] = sum_c code[ii][c] * Dt[f][c] (+ item_bias[f])        the score of recsys_topn_kernel, bit for bit
+//   score[ii][f] = sum_c code[ii][c] * Dt[f][c] (+ item_bias[f])        the score of recsys_topn_kernel, bit for bit: both kernels
+//                                                                             get it from topn_score_tile (recsys_topn.hpp)
 //   ranks[e]     = #{ c != t : c not excluded for ii, (score[ii][c], c) beats (score[ii][t], t) }     t = t_indices[e] of query ii
 //
 // The b x p scores are never written.  The launches:
-//   1. a memset of the two bitmasks and of the counters; recsys_rank_mask_kernel twice: the exclusion pattern and the first
-//      t_max entries of every target row, each ORed into a bitmask of p bits per query.
+//   1. a memset of the two bitmasks and of the counters; the top-N file's recsys_mask_kernel twice (launch_recsys_mask): the
+//      exclusion pattern and the first t_max entries of every target row, each ORed into a bitmask of p bits per query.
 //   2. recsys_rank_sweep_kernel<T, false> ("capture"): the tile product of the top-N kernel (a workgroup owns 32 queries and
-//      one slab of items; tiles of 128 / 64 items, K in chunks of 64, the same Mma<T> chain).  A score whose bit is set in
+//      one slab of items; tiles of 128 / 64 items, K in chunks of 64: topn_score_tile).  A score whose bit is set in
 //      the target mask is written to every entry of the query's target row that names the item (the row's ids are in LDS;
 //      a hit is rare and the hitting lane scans the row).
 //   3. recsys_rank_sweep_kernel<T, true> ("count"): the workgroup first sorts the (score, item) pairs of each of its queries'
@@ -40,47 +41,19 @@ template <typename T> __device__ __forceinline__ int rank_sorted_pos(const T *rs
     return pos;
 }
 
-// one wavefront per query ORs the first `limit` entries of its CSR row into the query's bitmask
-__global__ __launch_bounds__(256) void recsys_rank_mask_kernel(const int32_t *indptr, const int32_t *indices,
-                                                               const int64_t *rows, int64_t b, int64_t p, int64_t W,
-                                                               int limit, unsigned int *mask) {
-    const int lane = threadIdx.x & 63;
-    const int64_t ii = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ii >= b) return;
-    const int64_t r = rows ? rows[ii] : ii;
-    unsigned int *row = mask + ii * W;
-    const int32_t e0 = indptr[r];
-    const int64_t len = (int64_t)indptr[r + 1] - e0;
-    const int32_t e1 = e0 + (int32_t)(len < limit ? len : limit);
-    for (int32_t e = e0 + lane; e < e1; e += 64) {
-        const int32_t f = indices[e];
-        if (f >= 0 && f < p) atomicOr(row + (f >> 5), 1u << (f & 31));
-    }
-}
-
-struct RankLds { size_t cs, ds, ths, raws, bs, thi, rawi, hist, nn, nv, mk, total; int ldc, ldd, ldt, ldh; };
+struct RankLds : TopnTileLds { size_t ths, raws, thi, rawi, hist, nn, nv; int ldt, ldh; };
 template <typename T> static RankLds rank_lds(int k, int t_max) {
-    constexpr int IT = 4 * TopnCfg<T>::WN, TK = Mma<T>::TK;
-    const int kp = (k + TK - 1) / TK * TK;
+    const int ldt = t_max | 1, ldh = (t_max + 1) | 1;
+    const size_t rows = (size_t)kTopnUsers * ldt, hist = (size_t)kTopnUsers * ldh;
     RankLds L;
-    L.ldc = kp | 1;
-    L.ldd = (kp < kTopnKC ? kp : kTopnKC) | 1;
-    L.ldt = t_max | 1;
-    L.ldh = (t_max + 1) | 1;
-    size_t o = 0;
-    L.cs = o; o += sizeof(T) * (size_t)kTopnUsers * L.ldc;
-    L.ds = o; o += sizeof(T) * (size_t)IT * L.ldd;
-    L.ths = o; o += sizeof(T) * (size_t)kTopnUsers * L.ldt;
-    L.raws = o; o += sizeof(T) * (size_t)kTopnUsers * L.ldt;
-    o = align_up(o, 8);
-    L.bs = o; o += sizeof(double) * IT;
-    L.thi = o; o += sizeof(int) * (size_t)kTopnUsers * L.ldt;
-    L.rawi = o; o += sizeof(int) * (size_t)kTopnUsers * L.ldt;
-    L.hist = o; o += sizeof(int) * (size_t)kTopnUsers * L.ldh;
-    L.nn = o; o += sizeof(int) * kTopnUsers;
-    L.nv = o; o += sizeof(int) * kTopnUsers;
-    L.mk = o; o += sizeof(unsigned int) * kTopnUsers * (IT / 32);
-    L.total = align_up(o, 16);
+    static_cast<TopnTileLds &>(L) = topn_tile_lds<T>(k, 2 * rows, 2 * rows + hist + 2 * kTopnUsers, &L.ths, &L.thi);
+    L.ldt = ldt;
+    L.ldh = ldh;
+    L.raws = L.ths + sizeof(T) * rows;
+    L.rawi = L.thi + sizeof(int) * rows;
+    L.hist = L.rawi + sizeof(int) * rows;
+    L.nn = L.hist + sizeof(int) * hist;
+    L.nv = L.nn + sizeof(int) * kTopnUsers;
     return L;
 }
 
@@ -108,20 +81,13 @@ __global__ __launch_bounds__(256) void recsys_rank_sweep_kernel(const T *code, c
     int *nv = reinterpret_cast<int *>(smem_raw + L.nv);        // in-range ones among them
     unsigned int *mk = reinterpret_cast<unsigned int *>(smem_raw + L.mk);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int kp = (k + MT::TK - 1) / MT::TK * MT::TK, ldc = L.ldc, ldd = L.ldd, ldt = L.ldt, ldh = L.ldh;
+    const int ldt = L.ldt, ldh = L.ldh;
     const int64_t u0 = (int64_t)blockIdx.x * kTopnUsers;
     const int slab = blockIdx.y;
     const int64_t f_begin = (int64_t)slab * slab_items;
     const int64_t f_end = f_begin + slab_items < p ? f_begin + slab_items : p;
 
-    // the codes of the tile's queries (zero beyond b and beyond k)
-    for (int e = tid; e < kTopnUsers * ldc; e += 256) {
-        const int m = e / ldc, c = e % ldc;
-        const int64_t ii = u0 + m < b ? u0 + m : b - 1;
-        const int64_t row = code_rows ? code_rows[ii] : ii;
-        const T v = code[row * k + (c < k ? c : 0)];
-        Cs[e] = (u0 + m < b && c < k) ? v : (T)0;
-    }
+    topn_stage_codes(Cs, L.ldc, code, code_rows, u0, b, k);
     // the target rows
     if (tid < kTopnUsers) {
         int n = 0;
@@ -160,56 +126,10 @@ __global__ __launch_bounds__(256) void recsys_rank_sweep_kernel(const T *code, c
         }
     }
 
-    const int lpr = kp > 32 ? 64 : (kp > 16 ? 32 : 16);       // lanes that walk one dictionary row
-    const int rpp = 256 / lpr, sub = tid / lpr, c0 = tid % lpr;
+    const TopnSplit sp = topn_split<T>(k);
     for (int64_t item0 = f_begin; item0 < f_end; item0 += IT) {
-        typename MT::acc_t acc[RM];
-#pragma unroll
-        for (int i = 0; i < RM; ++i)
-#pragma unroll
-            for (int r = 0; r < MT::NACC; ++r) acc[i][r] = 0;
-        for (int kc0 = 0; kc0 < kp; kc0 += kTopnKC) {
-            const int kcn = kp - kc0 < kTopnKC ? kp - kc0 : kTopnKC;
-            __syncthreads();                                 // the tile before this one is consumed; the sorted rows are written
-            if (kc0 == 0) {
-                if (tid < kTopnUsers * MW) {
-                    const int m = tid / MW, w = tid % MW;
-                    const int64_t ii = u0 + m < b ? u0 + m : b - 1;
-                    const int64_t word = item0 / 32 + w;
-                    mk[tid] = (mask && word < W) ? mask[ii * W + word] : 0u;
-                }
-                if (tid < IT) {
-                    const int64_t f = item0 + tid < p ? item0 + tid : p - 1;
-                    bs[tid] = item_bias ? item_bias[f] : 0.0;
-                }
-            }
-            for (int c = c0; c < kcn; c += lpr) {
-                const int cc = kc0 + c;
-                for (int it0 = sub; it0 < IT; it0 += 8 * rpp) {
-                    T v[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int64_t f = item0 + it0 + q * rpp;
-                        v[q] = Dt[(f < p ? f : p - 1) * k + (cc < k ? cc : 0)];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int item = it0 + q * rpp;
-                        if (item < IT) Ds[item * ldd + c] = (item0 + item < f_end && cc < k) ? v[q] : (T)0;
-                    }
-                }
-            }
-            __syncthreads();
-            for (int kk = 0; kk < kcn; kk += MT::TK) {
-                const int kr = kk + MT::frag_k(lane);
-                const T bf = Ds[(wid * WN + MT::frag_i(lane)) * ldd + kr];
-#pragma unroll
-                for (int i = 0; i < RM; ++i) {
-                    const T af = Cs[(i * MT::TM + MT::frag_i(lane)) * ldc + kc0 + kr];
-                    acc[i] = MT::mma(af, bf, acc[i]);
-                }
-            }
-        }
+        typename MT::acc_t acc[RM];                          // (its first barrier: the sorted rows are written)
+        topn_score_tile(acc, Cs, Ds, mk, bs, L.ldc, L.ldd, Dt, p, k, mask, W, item_bias, item0, f_end, u0, b, sp);
         {
             const int col = wid * WN + MT::acc_col(lane, 0);
             const int64_t f = item0 + col;
@@ -341,14 +261,8 @@ static int recsys_ranks(const T *code, const int64_t *code_rows, int64_t b, int 
     T *tscore = reinterpret_cast<T *>(base + w.tscore);
     const size_t z0 = ex_indptr ? w.ex_mask : w.t_mask;
     MODL_HIP(hipMemsetAsync(base + z0, 0, w.zeroed - z0, st));
-    if (ex_indptr) {
-        hipLaunchKernelGGL(recsys_rank_mask_kernel, dim3((unsigned)cdiv(b, 4)), dim3(256), 0, st, ex_indptr, ex_indices,
-                           ex_rows, b, p, w.W, 0x7fffffff, ex_mask);
-        MODL_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(recsys_rank_mask_kernel, dim3((unsigned)cdiv(b, 4)), dim3(256), 0, st, t_indptr, t_indices,
-                       (const int64_t *)nullptr, b, p, w.W, t_max, t_mask);
-    MODL_LAUNCH_CHECK();
+    if (ex_indptr) MODL_TRY(launch_recsys_mask(st, ex_indptr, ex_indices, ex_rows, b, p, w.W, INT32_MAX, ex_mask));
+    MODL_TRY(launch_recsys_mask(st, t_indptr, t_indices, nullptr, b, p, w.W, t_max, t_mask));
     const RankLds L = rank_lds<T>(k, t_max);
     int top_step = 1;                                         // the largest power of two not above t_max
     while (top_step * 2 <= t_max) top_step *= 2;

@@ -4,13 +4,13 @@
 //   items[ii][j] = the item with the j-th largest score; equal scores by ascending item id
 //
 // The b x p scores are never written.  Three launches:
-//   1. recsys_topn_mask_kernel (only with an exclusion pattern): one wavefront per query ORs the items of its CSR row into a
-//      bitmask of p bits (zeroed by a memset before it).  An OR commutes: duplicates and unsorted indices cost nothing and
-//      no order depends on an atomic.
+//   1. recsys_mask_kernel (only with an exclusion pattern; launch_recsys_mask serves the rank kernels too): one wavefront per
+//      query ORs the items of its CSR row into a bitmask of p bits (zeroed by a memset before it).
 //   2. recsys_topn_kernel: a workgroup owns 32 queries and one slab of items.  The 32 codes stay in LDS; the slab is streamed
 //      in tiles of IT items (f32: 128, f64: 64; a tile of the feature-major dictionary is one contiguous block), K in chunks
 //      of 64.  Each of the four wavefronts multiplies the 32 codes with its quarter of the tile on the matrix cores (Mma<T> of
-//      gemm.hpp: one 32 x 32 x 2 tile in f32, two 16 x 16 x 4 tiles in f64), and every lane tests its scores against the
+//      gemm.hpp: one 32 x 32 x 2 tile in f32, two 16 x 16 x 4 tiles in f64; topn_score_tile of recsys_topn.hpp, shared with
+//      the rank kernels), and every lane tests its scores against the
 //      query's exclusion word (staged in LDS with the tile: O(1) per score) and the query's threshold, the n_top-th best so
 //      far.  Scores that beat it go to the query's candidate buffer in LDS; when a buffer holds kMergeMin candidates the
 //      wavefront that owns the query merges it into the query's sorted list by ranking (every element counts the elements
@@ -24,39 +24,40 @@
 
 namespace modl {
 
-__global__ __launch_bounds__(256) void recsys_topn_mask_kernel(const int32_t *indptr, const int32_t *indices,
-                                                               const int64_t *ex_rows, int64_t b, int64_t p, int64_t W,
-                                                               unsigned int *mask) {
+__global__ __launch_bounds__(256) void recsys_mask_kernel(const int32_t *indptr, const int32_t *indices,
+                                                          const int64_t *rows, int64_t b, int64_t p, int64_t W, int limit,
+                                                          unsigned int *mask) {
     const int lane = threadIdx.x & 63;
     const int64_t ii = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ii >= b) return;
-    const int64_t r = ex_rows ? ex_rows[ii] : ii;
+    const int64_t r = rows ? rows[ii] : ii;
     unsigned int *row = mask + ii * W;
-    for (int32_t e = indptr[r] + lane; e < indptr[r + 1]; e += 64) {
+    const int32_t e0 = indptr[r];
+    const int64_t len = (int64_t)indptr[r + 1] - e0;
+    const int32_t e1 = e0 + (int32_t)(len < limit ? len : limit);
+    for (int32_t e = e0 + lane; e < e1; e += 64) {
         const int32_t f = indices[e];
         if (f >= 0 && f < p) atomicOr(row + (f >> 5), 1u << (f & 31));
     }
 }
 
-struct TopnLds { size_t cs, ds, tops, topi, cands, candi, cnt, mk, bs, total; int ldc, ldd; };
+int launch_recsys_mask(hipStream_t st, const int32_t *indptr, const int32_t *indices, const int64_t *rows, int64_t b,
+                       int64_t p, int64_t W, int limit, unsigned int *mask) {
+    hipLaunchKernelGGL(recsys_mask_kernel, dim3((unsigned)cdiv(b, 4)), dim3(256), 0, st, indptr, indices, rows, b, p, W,
+                       limit, mask);
+    MODL_LAUNCH_CHECK();
+    return MODL_OK;
+}
+
+struct TopnLds : TopnTileLds { size_t tops, topi, cands, candi, cnt; };
 template <typename T> static TopnLds topn_lds(int k, int n_top) {
-    constexpr int IT = 4 * TopnCfg<T>::WN, CB = IT + kTopnMergeMin, TK = Mma<T>::TK;
-    const int kp = (k + TK - 1) / TK * TK;
+    constexpr int IT = 4 * TopnCfg<T>::WN, CB = IT + kTopnMergeMin;
+    const size_t lists = (size_t)kTopnUsers * n_top, bufs = (size_t)kTopnUsers * CB;
     TopnLds L;
-    L.ldc = kp | 1;
-    L.ldd = (kp < kTopnKC ? kp : kTopnKC) | 1;
-    size_t o = 0;
-    L.cs = o; o += sizeof(T) * (size_t)kTopnUsers * L.ldc;
-    L.ds = o; o += sizeof(T) * (size_t)IT * L.ldd;
-    L.tops = o; o += sizeof(T) * (size_t)kTopnUsers * n_top;
-    L.cands = o; o += sizeof(T) * (size_t)kTopnUsers * CB;
-    o = align_up(o, 8);
-    L.bs = o; o += sizeof(double) * IT;
-    L.topi = o; o += sizeof(int) * (size_t)kTopnUsers * n_top;
-    L.candi = o; o += sizeof(int) * (size_t)kTopnUsers * CB;
-    L.cnt = o; o += sizeof(int) * kTopnUsers;
-    L.mk = o; o += sizeof(unsigned int) * kTopnUsers * (IT / 32);
-    L.total = align_up(o, 16);
+    static_cast<TopnTileLds &>(L) = topn_tile_lds<T>(k, lists + bufs, lists + bufs + kTopnUsers, &L.tops, &L.topi);
+    L.cands = L.tops + sizeof(T) * lists;
+    L.candi = L.topi + sizeof(int) * lists;
+    L.cnt = L.candi + sizeof(int) * bufs;
     return L;
 }
 
@@ -121,7 +122,6 @@ __global__ __launch_bounds__(256) void recsys_topn_kernel(const T *code, const i
     int *cnt = reinterpret_cast<int *>(smem_raw + L.cnt);
     unsigned int *mk = reinterpret_cast<unsigned int *>(smem_raw + L.mk);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int kp = (k + MT::TK - 1) / MT::TK * MT::TK, ldc = L.ldc, ldd = L.ldd;
     const int64_t u0 = (int64_t)blockIdx.x * kTopnUsers;
     const int slab = blockIdx.y;
     const int64_t f_begin = (int64_t)slab * slab_items;
@@ -129,69 +129,17 @@ __global__ __launch_bounds__(256) void recsys_topn_kernel(const T *code, const i
     const T ninf = -std::numeric_limits<T>::infinity();
 
     // the codes of the tile's queries (zero beyond b and beyond k), the empty lists
-    for (int e = tid; e < kTopnUsers * ldc; e += 256) {
-        const int m = e / ldc, c = e % ldc;
-        const int64_t ii = u0 + m < b ? u0 + m : b - 1;
-        const int64_t row = code_rows ? code_rows[ii] : ii;
-        const T v = code[row * k + (c < k ? c : 0)];
-        Cs[e] = (u0 + m < b && c < k) ? v : (T)0;
-    }
+    topn_stage_codes(Cs, L.ldc, code, code_rows, u0, b, k);
     for (int e = tid; e < kTopnUsers * n_top; e += 256) {
         top_s[e] = ninf;
         top_i[e] = -1 - e % n_top;                            // (distinct: every pair (score, item) of a list differs)
     }
     if (tid < kTopnUsers) cnt[tid] = 0;
 
-    const int lpr = kp > 32 ? 64 : (kp > 16 ? 32 : 16);       // lanes that walk one dictionary row
-    const int rpp = 256 / lpr, sub = tid / lpr, c0 = tid % lpr;
+    const TopnSplit sp = topn_split<T>(k);
     for (int64_t item0 = f_begin; item0 < f_end; item0 += IT) {
-        typename MT::acc_t acc[RM];
-#pragma unroll
-        for (int i = 0; i < RM; ++i)
-#pragma unroll
-            for (int r = 0; r < MT::NACC; ++r) acc[i][r] = 0;
-        for (int kc0 = 0; kc0 < kp; kc0 += kTopnKC) {
-            const int kcn = kp - kc0 < kTopnKC ? kp - kc0 : kTopnKC;
-            __syncthreads();                                 // the tile before this one is consumed, the merges are done
-            if (kc0 == 0) {
-                if (tid < kTopnUsers * MW) {
-                    const int m = tid / MW, w = tid % MW;
-                    const int64_t ii = u0 + m < b ? u0 + m : b - 1;
-                    const int64_t word = item0 / 32 + w;
-                    mk[tid] = (mask && word < W) ? mask[ii * W + word] : 0u;
-                }
-                if (tid < IT) {
-                    const int64_t f = item0 + tid < p ? item0 + tid : p - 1;
-                    bs[tid] = item_bias ? item_bias[f] : 0.0;
-                }
-            }
-            for (int c = c0; c < kcn; c += lpr) {
-                const int cc = kc0 + c;
-                for (int it0 = sub; it0 < IT; it0 += 8 * rpp) {
-                    T v[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int64_t f = item0 + it0 + q * rpp;
-                        v[q] = Dt[(f < p ? f : p - 1) * k + (cc < k ? cc : 0)];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int item = it0 + q * rpp;
-                        if (item < IT) Ds[item * ldd + c] = (item0 + item < f_end && cc < k) ? v[q] : (T)0;
-                    }
-                }
-            }
-            __syncthreads();
-            for (int kk = 0; kk < kcn; kk += MT::TK) {
-                const int kr = kk + MT::frag_k(lane);
-                const T bf = Ds[(wid * WN + MT::frag_i(lane)) * ldd + kr];
-#pragma unroll
-                for (int i = 0; i < RM; ++i) {
-                    const T af = Cs[(i * MT::TM + MT::frag_i(lane)) * ldc + kc0 + kr];
-                    acc[i] = MT::mma(af, bf, acc[i]);
-                }
-            }
-        }
+        typename MT::acc_t acc[RM];                          // (its first barrier: the merges of the tile before are done)
+        topn_score_tile(acc, Cs, Ds, mk, bs, L.ldc, L.ldd, Dt, p, k, mask, W, item_bias, item0, f_end, u0, b, sp);
         // selection: this lane's item against the threshold of each of its queries
         {
             const int col = wid * WN + MT::acc_col(lane, 0);
@@ -325,9 +273,7 @@ static int recsys_topn(const T *code, const int64_t *code_rows, int64_t b, int k
     if (ex_indptr) {
         mask = reinterpret_cast<unsigned int *>(base + w.mask);
         MODL_HIP(hipMemsetAsync(mask, 0, sizeof(unsigned int) * (size_t)b * w.W, st));
-        hipLaunchKernelGGL(recsys_topn_mask_kernel, dim3((unsigned)cdiv(b, 4)), dim3(256), 0, st, ex_indptr, ex_indices,
-                           ex_rows, b, p, w.W, mask);
-        MODL_LAUNCH_CHECK();
+        MODL_TRY(launch_recsys_mask(st, ex_indptr, ex_indices, ex_rows, b, p, w.W, INT32_MAX, mask));
     }
     const TopnLds L = topn_lds<T>(k, n_top);
     int32_t *o_items = S == 1 ? items : reinterpret_cast<int32_t *>(base + w.part_items);

@@ -8,23 +8,23 @@ the dispatch, and every leaf of the restatement to at least one point; the same 
 branch of the restatement, marked where it is taken by a call of `_leaf`; the list of all leaves is read out of this file's own
 text.  `UNREACHED` lists, with the reason, the leaves that no point takes.  Lines as of this commit, in modl_amd/csrc:
 G = masked_gram.hip, M = masked_stats.hip, S = somf_step.hip.
-  G:48-52    tile        ntile = ceil(k / 64); ntile (ntile + 1) / 2 workgroups per sample, the upper triangle numbered row by row:
+  G:49-53    tile        ntile = ceil(k / 64); ntile (ntile + 1) / 2 workgroups per sample, the upper triangle numbered row by row:
                          `while (tc >= ntile - ta)`; closed form ta = floor((2 ntile + 1 - sqrt((2 ntile + 1)^2 - 8 t)) / 2),
                          tc = t - ta ntile + ta (ta - 1) / 2 + ta (`gram_tile`, checked against the loop for ntile = 1 .. 16);
-                         ta == tc: diagonal (upper half written to both sides, G:138), else mirrored (G:140-144); ta == 0: the
-                         tile carries Dx (G:82-87, 101-105, 114-122)
-  G:54-57    count       m_i over e < p (never the ldo padding), r_i = p / m_i in the dtype, 0 for an empty row (G:110-112)
-  G:69-88    staging     K-steps of 16 rows of Dt, zeros selected for an unobserved row, for e >= p (K tail p % 16) and for an
+                         ta == tc: diagonal (upper half written to both sides, G:115), else mirrored (G:117-121); ta == 0: the
+                         tile carries Dx (G:77-82, 85-89, 98-106)
+  G:55-58    count       m_i over e < p (never the ldo padding), r_i = p / m_i in the dtype, 0 for an empty row (G:94-96)
+  G:64-83    staging     K-steps of 16 rows of Dt, zeros selected for an unobserved row, for e >= p (K tail p % 16) and for an
                          atom >= k (edge tile k % 64)
-  G:152-159  launches    ceil(b / 65535), the later ones with ii0 into rows, G, Dx and nobs
-  M:193-200  stats       R = 2 (64 x 64 tiles) iff ceil(p / 64) ceil(k / 64) >= 512, else R = 1 (32 x 32); grid ceil(k / BT) x
-                         ceil(p / BT); refusal ceil(p / 64) > 65535 on the R = 2 branch (M:194)
-  M:52-63    observers   NS = 256 / BT row slices: 8 for R = 1 (lanes l and l + 32 folded by the cross-lane exchange), 4 for R = 2
-  M:73-87    staging     K-steps of 16 samples; zeros selected for an unobserved element, a sample >= b (K tail b % 16), a
+  G:129-136  launches    ceil(b / 65535), the later ones with ii0 into rows, G, Dx and nobs
+  M:167-174  stats       R = 2 (64 x 64 tiles) iff ceil(p / 64) ceil(k / 64) >= 512, else R = 1 (32 x 32); grid ceil(k / BT) x
+                         ceil(p / BT); refusal ceil(p / 64) > 65535 on the R = 2 branch (M:168)
+  M:49-60    observers   NS = 256 / BT row slices: 8 for R = 1 (lanes l and l + 32 folded by the cross-lane exchange), 4 for R = 2
+  M:65-79    staging     K-steps of 16 samples; zeros selected for an unobserved element, a sample >= b (K tail b % 16), a
                          feature >= p, an atom >= k
-  M:105-118  weights     seen = feature_n_iter[e] + c_e (read, never written here), w_e = min(1, w (c_e / b) (n_iter / seen)),
+  M:85-98    weights    seen = feature_n_iter[e] + c_e (read, never written here), w_e = min(1, w (c_e / b) (n_iter / seen)),
                          alpha = w_e / c_e, beta = 1 - w_e in f64, rounded to the dtype; c_e = 0: the row is not touched
-  M:138-147  counts      feature_n_iter[e] += c_e where c_e > 0, count[e] = c_e when given, after the product on the stream
+  M:112-121  counts      feature_n_iter[e] += c_e where c_e > 0, count[e] = c_e when given, after the product on the stream
   S:1365-68  chunk rows  clamp(256 MiB / (k k sizeof T), 1, 4096) - HipBackend.masked_chunk_rows in Python
   S:1381-84  workspace   crows = min(chunk rows, max_batch); need_F = ridge codes and 128 < k <= 512 (neither the blocked nor the
                          one-launch factorisation): a second block of crows k k for the factors
@@ -143,7 +143,7 @@ LD = np.longdouble
 BOTH = ('f32', 'f64')
 FILL = 7.5
 EINVAL = -1
-MAX_Y = 65535                                  # samples per launch of masked_gram (G:153), tile rows of masked_stats (M:194)
+MAX_Y = 65535                                  # samples per launch of masked_gram (G:130), tile rows of masked_stats (M:168)
 
 
 def cdiv(a, b):
@@ -166,7 +166,7 @@ def all_leaves():
 
 
 # ---------------------------------------------------------------------------------------------------- the dispatch, restated
-def gram_tile_loop(t, ntile):                  # G:48-50, as written there
+def gram_tile_loop(t, ntile):                  # G:49-51, as written there
     ta, tc = 0, t
     while tc >= ntile - ta:
         tc -= ntile - ta
@@ -190,9 +190,9 @@ def gram_tile(t, ntile):
 
 
 def gram_route(k, p, b, rows):
-    if k < 1 or k > 1024 or p < 1 or b < 0:                                  # G:150
+    if k < 1 or k > 1024 or p < 1 or b < 0:                                  # G:127
         return SimpleNamespace(s=_leaf('gram/einval'), launches=0)
-    ntile = cdiv(k, 64)                                                      # G:152
+    ntile = cdiv(k, 64)                                                      # G:129
     wg = ntile * (ntile + 1) // 2
     kinds = []
     for t in range(wg):
@@ -201,7 +201,7 @@ def gram_route(k, p, b, rows):
             kinds.append(_leaf('gram/diag+dx') if ta == 0 else _leaf('gram/diag'))
         else:
             kinds.append(_leaf('gram/mirrored+dx') if ta == 0 else _leaf('gram/mirrored'))
-    launches = cdiv(b, MAX_Y)                                                # G:154-159
+    launches = cdiv(b, MAX_Y)                                                # G:131-136
     s = 'gram/ntile%d/wg%d/diag%d/dx%d/' % (ntile, wg, sum('diag' in x for x in kinds), sum('+dx' in x for x in kinds))
     s += _leaf('gram/relaunch') if launches > 1 else _leaf('gram/one_launch')
     s += '%d/' % launches
@@ -212,17 +212,17 @@ def gram_route(k, p, b, rows):
 
 
 def stats_route(k, p, b, rows, count):
-    if k < 1 or k > 1024 or p < 1 or b < 0:                                  # M:190
+    if k < 1 or k > 1024 or p < 1 or b < 0:                                  # M:164
         return SimpleNamespace(s=_leaf('stats/einval'), rc=EINVAL)
-    if cdiv(p, 64) * cdiv(k, 64) >= 512:                                     # M:193
-        if cdiv(p, 64) > MAX_Y:                                              # M:194
+    if cdiv(p, 64) * cdiv(k, 64) >= 512:                                     # M:167
+        if cdiv(p, 64) > MAX_Y:                                              # M:168
             return SimpleNamespace(s=_leaf('stats/R2/refused'), rc=EINVAL)
         R, s = 2, _leaf('stats/R2')
     else:
         R, s = 1, _leaf('stats/R1')
     BT = 32 * R
-    grid = (cdiv(k, BT), cdiv(p, BT))                                        # M:195, 198
-    NS = 256 // BT                                                           # M:53
+    grid = (cdiv(k, BT), cdiv(p, BT))                                        # M:169, 172
+    NS = 256 // BT                                                           # M:50
     s += '/grid%dx%d/' % grid
     s += (_leaf('stats/NS8') if NS == 8 else _leaf('stats/NS4')) + '/'
     s += (_leaf('stats/rows') if rows else _leaf('stats/rows_null')) + '/'
@@ -603,7 +603,7 @@ def judge_gram(c, G, Dx, nobs, who=None):
 
 
 def stats_weights(c_e, fni0, w, n_iter, b):
-    """beta_e, alpha_e in f64, the operations in the order of M:110-113"""
+    """beta_e, alpha_e in f64, the operations in the order of M:90-93"""
     c_e = c_e.astype(np.float64)
     with np.errstate(divide='ignore', invalid='ignore'):
         seen = (fni0 + c_e.astype(np.int64)).astype(np.float64)
@@ -776,7 +776,7 @@ def stats_restated(c, dt, mut=(), BT=8, BK=4, NS=8, obs=None, X=None, code_behin
                 new = beta[:, None] * old + alpha[:, None] * acc
                 Bt[(e0 + np.arange(BT))[:, None].repeat(BT, 1)[ok], (a0 + np.arange(BT))[None].repeat(BT, 0)[ok]] = new[ok]
     tally = (lambda v: v == 1) if 'byte2_counts_kernel' in mut else (lambda v: v != 0)
-    ce = tally(ob[rr[:b]][:, :p]).sum(axis=0)                                # masked_counts_kernel (M:138-147)
+    ce = tally(ob[rr[:b]][:, :p]).sum(axis=0)                                # masked_counts_kernel (M:112-121)
     return Bt, fni0 + ce, ce.astype(np.int32)
 
 

@@ -39,9 +39,9 @@ B = bcd.hip.
                          launch_gemm_dense's own kernel is always pipelined (D:415-423)
   D:70-101  TileLoader   a tile inside an aligned operand by 16-byte loads, every other (edge, K tail, misaligned operand)
                          element by element, a lane outside the operand from element [0, 0] (D:97), zeros selected afterwards
-  G:285-329 launch_gemm  tall 128 x 32 (BK 32) when N <= 32, big 128 x 128 when ceil(M/128) ceil(N/128) >= 512, else small
+  G:326-370 launch_gemm  tall 128 x 32 (BK 32) when N <= 32, big 128 x 128 when ceil(M/128) ceil(N/128) >= 512, else small
                          64 x 64 (BK 16); splits = min(target / tiles, max(1, K / 128), max_splits, scratch / (M N)); tall tiles at
-                         least half full, no gather on K: "dense" staging from clamped coordinates (G:159-161, 77-103)
+                         least half full, no gather on K: "dense" staging from clamped coordinates (G:212-214, 135-161)
   D:644-651 plan_stats   f32, 32 x 32 tiles of 16x16x4, K <= 256, no split (resident-K tile, 4 K-tiles of 64)
   W:46-58   plan_wide    16-byte aligned operands, M, N, leading strides % 4 == 0, K <= 256
   S:632-683 stats_pair   f32: resident (plan_stats(C) ok, rows >= 4096, k <= 256, b % 4 == 0, switch on, plan_wide ok; the
@@ -259,7 +259,7 @@ def dense_str(dt, P, paired):
 
 
 def launch_gemm(dt, M, N, K, ws, target=512, max_splits=64, gather_k=False):
-    """G:285-329 and the staging predicate of gemm_kernel (G:159-161): (route string, launches, splits)."""
+    """G:326-370 and the staging predicate of gemm_kernel (G:212-214): (route string, launches, splits)."""
     if N <= 32:
         cfg, bm, bn, bk = 'tall', 128, 32, 32
     elif cdiv(M, 128) * cdiv(N, 128) >= 512:
