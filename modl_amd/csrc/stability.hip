@@ -260,6 +260,10 @@ int am_plan(int dtype, int n, const int64_t *h_k, int64_t p, AmPlan &pl, std::ve
     int64_t ns = 1;
     if (pl.ntiles < kTargetItems) {
         ns = std::min<int64_t>(cdiv(kTargetItems, pl.ntiles), p / kMinSplitK);
+        // (a guard that cannot bind at these constants: t < 512 tiles take at most ceil(512 / t) splits, under 1 023
+        //  tile-splits of BM * BM * es = 64 KiB (f32) or 32 KiB (f64), 64 MiB in all, and floor(4096 / t) >= ceil(512 / t) for
+        //  every such t - tests/test_stability_routes.py::test_partial_cap_cannot_bind enumerates them.  It stays for the day
+        //  kTargetItems, the tile size or the cap changes.)
         ns = std::min<int64_t>(ns, kMaxPartialBytes / (pl.ntiles * BM * BM * (int64_t)es));
         ns = std::max<int64_t>(ns, 1);
     }
