@@ -528,8 +528,7 @@ extern std::atomic<int> g_stage_ahead;                  // somf_step.hip
 template <typename T>
 int launch_cd(hipStream_t stream, const CdArgs<T> &a0) {
     if (a0.b <= 0 || a0.k <= 0) return MODL_OK;
-    if (a0.k > MODL_MAX_COMPONENTS) return MODL_EINVAL;
-    if (a0.k > 1024) return launch_cd_wide<T>(stream, a0);          // (cd_wide.hip: the k-vectors in LDS)
+    if (a0.k > 1024) return MODL_EINVAL;                            // (code_solve.hip sends those to cd_wide.hip)
     CdArgs<T> a = a0;
     const int sparse_pct = g_cd_sparse_pct.load(std::memory_order_relaxed);   // diagnostics: modl_debug_set
     if (sparse_pct >= 0) a.sparse_pct = sparse_pct;

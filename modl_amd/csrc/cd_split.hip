@@ -13,16 +13,18 @@ template void launch_split_nb<float, 4>(hipStream_t, const CdArgs<float> &);
 
 // the split solver takes a Gram matrix whose row stride is 128 / 256 / 512 / 1024 (any k up to it: the padding is dead
 // coordinates), shared or one per sample; no readable rows behind it are needed (its prefetch wraps around inside the sweep)
-template <typename T>
-bool cd_split_applies(const CdArgs<T> &a) {
-    const int kq = a.ldg ? a.ldg : a.k;
+bool cd_split_takes(size_t tsz, int k, int kq, int64_t g_stride, bool g_aligned16) {
     // a matrix per sample (G_agg = 'average'): every matrix 16-byte aligned; k itself one of the strides (solved where
     // the matrices are stored) or zero-padded copies of a slice of the minibatch (launch_cd_per_sample, cd_solver.hip)
-    if (a.g_stride != 0 && (a.g_stride * (int64_t)sizeof(T)) % 16 != 0) return false;
+    if (g_stride != 0 && (g_stride * (int64_t)tsz) % 16 != 0) return false;
     if (kq != 128 && kq != 256 && kq != 512 && kq != 1024) return false;
-    if (a.k <= kq / 2 && kq > 128) return false;                  // (a smaller stride serves it)
-    if (a.k < 32) return false;
-    return reinterpret_cast<uintptr_t>(a.G) % 16 == 0;
+    if (k <= kq / 2 && kq > 128) return false;                    // (a smaller stride serves it)
+    if (k < 32) return false;
+    return g_aligned16;
+}
+template <typename T>
+bool cd_split_applies(const CdArgs<T> &a) {
+    return cd_split_takes(sizeof(T), a.k, a.ldg ? a.ldg : a.k, a.g_stride, reinterpret_cast<uintptr_t>(a.G) % 16 == 0);
 }
 
 template <typename T>

@@ -34,6 +34,8 @@ template <typename T> int launch_cd(hipStream_t stream, const CdArgs<T> &a);
 template <typename T> int launch_cd_wide(hipStream_t stream, const CdArgs<T> &a);
 // cd_split.hip: the same solver with the chain and the k-wide update on two wavefronts (shared Gram, 64 < k <= 512)
 template <typename T> bool cd_split_applies(const CdArgs<T> &a);
+// ... what it reads: element size, k, the row stride kq of G, g_stride, G on a 16-byte boundary
+bool cd_split_takes(size_t tsz, int k, int kq, int64_t g_stride, bool g_aligned16);
 template <typename T> int launch_cd_split(hipStream_t stream, const CdArgs<T> &a);
 // a Gram matrix PER SAMPLE whose size is not one of the solver's strides: slices of the minibatch through zero-padded
 // copies (slots: scratch of cd_per_sample_scratch_bytes, zero outside the k x k corners - zero-filled once per k)
@@ -74,6 +76,49 @@ bool chol_blocked(int k, size_t tsz, bool shared);   // which ridge systems take
 template <typename T>
 int ridge_solve_wide(hipStream_t stream, const T *G, int64_t g_stride, const int64_t *h_gidx, T *F, T *Linv, T *rhs, int b,
                      int k, T alpha, T *code, const int64_t *d_idx);
+
+// ---- code_solve.hip ---------------------------------------------------------
+// Which kernels solve for the codes of a minibatch: decided here and nowhere else, for the step (somf_step.hip) and for
+// modl_enet_regression_* alike.
+enum CodeRoute {                  // (the ridge leaves first: code_solve tells the two families apart by that)
+    CODE_RIDGE_BLOCKED,   // ridge_solve_wide: blocked factorisation and substitutions on the matrix cores
+    CODE_RIDGE_SMALL,     // launch_ridge_small: factor + substitutions in one launch, in LDS
+    CODE_RIDGE_FACTOR,    // launch_cholesky, then launch_chol_solve
+    CODE_CD_WIDE,         // k > 1024: launch_cd_wide, shared or per-sample Gram as stored
+    CODE_CD_SLOTS,        // a Gram per sample of a size the four-wavefront solver does not take as stored: launch_cd_per_sample
+    CODE_CD_PADDED,       // a shared Gram copied into a zero-padded matrix of the vectorised solver's stride, then launch_cd
+    CODE_CD_STORED,       // launch_cd on the matrices where they are
+};
+// pure: tsz = sizeof(T), g_stride = 0 for a shared Gram, g_aligned16 = G sits on a 16-byte boundary, split_enabled /
+// one_wave_covers = cd_split_enabled() / cd_one_wave_covers(k) (arguments, so that a size can be asked for whatever the
+// diagnostics switch says).  The size of the minibatch plays no part.
+CodeRoute code_route(size_t tsz, int k, double l1_ratio, int64_t g_stride, bool g_aligned16, bool split_enabled,
+                     bool one_wave_covers);
+template <typename T> inline CodeRoute code_route_of(const T *G, int64_t g_stride, int k, double l1_ratio) {
+    return code_route(sizeof(T), k, l1_ratio, g_stride, reinterpret_cast<uintptr_t>(G) % 16 == 0, cd_split_enabled(),
+                      cd_one_wave_covers(k));
+}
+// what the leaves need besides the operands; each caller fills it from its own memory
+template <typename T>
+struct CodeScratch {
+    T *F = nullptr, *Linv = nullptr;      // Cholesky factor(s); chol_wide_scratch_elems(k) for the blocked leaf
+    T *H0 = nullptr;                      // [b][k]
+    T *Gpad = nullptr; int ld_gpad = 0;   // [ld_gpad + 16][ld_gpad], zero outside the k x k corner (null: nothing is padded)
+    size_t gpad_zero_bytes = 0;           // != 0: zero-fill that much of Gpad now (0: the caller did, once)
+    T *slots = nullptr; size_t slots_bytes = 0;   // launch_cd_per_sample's scratch
+    bool slots_zero = false;              // zero-fill it now
+    int g_pad_rows = 0;                   // CdArgs::g_pad_rows of a shared Gram that is solved as stored
+    // H0 = code G of a shared Gram by a product launch of its own instead of inside the solver.  The wide solver needs it;
+    // modl_enet_regression_* also asks for it at every other size, the step does not: the two sum in different orders,
+    // and each caller keeps the bits it has always returned.
+    bool h0_by_product = false;
+};
+// a: the operands and tol, max_iter, positive as for launch_cd (code2 / idx2: the optional second destination, written by
+// every leaf); Dx, H0, ldg, g_pad_rows, alpha and beta are set here.  Dx [b][k]: the ridge leaves solve in place.  h_gidx:
+// g_idx on the host (the blocked ridge leaf walks per-sample matrices from there).  launches: optional counter.
+template <typename T>
+int code_solve(hipStream_t stream, CdArgs<T> a, T *Dx, T code_alpha, double l1_ratio, const int64_t *h_gidx,
+               const CodeScratch<T> &sc, int *launches);
 
 // ---- enet.hip ---------------------------------------------------------------
 template <typename T>

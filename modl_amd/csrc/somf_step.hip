@@ -1,5 +1,5 @@
-// The fused, device-resident SOMF minibatch step and the fine-grained solver
-// entry points of the C-ABI (include/modl_hip.h).
+// The fused, device-resident SOMF minibatch step of the C-ABI (include/modl_hip.h); the code solve it
+// calls, and the entry points that expose that solve alone, are in code_solve.hip.
 //
 // Replaces DictFact._single_batch_fit and what it calls
 //   (reference: modl/decomposition/dict_fact.py:495-533 _single_batch_fit,
@@ -534,92 +534,34 @@ int gram_of_rows(modl_somf_plan *pl, hipStream_t st, const T *Dt, const int32_t 
     return launch_gemm<T, Epi>(st, A, A, pl->d.k, pl->d.k, s, epi, ws, nl);
 }
 
+// The code solve (code_solve.hip decides the kernels) with the plan's scratch.  Fbuf: off_F, or the masked step's factors.
 template <typename T>
 int solve_codes(modl_somf_plan *pl, hipStream_t st, const T *G, int64_t g_stride, const int64_t *g_idx, T *Dx,
-                const T *xnorm2, T *code, const int64_t *d_idx, int b, int32_t *d_sweeps, int *nl, T *H0buf, T *Fbuf,
+                const T *xnorm2, T *code, const int64_t *d_idx, int b, int32_t *d_sweeps, int *nl, T *Fbuf,
                 T *scatter_dst = nullptr, const int64_t *scatter_idx = nullptr, const int64_t *h_gidx = nullptr) {
     const modl_somf_desc &d = pl->d;
-    const int k = d.k;
-    if (d.code_l1_ratio == 0.0 && chol_blocked(k, sizeof(T), g_stride == 0)) {   // blocked, on the matrix cores
-        if (g_stride && g_idx && !h_gidx) return MODL_EINVAL;         // per-sample Grams are walked from the host
-        T *Linv = reinterpret_cast<T *>(pl->dws + pl->off_Linv);
-        MODL_TRY(ridge_solve_wide<T>(st, G, g_stride, h_gidx, Fbuf, Linv, Dx, b, k, (T)d.code_alpha, code, d_idx));
-        *nl += 2;
-        if (scatter_dst) {
-            hipLaunchKernelGGL((scatter_rows_T_kernel<T, int64_t>), dim3((unsigned)b), dim3(256), 0, st, scatter_dst,
-                               (int64_t)k, scatter_idx, (int64_t)b, (int64_t)k, Dx, (int64_t)k);
-            MODL_LAUNCH_CHECK();
-            ++*nl;
-        }
-        return MODL_OK;
-    }
-    if (d.code_l1_ratio == 0.0) {                                     // ridge: dict_fact_fast.pyx:82-94, 174-197
-        const int nmat = g_stride ? b : 1;
-        if (ridge_small_applies<T>(k)) {                              // factor + substitutions in one launch, in LDS
-            MODL_TRY(launch_ridge_small<T>(st, G, g_stride, g_idx, Dx, b, k, (T)d.code_alpha, code, d_idx));
-            *nl += 1;
-        } else {
-            MODL_TRY(launch_cholesky<T>(st, G, g_stride, g_idx, Fbuf, k, (T)d.code_alpha, nmat));
-            MODL_TRY(launch_chol_solve<T>(st, Fbuf, g_stride ? (int64_t)k * k : 0, Dx, b, k, code, d_idx));
-            *nl += 2;
-        }
-        if (scatter_dst) {
-            hipLaunchKernelGGL((scatter_rows_T_kernel<T, int64_t>), dim3((unsigned)b), dim3(256), 0, st, scatter_dst,
-                               (int64_t)k, scatter_idx, (int64_t)b, (int64_t)k, code, (int64_t)k);
-            MODL_LAUNCH_CHECK();
-            ++*nl;
-        }
-        return MODL_OK;
-    }
-    // H0 = Q w is formed inside the solver (rows stream through its prefetch ring: ~6 us at k = 256, less
-    // than the launch of a separate 256 x 256 x 256 product that only occupies 16 workgroups)
-    const T *H0 = nullptr;
-    (void)H0buf;
     CdArgs<T> a;
-    a.G = G; a.g_stride = g_stride; a.g_idx = g_idx; a.Dx = Dx; a.xnorm2 = xnorm2; a.H0 = H0; a.code = code;
-    a.idx = d_idx;
+    a.G = G; a.g_stride = g_stride; a.g_idx = g_idx; a.xnorm2 = xnorm2; a.code = code; a.idx = d_idx;
     a.code2 = scatter_dst; a.idx2 = scatter_idx;
-    a.g_pad_rows = (G == reinterpret_cast<const T *>(pl->dws + pl->off_G)) ? 16 : 0;
-    if (!g_stride && pl->ld_gpad && k <= 1024) { // any k on the vectorised kernel (cd_solver.hip: cd_padded_ld)
-        T *Gp = reinterpret_cast<T *>(pl->dws + pl->off_Gpad);
-        MODL_TRY(launch_cd_pad_gram<T>(st, G, k, Gp, pl->ld_gpad));
-        ++*nl;
-        a.G = Gp; a.ldg = pl->ld_gpad; a.g_pad_rows = 16;
-    }
-    a.sweeps = d_sweeps; a.b = b; a.k = k;
-    a.alpha = (T)((T)d.code_alpha * (T)d.code_l1_ratio);
-    a.beta = (T)((double)(T)d.code_alpha * (1.0 - (double)(T)d.code_l1_ratio));
+    a.sweeps = d_sweeps; a.b = b; a.k = d.k;
     a.tol = (T)d.tol; a.max_iter = d.max_iter; a.positive = d.code_pos;
-    if (k > 1024) {                              // wide dictionaries, shared or per-sample Gram as stored (cd_wide.hip)
-        a.G = G; a.ldg = 0; a.g_pad_rows = 0;
-        if (!g_stride) {                         // H0 = code G on the matrix cores: k rows per sample, not streamed by one CU
-            Operand A, B;
-            A.ptr = code; A.si = k; A.sk = 1; A.gi = gather64(d_idx);
-            B.ptr = G; B.si = k; B.sk = 1;
-            EpiStore<T> epi{H0buf, k, (T)1};
-            SplitWs none;
-            MODL_TRY((launch_gemm<T, EpiStore<T>>(st, A, B, b, k, k, epi, none, nl, 512, 1)));
-            a.H0 = H0buf;
-        }
-        MODL_TRY(launch_cd_wide<T>(st, a));
-        ++*nl;
-        return MODL_OK;
+    const CodeRoute route = code_route_of<T>(G, g_stride, d.k, d.code_l1_ratio);
+    CodeScratch<T> sc;
+    sc.F = Fbuf;
+    sc.Linv = reinterpret_cast<T *>(pl->dws + pl->off_Linv);
+    sc.H0 = reinterpret_cast<T *>(pl->dws + pl->off_H0);
+    if (pl->ld_gpad) sc.Gpad = reinterpret_cast<T *>(pl->dws + pl->off_Gpad);   // (zero-filled when the plan was created)
+    sc.ld_gpad = pl->ld_gpad;
+    sc.g_pad_rows = (G == reinterpret_cast<const T *>(pl->dws + pl->off_G)) ? 16 : 0;
+    sc.h0_by_product = route == CODE_CD_WIDE;
+    if (route == CODE_CD_SLOTS && !pl->Gslots) {
+        pl->Gslots_bytes = cd_per_sample_scratch_bytes(sizeof(T), d.max_batch, d.k);
+        MODL_HIP(hipMalloc(&pl->Gslots, pl->Gslots_bytes));
+        sc.slots_zero = true;
     }
-    if (g_stride && k >= 32 && (cd_split_enabled() || !cd_one_wave_covers(k)) && !cd_split_applies<T>(a)) {
-        // a Gram matrix per sample of a size the four-wavefront solver does not take as stored: zero-padded copies,
-        // a slice of the minibatch at a time (cd_solver.hip: launch_cd_per_sample)
-        if (!pl->Gslots) {
-            pl->Gslots_bytes = cd_per_sample_scratch_bytes(sizeof(T), d.max_batch, k);
-            MODL_HIP(hipMalloc(&pl->Gslots, pl->Gslots_bytes));
-            MODL_HIP(hipMemsetAsync(pl->Gslots, 0, pl->Gslots_bytes, st));
-        }
-        MODL_TRY(launch_cd_per_sample<T>(st, a, static_cast<T *>(pl->Gslots), pl->Gslots_bytes));
-        *nl += 2;
-        return MODL_OK;
-    }
-    MODL_TRY(launch_cd<T>(st, a));
-    ++*nl;
-    return MODL_OK;
+    sc.slots = static_cast<T *>(pl->Gslots);
+    sc.slots_bytes = pl->Gslots_bytes;
+    return code_solve<T>(st, a, Dx, (T)d.code_alpha, d.code_l1_ratio, h_gidx, sc, nl);
 }
 
 constexpr int64_t kResidentMinRows = 4096;
@@ -707,7 +649,6 @@ int phase1(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_batch
     T *code = static_cast<T *>(stt->d_code);
     T *xnorm = reinterpret_cast<T *>(pl->dws + pl->off_xnorm);
     T *Dx = reinterpret_cast<T *>(pl->dws + pl->off_Dx);
-    T *H0 = reinterpret_cast<T *>(pl->dws + pl->off_H0);
     T *Gbuf = reinterpret_cast<T *>(pl->dws + pl->off_G);
     T *Fbuf = reinterpret_cast<T *>(pl->dws + pl->off_F);
     SplitWs sws{pl->dws + pl->off_split, pl->split_bytes};
@@ -839,14 +780,14 @@ int phase1(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_batch
         if (d.G_agg == MODL_AGG_AVERAGE) {                            // per-sample Gram = rows idx of G_average_
             const T *Gavg = static_cast<const T *>(stt->d_G_average);
             MODL_TRY(solve_codes<T>(pl, st, Gavg, (int64_t)k * k, d_idx, Dx, xnorm, code, d_idx, b, d_sweeps,
-                                    &ps.launches, H0, Fbuf, nullptr, nullptr, bt->h_sample_idx));
+                                    &ps.launches, Fbuf, nullptr, nullptr, bt->h_sample_idx));
         } else {
             const T *G = (d.G_agg == MODL_AGG_FULL) ? static_cast<const T *>(stt->d_G) : Gbuf;
             if (cd_on_compact) {     // solve on the compact rows, the solver also writes code_[idx]
-                MODL_TRY(solve_codes<T>(pl, st, G, 0, nullptr, Dx, xnorm, cb, nullptr, b, d_sweeps, &ps.launches, H0, Fbuf,
+                MODL_TRY(solve_codes<T>(pl, st, G, 0, nullptr, Dx, xnorm, cb, nullptr, b, d_sweeps, &ps.launches, Fbuf,
                                         d_idx ? code : nullptr, d_idx));
             } else {
-                MODL_TRY(solve_codes<T>(pl, st, G, 0, nullptr, Dx, xnorm, code, d_idx, b, d_sweeps, &ps.launches, H0, Fbuf));
+                MODL_TRY(solve_codes<T>(pl, st, G, 0, nullptr, Dx, xnorm, code, d_idx, b, d_sweeps, &ps.launches, Fbuf));
             }
         }
     }
@@ -1008,46 +949,12 @@ int phase2(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_batch
     return MODL_OK;
 }
 
-template <typename T>
-int transform_impl(modl_somf_plan *pl, const T *Dt, const T *G, const T *X, int64_t ldx, int64_t n, T *code_out,
-                   hipStream_t st) {
-    const modl_somf_desc &d = pl->d;
-    const int k = d.k;
-    const int64_t p = d.p;
-    T *xnorm = reinterpret_cast<T *>(pl->dws + pl->off_xnorm);
-    T *Dx = reinterpret_cast<T *>(pl->dws + pl->off_Dx);
-    T *H0 = reinterpret_cast<T *>(pl->dws + pl->off_H0);
-    T *Gbuf = reinterpret_cast<T *>(pl->dws + pl->off_G);
-    T *Fbuf = reinterpret_cast<T *>(pl->dws + pl->off_F);
-    SplitWs sws{pl->dws + pl->off_split, pl->split_bytes};
-    int nl = 0;
-    if (!G) {                                                         // dict_fact.py:67-70
-        EpiStore<T> epi{Gbuf, k, (T)1};
-        MODL_TRY((gram_of_rows<T, EpiStore<T>>(pl, st, Dt, nullptr, p, epi, &nl)));
-        G = Gbuf;
-    }
-    hipLaunchKernelGGL((fill_kernel<T>), dim3((unsigned)std::min<int64_t>(cdiv(n * k, 256), 2048)), dim3(256), 0, st,
-                       code_out, n * k, (T)1);                        // code = ones (:72)
-    MODL_LAUNCH_CHECK();
-    for (int64_t r0 = 0; r0 < n; r0 += d.max_batch) {
-        const int b = (int)std::min<int64_t>(d.max_batch, n - r0);
-        const T *Xb = X + r0 * ldx;
-        if (d.code_l1_ratio != 0.0) MODL_TRY(launch_row_norm2<T>(st, Xb, ldx, p, b, xnorm));
-        DenseOperand A, B;
-        A.ptr = Xb; A.si = ldx; A.sk = 1;
-        B.ptr = Dt; B.si = 1; B.sk = k;
-        EpiStore<T> epi{Dx, k, (T)1};
-        MODL_TRY((launch_gemm_dense<T, EpiStore<T>>(st, A, B, b, k, p, epi, sws, &nl)));
-        MODL_TRY(solve_codes<T>(pl, st, G, 0, nullptr, Dx, xnorm, code_out + r0 * k, nullptr, b, nullptr, &nl, H0, Fbuf));
-    }
-    return MODL_OK;
-}
-
-// transform_impl with the OMP coder (omp.hip) in the place of solve_codes: nothing is warm-started, the kernel writes
-// every element of its outputs
-template <typename T>
-int transform_omp_impl(modl_somf_plan *pl, const T *Dt, const T *G, const T *X, int64_t ldx, int64_t n, int n_nonzero, T tol,
-                       T *code_out, int32_t *support_out, int32_t *n_active_out, hipStream_t st) {
+// The chunk loop of both transforms (dict_fact.py:47-92): the Gram matrix unless it is given (:67-70), then for every
+// max_batch rows their squared norms (where the coder reads them), Dx and solve(G, xnorm, Dx, r0, b, &launches), the coder's
+// own call for rows r0 .. r0 + b.  ones: the warm starts to fill with ones first (:72), or null.
+template <typename T, class Solve>
+int transform_chunks(modl_somf_plan *pl, const T *Dt, const T *G, const T *X, int64_t ldx, int64_t n, T *ones, bool norms,
+                     hipStream_t st, const Solve &solve) {
     const modl_somf_desc &d = pl->d;
     const int k = d.k;
     const int64_t p = d.p;
@@ -1055,92 +962,53 @@ int transform_omp_impl(modl_somf_plan *pl, const T *Dt, const T *G, const T *X, 
     T *Dx = reinterpret_cast<T *>(pl->dws + pl->off_Dx);
     T *Gbuf = reinterpret_cast<T *>(pl->dws + pl->off_G);
     SplitWs sws{pl->dws + pl->off_split, pl->split_bytes};
-    const bool use_tol = tol >= (T)0;
     int nl = 0;
     if (!G) {
         EpiStore<T> epi{Gbuf, k, (T)1};
         MODL_TRY((gram_of_rows<T, EpiStore<T>>(pl, st, Dt, nullptr, p, epi, &nl)));
         G = Gbuf;
     }
+    if (ones) {
+        hipLaunchKernelGGL((fill_kernel<T>), dim3((unsigned)std::min<int64_t>(cdiv(n * k, 256), 2048)), dim3(256), 0, st,
+                           ones, n * k, (T)1);
+        MODL_LAUNCH_CHECK();
+    }
     for (int64_t r0 = 0; r0 < n; r0 += d.max_batch) {
         const int b = (int)std::min<int64_t>(d.max_batch, n - r0);
         const T *Xb = X + r0 * ldx;
-        if (use_tol) MODL_TRY(launch_row_norm2<T>(st, Xb, ldx, p, b, xnorm));
+        if (norms) MODL_TRY(launch_row_norm2<T>(st, Xb, ldx, p, b, xnorm));
         DenseOperand A, B;
         A.ptr = Xb; A.si = ldx; A.sk = 1;
         B.ptr = Dt; B.si = 1; B.sk = k;
         EpiStore<T> epi{Dx, k, (T)1};
         MODL_TRY((launch_gemm_dense<T, EpiStore<T>>(st, A, B, b, k, p, epi, sws, &nl)));
-        MODL_TRY(launch_omp<T>(st, G, 0, Dx, use_tol ? xnorm : nullptr, b, k, n_nonzero, tol, code_out + r0 * k,
-                               support_out ? support_out + r0 * n_nonzero : nullptr,
-                               n_active_out ? n_active_out + r0 : nullptr));
+        MODL_TRY(solve(G, xnorm, Dx, r0, b, &nl));
     }
     return MODL_OK;
 }
 
 template <typename T>
-int enet_regression_abi(const T *G, int64_t g_stride, T *Dx, const T *X, int64_t ldx, int64_t p, T *code,
-                        const int64_t *d_indices, int64_t b, int64_t k, T l1_ratio, T alpha, int positive, T tol,
-                        int max_iter, int32_t *d_sweeps, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!G || !Dx || !X || !code || b < 0 || k <= 0 || k > MODL_MAX_COMPONENTS || p < 0 || ldx < p) return MODL_EINVAL;
-    if (!(l1_ratio >= 0 && l1_ratio <= 1)) return MODL_EINVAL;
-    if (b == 0) return MODL_OK;
-    const size_t need = modl_enet_regression_workspace(DType<T>::id, b, k, g_stride != 0);
-    if (!d_ws || ws_bytes < need) return MODL_ENOMEM;
-    hipStream_t st = (hipStream_t)stream;
-    char *w = static_cast<char *>(d_ws);
-    T *xnorm = reinterpret_cast<T *>(w);
-    T *H0 = reinterpret_cast<T *>(w + align_up(sizeof(T) * (size_t)b, 256));
-    T *F = reinterpret_cast<T *>(w + align_up(sizeof(T) * (size_t)b, 256) + align_up(sizeof(T) * (size_t)b * k, 256));
-    if (l1_ratio == 0 && chol_blocked((int)k, sizeof(T), g_stride == 0)) {
-        T *Linv = F + (size_t)k * k;
-        return ridge_solve_wide<T>(st, G, g_stride, nullptr, F, Linv, Dx, (int)b, (int)k, alpha, code, d_indices);
-    }
-    if (l1_ratio == 0) {
-        const int nmat = g_stride ? (int)b : 1;
-        if (ridge_small_applies<T>((int)k))
-            return launch_ridge_small<T>(st, G, g_stride, nullptr, Dx, (int)b, (int)k, alpha, code, d_indices);
-        MODL_TRY(launch_cholesky<T>(st, G, g_stride, nullptr, F, (int)k, alpha, nmat));
-        return launch_chol_solve<T>(st, F, g_stride ? k * k : 0, Dx, (int)b, (int)k, code, d_indices);
-    }
-    MODL_TRY(launch_row_norm2<T>(st, X, ldx, p, b, xnorm));
-    const T *H0p = nullptr;
-    if (g_stride == 0) {
-        Operand A, B;
-        A.ptr = code; A.si = k; A.sk = 1; A.gi = gather64(d_indices);
-        B.ptr = G; B.si = k; B.sk = 1;
-        EpiStore<T> epi{H0, k, (T)1};
-        SplitWs none;
-        MODL_TRY((launch_gemm<T, EpiStore<T>>(st, A, B, b, k, k, epi, none, nullptr, 512, 1)));
-        H0p = H0;
-    }
-    CdArgs<T> a;
-    a.G = G; a.g_stride = g_stride; a.g_idx = nullptr; a.Dx = Dx; a.xnorm2 = xnorm; a.H0 = H0p; a.code = code;
-    a.idx = d_indices;
-    a.sweeps = d_sweeps; a.b = (int)b; a.k = (int)k;
-    // any k on the vectorised kernel: padded copy at the end of the caller's workspace.  Also for k = 512 / 1024 when the
-    // caller's matrix is not 16-byte aligned: beyond 256 coefficients only the four-wavefront solver exists in the product
-    // build, and it wants aligned rows (such a call used to end in MODL_EINVAL)
-    const bool g_misaligned = reinterpret_cast<uintptr_t>(G) % 16 != 0;
-    if (!g_stride && k <= 1024 && (cd_padded_ld((int)k) != (int)k || (k > 256 && g_misaligned))) {
-        const int kq = cd_padded_ld((int)k);
-        const size_t gp_bytes = align_up(sizeof(T) * ((size_t)kq + 16) * kq, 256);
-        T *Gp = reinterpret_cast<T *>(w + need - gp_bytes);
-        MODL_HIP(hipMemsetAsync(Gp, 0, gp_bytes, st));
-        MODL_TRY(launch_cd_pad_gram<T>(st, G, (int)k, Gp, kq));
-        a.G = Gp; a.ldg = kq; a.g_pad_rows = 16;
-    }
-    a.alpha = alpha * l1_ratio;
-    a.beta = (T)((double)alpha * (1.0 - (double)l1_ratio));
-    a.tol = tol; a.max_iter = max_iter; a.positive = positive;
-    if (k > 1024) return launch_cd_wide<T>(st, a);   // any Gram as stored, H0 from the product above (cd_wide.hip)
-    if (g_stride && k >= 32 && k <= 1024 && (cd_split_enabled() || !cd_one_wave_covers((int)k)) && !cd_split_applies<T>(a)) {  // one Gram matrix per sample, any k: zero-padded slots
-        const size_t slot_bytes = cd_per_sample_scratch_bytes(sizeof(T), b, (int)k);   // (at the end of the workspace)
-        T *slots = reinterpret_cast<T *>(w + need - align_up(slot_bytes, 256));
-        MODL_HIP(hipMemsetAsync(slots, 0, slot_bytes, st));
-        return launch_cd_per_sample<T>(st, a, slots, slot_bytes);
-    }
-    return launch_cd<T>(st, a);
+int transform_impl(modl_somf_plan *pl, const T *Dt, const T *G, const T *X, int64_t ldx, int64_t n, T *code_out,
+                   hipStream_t st) {
+    return transform_chunks<T>(pl, Dt, G, X, ldx, n, code_out, pl->d.code_l1_ratio != 0.0, st,
+                               [&](const T *Gm, const T *xnorm, T *Dx, int64_t r0, int b, int *nl) {
+        return solve_codes<T>(pl, st, Gm, 0, nullptr, Dx, xnorm, code_out + r0 * pl->d.k, nullptr, b, nullptr, nl,
+                              reinterpret_cast<T *>(pl->dws + pl->off_F));
+    });
+}
+
+// the OMP coder (omp.hip) in the place of solve_codes: nothing is warm-started, the kernel writes every element of its
+// outputs
+template <typename T>
+int transform_omp_impl(modl_somf_plan *pl, const T *Dt, const T *G, const T *X, int64_t ldx, int64_t n, int n_nonzero, T tol,
+                       T *code_out, int32_t *support_out, int32_t *n_active_out, hipStream_t st) {
+    const bool use_tol = tol >= (T)0;
+    return transform_chunks<T>(pl, Dt, G, X, ldx, n, (T *)nullptr, use_tol, st,
+                               [&](const T *Gm, const T *xnorm, T *Dx, int64_t r0, int b, int *) {
+        return launch_omp<T>(st, Gm, 0, Dx, use_tol ? xnorm : nullptr, b, pl->d.k, n_nonzero, tol, code_out + r0 * pl->d.k,
+                             support_out ? support_out + r0 * n_nonzero : nullptr,
+                             n_active_out ? n_active_out + r0 : nullptr);
+    });
 }
 
 }  // namespace
@@ -1152,35 +1020,6 @@ int modl_device_count(void) {
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
-
-size_t modl_enet_regression_workspace(int dtype, int64_t b, int64_t k, int multi_gram) {
-    const size_t t = dtype == MODL_F32 ? 4 : 8;
-    if (b < 0 || k < 0) return 0;
-    const size_t kq = (!multi_gram && k > 0 && k <= 1024) ? (size_t)modl::cd_padded_ld((int)k) : 0;   // padded shared Gram (cd_padded_ld)
-    const size_t slots = (multi_gram && k >= 32 && k <= 1024) ? align_up(modl::cd_per_sample_scratch_bytes(t, b, (int)k), 256) : 0;
-    return align_up(t * (size_t)b, 256) + align_up(t * (size_t)b * k, 256) +
-           align_up(t * ((size_t)k * k * ((multi_gram && k <= 512) ? (size_t)b : 1) + modl::chol_wide_scratch_elems((int)k)), 256) +
-           ((kq && (kq != (size_t)k || k > 256)) ? align_up(t * (kq + 16) * kq, 256) : 0) + slots;   // (k > 256: a misaligned matrix is copied too)
-}
-
-#define ABI_REG(SFX, T)                                                                                            \
-    int modl_enet_regression_single_gram_##SFX(const T *d_G, T *d_Dx, const T *d_X, int64_t ldx, int64_t p,        \
-                                               T *d_code, const int64_t *d_indices, int64_t b, int64_t k,          \
-                                               T l1_ratio, T alpha, int positive, T tol, int max_iter,             \
-                                               int32_t *d_sweeps, void *d_ws, size_t ws_bytes, void *stream) {     \
-        return enet_regression_abi<T>(d_G, 0, d_Dx, d_X, ldx, p, d_code, d_indices, b, k, l1_ratio, alpha,          \
-                                      positive, tol, max_iter, d_sweeps, d_ws, ws_bytes, stream);                  \
-    }                                                                                                              \
-    int modl_enet_regression_multi_gram_##SFX(const T *d_G, T *d_Dx, const T *d_X, int64_t ldx, int64_t p,         \
-                                              T *d_code, const int64_t *d_indices, int64_t b, int64_t k,           \
-                                              T l1_ratio, T alpha, int positive, T tol, int max_iter,              \
-                                              int32_t *d_sweeps, void *d_ws, size_t ws_bytes, void *stream) {      \
-        return enet_regression_abi<T>(d_G, k * k, d_Dx, d_X, ldx, p, d_code, d_indices, b, k, l1_ratio, alpha,      \
-                                      positive, tol, max_iter, d_sweeps, d_ws, ws_bytes, stream);                  \
-    }
-ABI_REG(f32, float)
-ABI_REG(f64, double)
-#undef ABI_REG
 
 int64_t modl_somf_delta_elems(const modl_somf_desc *desc) {
     if (!desc) return 0;
@@ -1379,7 +1218,7 @@ int masked_step(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_
     const int64_t p = d.p;
     // the chunk's scratch: [c][k][k] Gram matrices (+ as many factors for the mid-size ridge systems) + [b] counts
     const int64_t crows = std::min<int64_t>(masked_chunk_rows(k, sizeof(T)), d.max_batch);
-    const bool need_F = d.code_l1_ratio == 0.0 && !chol_blocked(k, sizeof(T), false) && !ridge_small_applies<T>(k);
+    const bool need_F = code_route_of<T>((const T *)nullptr, (int64_t)k * k, k, d.code_l1_ratio) == CODE_RIDGE_FACTOR;   // (wherever Gc lands)
     const size_t g_bytes = align_up(sizeof(T) * (size_t)crows * k * k, 256);
     const size_t need = g_bytes * (need_F ? 2 : 1) + align_up(sizeof(int32_t) * (size_t)d.max_batch, 256);
     if (pl->masked_ws_bytes < need) {
@@ -1405,7 +1244,6 @@ int masked_step(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_
     T *code = static_cast<T *>(stt->d_code);
     T *xnorm = reinterpret_cast<T *>(pl->dws + pl->off_xnorm);
     T *Dx = reinterpret_cast<T *>(pl->dws + pl->off_Dx);
-    T *H0 = reinterpret_cast<T *>(pl->dws + pl->off_H0);
     T *codeb = reinterpret_cast<T *>(pl->dws + pl->off_codeb);
     T *Gc = static_cast<T *>(pl->masked_ws);
     T *Fc = need_F ? reinterpret_cast<T *>(static_cast<char *>(pl->masked_ws) + g_bytes)
@@ -1430,7 +1268,7 @@ int masked_step(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_
             // starts and receive the solutions
             MODL_TRY(solve_codes<T>(pl, st, Gc, (int64_t)k * k, nullptr, Dx + r0 * k, xnorm + r0,
                                     d_idx ? code : code + r0 * k, d_idx ? d_idx + r0 : nullptr, c, d_sweeps + r0,
-                                    &ps.launches, H0, Fc));
+                                    &ps.launches, Fc));
         }
     }
     {

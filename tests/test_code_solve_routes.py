@@ -3,30 +3,30 @@
 enet_regression_*_gram on inputs built to leave the main branch of enet_coordinate_descent_gram.
 
 ROUTES (`ROUTES`, checked against `expected_route`, a restatement of the dispatch; the same table is in DESIGN.md, section 19).
-Lines: A = csrc/somf_step.hip (enet_regression_abi), S = csrc/cd_solver.hip, P = csrc/cd_split.hip, as of this commit.
+Lines: A = csrc/code_solve.hip (code_route, code_solve), S = csrc/cd_solver.hip, P = csrc/cd_split.hip, as of this commit.
 
   shared Gram, product library, default switches
     k = 5, 31, 32, 33   one wavefront (cd_kernel, 1 coefficient per lane), 64-stride padded copy, padded-vector loader:
-                        A:1125-1131 copies (cd_padded_ld = 64, S:569); P:22 refuses a stride of 64, so S:546 falls
-                        through to S:548; S:496-498 picks VEC and PAD.  (The four-wavefront solver starts at k = 65 for a shared
+                        A:19, A:81-85 copies (cd_padded_ld = 64, S:568); P:20 refuses a stride of 64, so S:545 falls
+                        through to S:547; S:496-498 picks VEC and PAD.  (The four-wavefront solver starts at k = 65 for a shared
                         matrix: 32 <= k <= 64 is padded to 64, not to 128.  A per-sample matrix of that size is padded to 128,
-                        S:601.)
-    k = 70, 128         four wavefronts at stride 128 (P:31): 128 in place (A:1125 false), 70 through the padded copy
-    k = 129, 256        four wavefronts at stride 256 (P:32); 129 through the copy, 256 in place
-    k = 257, 512        stride 512 (P:33)
-    k = 513, 1024       stride 1024 (P:34)
-    k = 1025            the wide solver (A:1136, csrc/cd_wide.hip)
-  misaligned shared matrix (a view one element into a buffer), k = 128, 256: A:1125 makes no copy (k <= 256), P:25 refuses,
-                        S:548-550 + S:496 (not VEC): cd_kernel with the element-wise loader, 2 / 4 coefficients per lane
+                        S:600.)
+    k = 70, 128         four wavefronts at stride 128 (P:33): 128 in place (A:19 false), 70 through the padded copy
+    k = 129, 256        four wavefronts at stride 256 (P:34); 129 through the copy, 256 in place
+    k = 257, 512        stride 512 (P:35)
+    k = 513, 1024       stride 1024 (P:36)
+    k = 1025            the wide solver (A:16, csrc/cd_wide.hip)
+  misaligned shared matrix (a view one element into a buffer), k = 128, 256: A:19 makes no copy (k <= 256), P:23 refuses,
+                        S:547-549 + S:496 (not VEC): cd_kernel with the element-wise loader, 2 / 4 coefficients per lane
   per-sample Gram
-    k = 128             in place on the four-wavefront solver (A:1137: cd_split_applies holds, A:1143 -> S:546)
-    k = 70              through zero-padded slots of stride 128 (A:1137-1141, S:618-641)
-    k = 513, f64, b = 9 slots of 1024 x 1024 x 8 B = 8 MiB: eight per 64 MiB slice (S:590, S:602-608), so two slices (S:624)
-    k = 20, b = 5       cd_kernel, element-wise loader (A:1137 needs k >= 32; S:548); the second workgroup holds one sample
-    k = 1025            the wide solver with a matrix per sample (A:1136)
-  MODL_DEBUG_CD_SPLIT = 0 (S:544-546), shared, k = 70, 128, 200, 256: cd_kernel with 2 / 4 coefficients per lane; 70 and 200 through
+    k = 128             in place on the four-wavefront solver (A:20: cd_split_applies holds, A:87 -> S:545)
+    k = 70              through zero-padded slots of stride 128 (A:20-21, A:75-79, S:617-640)
+    k = 513, f64, b = 9 slots of 1024 x 1024 x 8 B = 8 MiB: eight per 64 MiB slice (S:589, S:601-607), so two slices (S:623)
+    k = 20, b = 5       cd_kernel, element-wise loader (A:20 needs k >= 32; S:547); the second workgroup holds one sample
+    k = 1025            the wide solver with a matrix per sample (A:16)
+  MODL_DEBUG_CD_SPLIT = 0 (S:543-545), shared, k = 70, 128, 200, 256: cd_kernel with 2 / 4 coefficients per lane; 70 and 200 through
                         the padded copy with the padded-vector loader (S:498), 128 and 256 in place with the vector loader
-  MODL_DEBUG_CD_SPARSE_PCT = 0 / 100 (S:534-535) on those four: dense / active-set sweeps only
+  MODL_DEBUG_CD_SPARSE_PCT = 0 / 100 (S:533-534) on those four: dense / active-set sweeps only
 Routing cannot be observed from outside; `test_workspace_table` pins what can be: the padded-copy and slot terms of
 modl_enet_regression_workspace for every (k, b) of the table.
 
@@ -122,7 +122,7 @@ F32_NOISE_SCENES = ('tight',)
 
 
 # ---------------------------------------------------------------------------------------------------- the dispatch, restated
-def padded_ld(k):                # csrc/cd_solver.hip:569
+def padded_ld(k):                # csrc/cd_solver.hip:568
     return 64 if k <= 64 else 128 if k <= 128 else 256 if k <= 256 else 512 if k <= 512 else 1024
 
 
@@ -130,13 +130,13 @@ def _au(x):
     return -(-x // 256) * 256
 
 
-def slot_count(tsz, b, k):       # csrc/cd_solver.hip:601-608
+def slot_count(tsz, b, k):       # csrc/cd_solver.hip:600-607
     ld = max(128, padded_ld(k))
     return min(max(1, (64 << 20) // (ld * ld * tsz)), max(b, 1)), ld
 
 
 def expected_workspace(dt, b, k, multi):
-    """modl_enet_regression_workspace restated (csrc/somf_step.hip:1156-1164): (total, padded-copy term, slot term)."""
+    """modl_enet_regression_workspace restated (csrc/code_solve.hip:142-154): (total, padded-copy term, slot term)."""
     t = 4 if dt == 'f32' else 8
     chol = -(-k // 64) * 64 * 64 if k > 128 else 0                      # csrc/chol.hip:512
     base = _au(t * b) + _au(t * b * k) + _au(t * (k * k * (b if multi and k <= 512 else 1) + chol))
@@ -185,27 +185,27 @@ def _route(name, k, want, cite, b=None, multi=False, misaligned=False, sw=None, 
                                   dts=dts, want=want, cite=cite, extra=extra))
 
 
-for _k, _want, _cite in ((5, 'one_wave/kpl1/padded', 'A:1125 S:546 P:22 S:548 S:498'), (31, 'one_wave/kpl1/padded', 'A:1125 P:24 S:548 S:498'),
-                         (32, 'one_wave/kpl1/padded', 'A:1125 P:22 S:548'), (33, 'one_wave/kpl1/padded', 'A:1125 P:22 S:548'),
-                         (70, 'split128/copy', 'A:1125 S:546 P:31'), (128, 'split128/in_place', 'A:1125 S:546 P:31'),
-                         (129, 'split256/copy', 'A:1125 P:32'), (256, 'split256/in_place', 'P:32'), (257, 'split512/copy', 'A:1125 P:33'),
-                         (512, 'split512/in_place', 'P:33'), (513, 'split1024/copy', 'A:1125 P:34'), (1024, 'split1024/in_place', 'P:34'),
-                         (1025, 'wide', 'A:1136')):
+for _k, _want, _cite in ((5, 'one_wave/kpl1/padded', 'A:19 S:545 P:20 S:547 S:498'), (31, 'one_wave/kpl1/padded', 'A:19 P:22 S:547 S:498'),
+                         (32, 'one_wave/kpl1/padded', 'A:19 P:20 S:547'), (33, 'one_wave/kpl1/padded', 'A:19 P:20 S:547'),
+                         (70, 'split128/copy', 'A:19 S:545 P:33'), (128, 'split128/in_place', 'A:19 S:545 P:33'),
+                         (129, 'split256/copy', 'A:19 P:34'), (256, 'split256/in_place', 'P:34'), (257, 'split512/copy', 'A:19 P:35'),
+                         (512, 'split512/in_place', 'P:35'), (513, 'split1024/copy', 'A:19 P:36'), (1024, 'split1024/in_place', 'P:36'),
+                         (1025, 'wide', 'A:16')):
     _route('shared-k%d' % _k, _k, _want, _cite, extra=_k in (31, 70, 256, 513, 1025))
-_route('misaligned-k128', 128, 'one_wave/kpl2/element', 'A:1125 P:25 S:549 S:496', misaligned=True)
-_route('misaligned-k256', 256, 'one_wave/kpl4/element', 'A:1125 P:25 S:550 S:496', misaligned=True)
-_route('multi-k128', 128, 'split128/in_place', 'A:1137 A:1143 S:546', multi=True)
-_route('multi-k70', 70, 'split128/slots/slices1', 'A:1137-1141 S:618', multi=True, extra=True)
-_route('multi-k513-two-slices', 513, 'split1024/slots/slices2', 'A:1137-1141 S:590 S:602-608 S:624', b=9, multi=True, dts=('f64',))
-_route('multi-k20', 20, 'one_wave/kpl1/element', 'A:1137 S:548 S:496', b=5, multi=True)
-_route('multi-k1025', 1025, 'wide', 'A:1136', multi=True)
+_route('misaligned-k128', 128, 'one_wave/kpl2/element', 'A:19 P:23 S:548 S:496', misaligned=True)
+_route('misaligned-k256', 256, 'one_wave/kpl4/element', 'A:19 P:23 S:549 S:496', misaligned=True)
+_route('multi-k128', 128, 'split128/in_place', 'A:20 A:87 S:545', multi=True)
+_route('multi-k70', 70, 'split128/slots/slices1', 'A:20-21 A:75-79 S:617', multi=True, extra=True)
+_route('multi-k513-two-slices', 513, 'split1024/slots/slices2', 'A:20-21 A:75-79 S:589 S:601-607 S:623', b=9, multi=True, dts=('f64',))
+_route('multi-k20', 20, 'one_wave/kpl1/element', 'A:20 S:547 S:496', b=5, multi=True)
+_route('multi-k1025', 1025, 'wide', 'A:16', multi=True)
 for _pct in (-1, 0, 100):
     for _k, _want in ((70, 'one_wave/kpl2/padded'), (128, 'one_wave/kpl2/vector'), (200, 'one_wave/kpl4/padded'),
                       (256, 'one_wave/kpl4/vector')):
         _sw = {'CD_SPLIT': 0}
         if _pct >= 0:
             _sw['CD_SPARSE_PCT'] = _pct
-        _route('split0%s-k%d' % ('' if _pct < 0 else '-pct%d' % _pct, _k), _k, _want, 'S:544-546 S:534 S:549-550 S:498', sw=_sw)
+        _route('split0%s-k%d' % ('' if _pct < 0 else '-pct%d' % _pct, _k), _k, _want, 'S:543-545 S:533 S:548-549 S:498', sw=_sw)
 ROUTE_BY_NAME = {r.name: r for r in ROUTES}
 
 

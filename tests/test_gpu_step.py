@@ -250,6 +250,63 @@ def test_per_sample_gram_on_the_four_wavefront_solver(DictFact, oracle, dt, tol)
     assert_within_f32_noise(est.code_[:16], st32.code[:16], st64.code[:16], 'codes')
 
 
+_PLAN_LEAVES = ([('shared', k, 0.9) for k in (31, 70, 256, 513, 1025)] + [('average', k, 0.9) for k in (20, 70, 128)] +
+                [(agg, k, 0.0) for agg in ('shared', 'average') for k in (50, 200, 520)])
+
+
+@pytest.mark.parametrize('dt', [np.float64, np.float32], ids=['f64', 'f32'])
+@pytest.mark.parametrize('agg,k,l1', _PLAN_LEAVES, ids=['%s-k%d-l1_%g' % leaf for leaf in _PLAN_LEAVES])
+def test_plan_code_solve_leaves(DictFact, oracle, agg, k, l1, dt):
+    """Every leaf of the code solve (csrc/code_solve.hip) as the PLAN enters it, with the plan's scratch: one-wavefront and
+    four-wavefront coordinate descent through the padded copy (k = 31, 70, 513) and as stored (256), the wide solver
+    (1025), per-sample matrices as stored (20, 128) and through the lazily allocated slots (70); ridge in one launch (50),
+    factor + solve (average 200) and blocked (shared 200, 520; average 520, walked from the host indices).  b = 9,
+    p = k + 80, two minibatches with permuted sample_indices (the second destination of the solve) that share four rows
+    (on their second visit w_sample < 1: G_average_[i] is no longer the minibatch's Gram matrix), then transform (the
+    shared-Gram leaf of the same k, warm start of ones).  The oracle transforms with the estimator's dictionary: both
+    sides solve the same systems.  (With each side's own dictionary the f32 case at k = 1025 compares solves of inputs
+    that differ by the fit's f32 noise, 5.6e-4: on this Gram matrix, condition number 2.4e6, one row of 18 - the one
+    with the most sweeps, 66 - then ends 3.5e-2 away, 6.5e-3 over all rows against a noise of 3.1e-4, while from the same
+    dictionary every row is within 1.4e-4 of the oracle and the sweep counts are equal.)
+    f64: 1e-9 as the neighbours; f32: the oracle's own noise."""
+    from .conftest import assert_within_f32_noise
+    b, n, p = 9, 18, k + 80
+    rs = np.random.RandomState(k)
+    X = ((rs.randn(max(n, k), 32) * (rs.rand(max(n, k), 32) < 0.3)).dot(rs.randn(32, p)) / np.sqrt(0.3 * 32)
+         + 0.1 * rs.randn(max(n, k), p))
+    perm = rs.permutation(n)
+    g = 'average' if agg == 'average' else 'masked'
+    kw = dict(n_components=k, batch_size=b, reduction=2, code_alpha=0.3 if l1 else 1e-2, code_l1_ratio=l1, G_agg=g, Dx_agg=g,
+              learning_rate=0.92, random_state=0)
+
+    def fit(make, partial_fit, Xd):
+        st = make(Xd)
+        for m in range(2):
+            rows = perm[5 * m:5 * m + b]
+            partial_fit(st, Xd[rows], rows)
+        return st
+
+    def reference(dtype, D):
+        pr = oracle.SomfParams(**kw)
+        st = fit(lambda Xd: oracle.prepare(pr, n_samples=n, X=Xd), lambda st, Xb, rows: oracle.partial_fit(st, pr, Xb, rows),
+                 X.astype(dtype))
+        return st.D, st.code, oracle.transform(pr, np.ascontiguousarray(D, dtype=dtype), X[:n].astype(dtype))
+
+    Xd = X.astype(dt)
+    est = fit(lambda Xd: DictFact(**kw).prepare(n_samples=n, X=Xd), lambda est, Xb, rows: est.partial_fit(Xb, rows), Xd)
+    got = (est.components_, est.code_, est.transform(Xd[:n]))
+    names = ('dictionary', 'codes', 'transform')
+    if dt == np.float64:
+        errs = [rel_fro(a, r) for a, r in zip(got, reference(np.float64, got[0]))]
+        print(agg, k, l1, dict(zip(names, errs)))
+        assert max(errs) < 1e-9, dict(zip(names, errs))
+    else:
+        r32, r64 = reference(np.float32, got[0]), reference(np.float64, got[0])
+        print(agg, k, l1, {w: (rel_fro(a, c), rel_fro(r, c)) for w, a, r, c in zip(names, got, r32, r64)})
+        for w, a, r, c in zip(names, got, r32, r64):
+            assert_within_f32_noise(a, r, c, w)
+
+
 @pytest.mark.parametrize('agg', ['masked', 'average'])
 def test_wide_ridge_estimator_vs_oracle(DictFact, oracle, agg):
     """fMRIDictFact's configuration (ridge codes, l1 atoms) at n_components = 600 > 512 through the estimator:

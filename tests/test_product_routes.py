@@ -44,18 +44,18 @@ B = bcd.hip.
                          least half full, no gather on K: "dense" staging from clamped coordinates (G:212-214, 135-161)
   D:644-651 plan_stats   f32, 32 x 32 tiles of 16x16x4, K <= 256, no split (resident-K tile, 4 K-tiles of 64)
   W:46-58   plan_wide    16-byte aligned operands, M, N, leading strides % 4 == 0, K <= 256
-  S:632-683 stats_pair   f32: resident (plan_stats(C) ok, rows >= 4096, k <= 256, b % 4 == 0, switch on, plan_wide ok; the
+  S:574-625 stats_pair   f32: resident (plan_stats(C) ok, rows >= 4096, k <= 256, b % 4 == 0, switch on, plan_wide ok; the
                          epilogue by 16 bytes for EpiStats, element by element for the row-indirected EpiStatsRows), else
                          wide pair (ceil(rows / 64) >= 1024, plan_wide ok: 32 features x 256 atoms per tile), else stats pair
                          (both plan_stats ok); any type: dense pair (both plan_dense ok, no split), else one launch each
                          (launch_gemm_dense: dense kernel, or gather kernel below 2^22)
-  S:741-835 phase1 code  need_sub = subset and not (G_agg == Dx_agg == full): prep_kernel gathers Ds = Dt[subset], Xs = X[:, subset]
+  S:682-776 phase1 code  need_sub = subset and not (G_agg == Dx_agg == full): prep_kernel gathers Ds = Dt[subset], Xs = X[:, subset]
                          (s_pad = ceil(s / 4) 4 columns); paired = G wanted and both plan_dense ok with 256 workgroups and
                          half the scratch each, the Gram symmetric; else one launch_gemm_dense each
-  S:760     ride         a proper subset, Dx_agg != full, no MODL_FLAG_NO_RIDER, ceil(p / 64) < 1024: C_ and the sampled rows
+  S:701     ride         a proper subset, Dx_agg != full, no MODL_FLAG_NO_RIDER, ceil(p / 64) < 1024: C_ and the sampled rows
                          of B_ (EpiStatsRows) now, the others under the dictionary update
   B:2889-2921 rider      f32 and k <= 512: wide tiles 32 x 128 when p >= 2048 and plan_wide ok, else the 32 x 32 tiles of
-                         plan_stats, shared out over the carrier launches; otherwise completed after the update (S:988-996)
+                         plan_stats, shared out over the carrier launches; otherwise completed after the update (S:929-937)
                          through stats_pair with EpiStatsSkip
 The launches of the code-product and statistics sections (modl_somf_prof_get: code_gemm, stats_gemm) are asserted against the
 restated count on every S point: paired or not, split or not.  A rider that the dictionary update did not consume is completed
@@ -87,7 +87,7 @@ launches and are not counted: that they ran is seen in the rows of B_, which til
   S-stats sgd; three steps      p 600 s 200 (and p 2400 s 800, the wide rider), overlapping subsets, judged after each step
 Not reachable from the ABI: the big configuration in f64 (k > 2048 would need 8 k^2 64 bytes of scratch - run in f32 only, as the
 issue lists it); the "dense" staging of the A operand in probe G (M = N <= 32 there; probe T's b = 200 covers it).
-Not reached by these probes (`UNREACHED`): a subset with Dx_agg = full and G_agg != full (S:760 then denies the rider); the
+Not reached by these probes (`UNREACHED`): a subset with Dx_agg = full and G_agg != full (S:701 then denies the rider); the
 probes set G_agg = Dx_agg, which their formulas assume.
 
 SCENES
@@ -181,7 +181,7 @@ def all_leaves():
 
 
 # ---------------------------------------------------------------------------------------------------- the dispatch, restated
-def split_scratch_elems(mb, k, p):             # S:1236-1237
+def split_scratch_elems(mb, k, p):             # S:1075-1076
     e = max(mb, k) * k * 64
     if p * k < e:
         e = max(e, p * k * 8)
@@ -315,25 +315,25 @@ def plan_wide_ok(M, N, K, ld_a, ld_b, base_a=0):                          # W:46
 
 
 def stats_pair(dt, k, M1, ld1, base1, K, ws, epi='stats', M0=None, resident=True):
-    """S:632-683: the products code^T code (M0 = k rows; 0: none) and X^T code (M1 rows of leading stride ld1) -> (route, launches)"""
+    """S:574-625: the products code^T code (M0 = k rows; 0: none) and X^T code (M1 rows of leading stride ld1) -> (route, launches)"""
     M0 = k if M0 is None else M0
     unal_c, unal_x = misaligned(dt, k), misaligned(dt, ld1, base1)
     if dt == 'f32':
         p0 = plan_stats_ok(dt, unal_c, unal_c, M0, k, K)
-        if p0 and M1 >= 4096 and k <= 256 and K % 4 == 0 and resident and plan_wide_ok(M1, k, K, ld1, k, base1):   # S:648-659
+        if p0 and M1 >= 4096 and k <= 256 and K % 4 == 0 and resident and plan_wide_ok(M1, k, K, ld1, k, base1):   # S:590-601
             _leaf('resident: vec4 epilogue') if epi == 'stats' else _leaf('resident: scalar row-indirected epilogue')
             return 'resident16/%s' % ('vec4' if epi == 'stats' else 'scalar'), 1
-        if p0 and cdiv(M1, 64) >= 1024 and plan_wide_ok(M1, k, K, ld1, k, base1):                                     # S:661-664
+        if p0 and cdiv(M1, 64) >= 1024 and plan_wide_ok(M1, k, K, ld1, k, base1):                                     # S:603-606
             _leaf('wide pair: one atom chunk') if k <= 256 else _leaf('wide pair: several atom chunks')
             return 'wide32/c%d' % cdiv(k, 256), 1
-        if p0 and plan_stats_ok(dt, unal_x, unal_c, M1, k, K):                                                        # S:665-669
+        if p0 and plan_stats_ok(dt, unal_x, unal_c, M1, k, K):                                                        # S:607-611
             _leaf('stats pair: misaligned') if unal_x or unal_c else _leaf('stats pair: aligned')
             return 'stats32/%s/t%dx%d' % ('unal' if unal_x or unal_c else 'al', cdiv(M1, 32), cdiv(k, 32)), 1
     ok0 = True
     if M0 > 0:
         ok0 = plan_dense(dt, unal_c, unal_c, M0, k, K, 0).ok
     P1 = plan_dense(dt, unal_x, unal_c, M1, k, K, 0, 512, 1, 64, 64)
-    if ok0 and P1.ok:                                                                                                 # S:679-680
+    if ok0 and P1.ok:                                                                                                 # S:621-622
         _leaf('dense pair: C and B') if M0 > 0 else _leaf('dense pair: B alone (after the update)')
         return 'densepair/%s/%s' % ('unal' if unal_x or unal_c else 'al', dense_tile(dt, P1, True)), 1
     n, parts = 0, []
@@ -348,20 +348,20 @@ def stats_pair(dt, k, M1, ld1, base1, K, ws, epi='stats', M0=None, resident=True
 
 
 def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, resident=True, has_idx=True, judged=('code', 'stats')):
-    """S:689-902 for ridge codes (no row norms, codes solved in place): the code-product and statistics sections.  Only the
+    """S:631-843 for ridge codes (no row norms, codes solved in place): the code-product and statistics sections.  Only the
     branches of the sections in `judged` count as taken (HIT): a probe vouches for the section whose result it judges."""
     taken, mine = set(HIT), {}
     HIT.clear()
     ws = split_scratch_elems(mb, k, p)
     full = G_agg == 'full' and Dx_agg == 'full'
-    need_sub = subset and not full                                           # S:741
+    need_sub = subset and not full                                           # S:682
     s_pad = cdiv(s, 4) * 4
     n = 0
-    if need_sub and s > 0:                                                   # S:769-774 (n_norm = n_code = 0 for ridge codes)
+    if need_sub and s > 0:                                                   # S:710-715 (n_norm = n_code = 0 for ridge codes)
         _leaf('phase1: prep_kernel gathers Ds and Xs')
         n += 1
     unal_d = misaligned(dt, k)
-    if Dx_agg == 'full':                                                     # S:778-786
+    if Dx_agg == 'full':                                                     # S:719-727
         _leaf('phase1: Dx over all of p')
         unal_a, Kdim = misaligned(dt, ldx, xbase), p
     elif need_sub:
@@ -371,7 +371,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
         _leaf('phase1: Dx over X as given (no subset)')
         unal_a, Kdim = misaligned(dt, ldx, xbase), s
     want_G, paired = G_agg != 'full', False
-    if want_G:                                                               # S:792-818
+    if want_G:                                                               # S:733-759
         half = ws // 2
         PG = plan_dense(dt, unal_d, unal_d, k, k, s, ws - half, 256, 64, 64, 64, True)
         PD = plan_dense(dt, unal_a, unal_d, b, k, Kdim, half, 256)
@@ -381,7 +381,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
             code = 'pair/Dx[%s]/G[%s]' % (dense_str(dt, PD, True), dense_str(dt, PG, True))
             n += 1 + (PD.splits > 1 or PG.splits > 1)
             splits = (PD.splits, PG.splits)
-    if not paired:                                                           # S:819-831
+    if not paired:                                                           # S:760-772
         sd, ld, spd = launch_gemm_dense(dt, unal_a, unal_d, b, k, Kdim, ws)
         code, splits = 'each/Dx[%s]' % sd, (spd, 1)
         n += ld
@@ -391,7 +391,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
             code += '/G[%s]' % sg
             n += lg
             splits = (spd, spg)
-    if G_agg == 'average':                                                   # S:832-835
+    if G_agg == 'average':                                                   # S:773-776
         _leaf('phase1: G_average rows updated')
         n += 1
     if need_sub:
@@ -399,10 +399,10 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
     out = SimpleNamespace(code=code, code_launches=n, splits=splits)
     mine['code'] = set(HIT)
     HIT.clear()
-    # ---- statistics (S:853-900)
+    # ---- statistics (S:794-841)
     m = 1 if has_idx else 0                                                  # the gather of code_[idx] (ridge: not solved on compact rows)
     proper = need_sub and 0 < s < p
-    ride = proper and Dx_agg != 'full' and not (flags & NO_RIDER) and cdiv(p, 64) < 1024      # S:760
+    ride = proper and Dx_agg != 'full' and not (flags & NO_RIDER) and cdiv(p, 64) < 1024      # S:701
     if not proper:
         _leaf('no rider: no proper subset')
     elif Dx_agg == 'full':
@@ -421,7 +421,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
         elif fused and plan_stats_ok(dt, unal_x, unal_c, p, k, b):           # B:2896, 2903
             _leaf('rider: stats32 unal') if unal_x or unal_c else _leaf('rider: stats32 al')
             rider = 'stats32/' + ('unal' if unal_x or unal_c else 'al')
-        else:                                                                # S:988-996
+        else:                                                                # S:929-937
             _leaf('rider: completed after the update')
             rider = 'after[%s]' % stats_pair(dt, k, p, ldx, xbase, b, ws, 'skip', M0=0, resident=resident)[0]
         out.stats = r + '/ride:' + rider
@@ -435,7 +435,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
     return out
 
 
-def partial_gram(dt, k, s, mb, p):             # S:956-961, 998-1001 -> gram_of_rows (S:529-535) with the subset on K
+def partial_gram(dt, k, s, mb, p):             # S:897-902, 939-942 -> gram_of_rows (S:529-535) with the subset on K
     return launch_gemm(dt, k, k, s, split_scratch_elems(mb, k, p), gather_k=True)
 
 
@@ -446,14 +446,14 @@ def expected_route(probe, dt, **sh):
         ldx, base = sh.get('ldx', p), sh.get('base', 0)
         ws = split_scratch_elems(mb, k, p)
         chunks = []
-        for r0 in range(0, n, mb):                                           # S:1032-1042
+        for r0 in range(0, n, mb):                                           # S:976-986
             b = min(mb, n - r0)
             _leaf('transform: a full chunk') if b == mb else _leaf('transform: a short last chunk')
             chunks.append(launch_gemm_dense(dt, misaligned(dt, ldx, base + r0 * ldx), misaligned(dt, k), b, k, p, ws)[0])
         return 'T:' + '|'.join(chunks)
     if probe == 'G':
         k, p = sh['k'], sh['p']
-        return 'G:' + launch_gemm(dt, k, k, p, split_scratch_elems(sh.get('mb', 64), k, p))[0]      # S:1784-1796
+        return 'G:' + launch_gemm(dt, k, k, p, split_scratch_elems(sh.get('mb', 64), k, p))[0]      # S:1622-1634
     agg = sh.get('agg', 'masked')
     r = phase1(dt, sh['b'], sh['k'], sh['p'], sh.get('s', sh['p']), sh.get('s') is not None, agg, agg, sh.get('ldx', sh['p']),
                sh['b'], sh.get('flags', 0), resident=sh.get('resident', True), judged=('code',) if probe == 'S-code' else ('stats',))
@@ -1281,7 +1281,7 @@ def _run_point(r, dt, dev):
             again = _with_resident_switch(c, lambda: run_S(c, dev))
             assert state_bits(snaps, c) == state_bits(again, c), ('a second identical call gave other bits', scene)
             if 'ride:after[' in route_of(r, dt) and scene == 'gaussian':
-                # the rider that no launch of the dictionary update consumed is completed behind it (S:988-996), counted under
+                # the rider that no launch of the dictionary update consumed is completed behind it (S:929-937), counted under
                 # dict_update: as many launches more than the same step without a rider as stats_pair takes for B_ alone
                 extra = stats_pair(dt, c.k, c.p, c.ldx, c.base, c.b, split_scratch_elems(c.b, c.k, c.p), 'skip', M0=0)[1]
                 c.flags |= NO_RIDER

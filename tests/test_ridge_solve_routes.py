@@ -3,16 +3,16 @@ modl_amd.dict_fact_fast._enet_regression_{single,multi}_gram (and modl_enet_regr
 buffer), against a Cholesky solve in np.longdouble written here and against LAPACK posv (the CPU oracle), row by row.
 
 ROUTES (`ROUTES`, checked against `expected_route`, a restatement of the dispatch; the same table is in DESIGN.md, section 19b).
-Lines: A = csrc/somf_step.hip (enet_regression_abi), C = csrc/chol.hip, as of this commit.
+Lines: A = csrc/code_solve.hip (code_route, code_solve), C = csrc/chol.hip, as of this commit.
 
-  A:1095 + C:516-518  chol_blocked: k > 512, or a shared matrix with k > 160 or k k sizeof(T) > kCholLdsBytes = 160 KiB - 512
+  A:13 + C:516-518    chol_blocked: k > 512, or a shared matrix with k > 160 or k k sizeof(T) > kCholLdsBytes = 160 KiB - 512
                       (C:31): shared f32 k >= 161, shared f64 k >= 143.  Blocks of kCholNB = 64 columns (C:336), the last of
                       nb = k - 64 (ceil(k / 64) - 1) (C:454)
-  A:1101 + C:286-288  ridge_small_applies: k <= 128 (C:211) and ((k | 1) k + ((k + 3) & ~3) + 3 (k <= 64 ? 4 : 8) 64) sizeof(T)
+  A:14 + C:286-288    ridge_small_applies: k <= 128 (C:211) and ((k | 1) k + ((k + 3) & ~3) + 3 (k <= 64 ? 4 : 8) 64) sizeof(T)
                       <= 150 KiB (every k <= 128 in both types).  RPL = 1 for k <= 64, else 2 (C:309); per_wave = 1 for a
                       matrix per sample, else ceil(b / 4) (C:306); NR = min(6, per_wave) (C:310-322); a shared matrix takes
                       ceil(b / (4 NR)) passes of the right-hand-side loop (C:264), a matrix per sample one workgroup each
-  A:1103-1104         cholesky_kernel<LDS> while k k sizeof(T) <= kCholLdsBytes (C:91: f32 k <= 202, f64 k <= 142), else
+  A:43-44             cholesky_kernel<LDS> while k k sizeof(T) <= kCholLdsBytes (C:91: f32 k <= 202, f64 k <= 142), else
                       cholesky_kernel<global>; chol_solve_kernel<KPL>, KPL = 4 for 129 <= k <= 256, 8 beyond (C:190-193)
 
   small, shared, RPL 1      k = 7, b in {1, 2, 4, 5, 8, 9, 12, 13, 16, 17, 20, 21, 24, 25, 49}: NR 1 1 1 2 2 3 3 4 4 5 5 6 6 6 6,
@@ -144,20 +144,20 @@ def chol_wide_scratch_elems(k):              # csrc/chol.hip:512
 def expected_route(dt, k, b, multi):
     """The code path of a ridge call (see the module docstring for the lines restated)."""
     t = 4 if dt == 'f32' else 8
-    if chol_blocked(t, k, not multi):                                    # A:1095
+    if chol_blocked(t, k, not multi):                                    # A:13
         nblk = -(-k // NB)
         return 'blocked/%s/blocks%d/last%d' % ('per_sample' if multi else 'shared', nblk, k - NB * (nblk - 1))
-    if ridge_small_applies(t, k):                                        # A:1101
+    if ridge_small_applies(t, k):                                        # A:14
         per_wave = 1 if multi else -(-b // 4)                            # C:306
         nr = min(6, per_wave)                                            # C:310-322
         count = 1 if multi else b                                        # C:229
         return 'small/%s/rpl%d/nr%d/passes%d' % ('per_sample' if multi else 'shared', 1 if k <= 64 else 2, nr, -(-count // (4 * nr)))
     return 'one_wg/%s/%s/kpl%d' % ('per_sample' if multi else 'shared', 'lds' if k * k * t <= chol_lds_bytes() else 'global',
-                                   4 if k <= 256 else 8)                 # A:1103-1104, C:91, C:190-193
+                                   4 if k <= 256 else 8)                 # A:43-44, C:91, C:190-193
 
 
 def ridge_workspace_terms(dt, b, k, multi):
-    """(F elements, Linv elements) of modl_enet_regression_workspace (csrc/somf_step.hip:1162)"""
+    """(F elements, Linv elements) of modl_enet_regression_workspace (csrc/code_solve.hip:152-153)"""
     return k * k * (b if multi and k <= 512 else 1), chol_wide_scratch_elems(k)
 
 
