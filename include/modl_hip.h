@@ -366,6 +366,14 @@ int modl_dict_update_f64(double *d_Dt, const double *d_Bt, const double *d_C, do
                          const int32_t *d_subset, int64_t s, const int32_t *d_order, const int64_t *h_order, int k,
                          int optimizer, int comp_pos, double comp_l1_ratio, double w, double step_size, void *d_ws,
                          size_t ws_bytes, void *stream);
+/* Which kernels modl_dict_update_* would run for these arguments under the current modl_debug_set switches, written to
+ * buf[cap] as "family/parameter/..." ("persist/RT1", "block/RT2/GPW8/acc1/shards4", "grouped/EPT20/G8/KPL4/enet", "wide",
+ * ...: csrc/bcd.hip, du_route).  Read-only: nothing is launched, no device memory is written.  ncu > 0: the route on a
+ * device of that many compute units, one workgroup of the persistent launch resident on each - no device is touched, so
+ * this works without a GPU; ncu == 0: the current device is asked, as modl_dict_update_* asks it.  MODL_EINVAL for a bad
+ * dtype, k outside 1 .. MODL_MAX_COMPONENTS, s <= 0, ncu < 0 or a buffer too small (64 bytes hold every route). */
+int modl_dict_update_route(int dtype, int k, int64_t s, int optimizer, int comp_pos, double comp_l1_ratio, int ncu,
+                           char *buf, size_t cap);
 
 /* ------------------------------------------------------------------------- *
  * Fused, device-resident minibatch step = DictFact._single_batch_fit,

@@ -216,6 +216,7 @@ def bind(lib):
     _sig('modl_masked_objective_workspace', _sz, C.c_int, _i64, _i64)
     _sig('modl_amari_workspace', _sz, C.c_int, C.c_int, _vp, _i64)
     _sig('modl_dict_update_workspace', _sz, C.c_int, _i64, C.c_int)
+    _sig('modl_dict_update_route', C.c_int, C.c_int, C.c_int, _i64, C.c_int, C.c_int, _f64, C.c_int, C.c_char_p, _sz)
     _sig('modl_recsys_topn_workspace', _sz, C.c_int, _i64, C.c_int, _i64, C.c_int)
     _sig('modl_recsys_ranks_workspace', _sz, C.c_int, _i64, C.c_int, _i64, C.c_int)
     _sig('modl_omp_workspace', _sz, C.c_int, _i64, C.c_int, C.c_int, C.c_int)

@@ -32,6 +32,7 @@
 //
 //  * sgd path (dict_fact.py:695-708).
 #include "bcd_shared.hpp"
+#include <cstdio>
 
 namespace modl {
 
@@ -2725,328 +2726,6 @@ int dict_update_wide(hipStream_t stream, const DictUpdateArgs<T> &a, int *launch
     return MODL_OK;
 }
 
-// ---------------------------------------------------------------------- driver
-template <typename T> int dict_update_generic(hipStream_t stream, const DictUpdateArgs<T> &a, int *launches);
-
-template <typename T>
-int dict_update(hipStream_t stream, const DictUpdateArgs<T> &a, int *launches) {
-    const int k = a.k;
-    const int64_t s = a.s;
-    if (s <= 0 || k <= 0) return MODL_OK;
-    if (k > MODL_MAX_COMPONENTS) return MODL_EINVAL;
-    if (k > 1024 && a.optimizer != MODL_OPT_SGD) return dict_update_wide<T>(stream, a, launches);   // (the sgd path takes any k)
-    const DuLayout L = du_layout(sizeof(T), s, k);
-    if (L.total > a.ws_bytes) return MODL_ENOMEM;
-    char *ws = static_cast<char *>(a.ws);
-    int nl = 0;
-
-    if (a.optimizer == MODL_OPT_SGD) {
-        double *colp = reinterpret_cast<double *>(ws + L.off_colp);
-        T *Dnew = reinterpret_cast<T *>(ws + L.off_Dnew);
-        const int nslab = (int)cdiv(s, kGramRows);
-        hipLaunchKernelGGL((col_norm_partial_kernel<T>), dim3(nslab), dim3(256), 0, stream, a.Dt, a.subset, s, k,
-                           a.comp_l1_ratio, colp);
-        MODL_LAUNCH_CHECK();
-        hipLaunchKernelGGL((col_norm_add_kernel<T>), dim3((unsigned)cdiv(k, 256)), dim3(256), 0, stream, colp, nslab, k,
-                           a.comp_norm);
-        MODL_LAUNCH_CHECK();
-        nl += 2;
-        Operand A, B;
-        A.ptr = a.Dt; A.si = k; A.sk = 1; A.gi = gather32(a.subset);
-        B.ptr = a.C; B.si = k; B.sk = 1;                 // B(n = j, kk = m) = C[j][m]
-        EpiSgd<T> epi{Dnew, a.Dt, a.Bt, a.subset, k, (T)(a.w * a.step_size)};
-        SplitWs none;
-        MODL_TRY((launch_gemm<T, EpiSgd<T>>(stream, A, B, s, k, k, epi, none, &nl, 512, 1)));
-        hipLaunchKernelGGL((sgd_project_kernel<T>), dim3(k), dim3(256), 0, stream, Dnew, a.Dt, a.subset, s, k,
-                           a.comp_l1_ratio, a.comp_norm);
-        MODL_LAUNCH_CHECK();
-        ++nl;
-    } else if (a.comp_l1_ratio == 0.0 && !a.comp_pos) {
-        T *CP = reinterpret_cast<T *>(ws + L.off_CP);
-        T *cdiag = reinterpret_cast<T *>(ws + L.off_cdiag);
-        int32_t *frozen = reinterpret_cast<int32_t *>(ws + L.off_frozen);
-        T *abuf = reinterpret_cast<T *>(ws + L.off_a);
-        double *partial = reinterpret_cast<double *>(ws + L.off_partial);
-        double *Tp = reinterpret_cast<double *>(ws + L.off_Tp);
-        double *coef_all = reinterpret_cast<double *>(ws + L.off_coef);
-        double *CA[2] = {Tp, Tp + kResStride};
-        unsigned int *counter = reinterpret_cast<unsigned int *>(Tp + 2 * kResStride);
-        const bool fused = std::is_same<T, float>::value && k <= 512;
-        const int kp = (int)cdiv(k, 4) * 4;                      // atoms of the packed arrays (dead ones behind the k real)
-        constexpr int64_t rt1_max = MODL_RT1_MAX;
-        int RT = (s <= rt1_max || k > 256) ? 1 : 2;              // k > 256: 64-row tiles would spill registers
-        {   // one workgroup per compute unit (registers): a grid that is a few workgroups larger than the chip runs in
-            // two rounds, i.e. every block launch takes twice as long (s = 16.7 k: 261 workgroups of 64 features ->
-            // 174 of 96 features)
-            static const int ncu_blk = [] {
-                int dev = 0;
-                hipDeviceProp_t prop;
-                if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                    return prop.multiProcessorCount;
-                return 256;
-            }();
-            if (RT == 2 && cdiv(s, 64) > ncu_blk && cdiv(s, 96) <= ncu_blk) RT = 3;
-        }
-        // ONE persistent launch per dictionary update (bcd_persist.hip) when its workgroups - one per 32 or 64 sampled rows
-        // plus the resolver - can all be resident at once; otherwise one launch per block of 32 atoms
-        int persist_rt = 0;
-        if (fused && a.allow_persist && g_bcd_persist.load(std::memory_order_relaxed) && g_bcd_acc.load(std::memory_order_relaxed) &&
-            cdiv(k, kNB) <= kPersistBlocksMax) {
-            // (every workgroup must be resident: the resolver + one per 32 or 64 sampled rows - asked of the runtime for the
-            //  kernel's own footprint on this device, bcd_persist_fits.  Reduction 1 at the metric's shape: 157 workgroups of
-            //  64 rows, 0.173 -> 0.138 ms per dictionary update against one launch per block; config 5's 16.7 k sampled rows
-            //  do not fit and keep one launch per block.  The LDS of riding k-wide tiles is part of the question: a launch
-            //  that cannot carry them must not have marked them consumed)
-            const size_t xl = (a.rider && a.rider->p >= 2048) ? wide_lds_bytes<32, 128>() : 0;
-            const int64_t n1 = cdiv(s, 32), n2 = cdiv(s, 64);
-            if (n1 <= kPersistRowsMax && bcd_persist_fits(kp, 1, (int)n1, xl)) persist_rt = 1;
-            else if (kp <= 256 && n2 <= kPersistRowsMax && bcd_persist_fits(kp, 2, (int)n2, xl)) persist_rt = 2;
-        }
-        if (persist_rt) RT = persist_rt;
-        const int nslab = fused ? (int)cdiv(s, 32 * RT) : (int)cdiv(s, kGramRows);
-        const int GPW = (kp <= 256) ? 8 : 16;
-        void (*blk)(BcdBlockArgs, BcdRiderArgs) = nullptr;
-        T *DsP = reinterpret_cast<T *>(ws + L.off_Dnew), *BsP = reinterpret_cast<T *>(ws + L.off_BsP), *CPP = CP;
-        // the Gram accumulators of the fused path (three in rotation; in the space of the group sums, which they replace)
-        long long *fused_acc = (fused && !persist_rt && g_bcd_acc.load(std::memory_order_relaxed)) ? reinterpret_cast<long long *>(ws + L.off_gpartial) : nullptr;
-        const int pshards = nslab > MODL_ACC_SHARD_MIN ? kAccShards : 1;
-        long long *pacc = persist_rt ? reinterpret_cast<long long *>(ws + L.off_pacc) : nullptr;
-        unsigned int *pflags = reinterpret_cast<unsigned int *>(ws + L.off_pflags);
-        double *qcoef = persist_rt ? reinterpret_cast<double *>(ws + L.off_qcoef) : nullptr;
-        static_assert(sizeof(long long) * 3 * kAccShards * kAccWords <= sizeof(double) * 2 * (size_t)kCounters * (kNB * kNB + kNB), "accumulators fit");
-        if (fused) {
-            blk = (RT == 1) ? (GPW == 8 ? bcd_block_kernel<1, 8> : bcd_block_kernel<1, 16>)
-                            : (RT == 2 ? bcd_block_kernel<2, 8> : bcd_block_kernel<3, 8>);
-            MODL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(blk), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024));
-            hipLaunchKernelGGL((bcd_setup_kernel<T>), dim3((unsigned)(kNB + cdiv(kp, kSetupRows) + cdiv(s, kSetupRows))), dim3(256), 0, stream, a.C, a.order, k, kp, CPP,
-                               cdiag, frozen, coef_all, counter, a.comp_norm, reinterpret_cast<T *>(ws + L.off_norm_in), a.Dt,
-                               a.Bt, a.subset, s, DsP, BsP, fused_acc, pacc,
-                               (long long)cdiv(k, kNB) * pshards * kPAccWords, qcoef, pflags,
-                               reinterpret_cast<long long *>(ws + L.off_Sbuf), persist_rt ? (long long)cdiv(k, kNB) * kNB * kNB : 0);
-            MODL_LAUNCH_CHECK();
-            ++nl;
-        } else {
-            const int nfew = (int)cdiv(s, kFewRows);
-            const bool few = std::is_same<T, double>::value && s > kTinyRows && nfew <= kFewMaxWg && g_bcd_tiny.load(std::memory_order_relaxed) &&
-                             g_bcd_few.load(std::memory_order_relaxed);
-            long long *few_x = few ? reinterpret_cast<long long *>(ws + L.off_few) : nullptr;
-            const long long few_words = 3LL * nfew * kFewRec;             // (the error word sits right behind them)
-            hipLaunchKernelGGL((bcd_prepare_kernel<T>), dim3(k > kNB ? k : kNB), dim3(256), sizeof(int32_t) * (size_t)k,
-                               stream, a.C, a.order, k, CP, cdiag, frozen, coef_all, counter, a.comp_norm,
-                               reinterpret_cast<T *>(ws + L.off_norm_in), few_x, few_words);
-            MODL_LAUNCH_CHECK();
-            ++nl;
-            if (few) {                                       // the whole sweep in one launch on a few workgroups
-                const size_t lds = bcd_tiny_lds(sizeof(T), kFewRows) + sizeof(T) * ((size_t)k + 1) + sizeof(int64_t) * kFewRows + 32;
-                MODL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bcd_few_kernel<T>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                hipLaunchKernelGGL((bcd_few_kernel<T>), dim3(nfew), dim3(256), lds, stream, a.Dt, a.Bt, CP, cdiag, frozen, coef_all,
-                                   a.subset, a.order, (int)s, k, a.comp_norm, reinterpret_cast<const T *>(ws + L.off_norm_in),
-                                   reinterpret_cast<double *>(few_x), reinterpret_cast<unsigned int *>(few_x + few_words),
-                                   a.persist_flags);
-                MODL_LAUNCH_CHECK();
-                ++nl;
-                if (launches) *launches += nl;
-                return MODL_OK;
-            }
-            if (std::is_same<T, double>::value && s <= kTinyRows && g_bcd_tiny.load(std::memory_order_relaxed)) {   // the whole sweep by one workgroup
-                MODL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bcd_tiny_kernel<T>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                hipLaunchKernelGGL((bcd_tiny_kernel<T>), dim3(1), dim3(256), bcd_tiny_lds(sizeof(T), s), stream, a.Dt, a.Bt, CP,
-                                   cdiag, frozen, coef_all, a.subset, a.order, (int)s, k, a.comp_norm);
-                MODL_LAUNCH_CHECK();
-                ++nl;
-                if (launches) *launches += nl;
-                return MODL_OK;
-            }
-        }
-        const size_t rec_half = (size_t)L.nslab_max * kResStride, grec_half = (size_t)kCounters * kResStride;   // >= the packed sizes
-        double *gpart = reinterpret_cast<double *>(ws + L.off_gpartial);
-        BcdBlockArgs base;
-        base.acc_out = nullptr; base.acc_in = nullptr; base.acc_zero = nullptr; base.shards = 1;
-        if (fused) {
-            base.Dt = reinterpret_cast<float *>(DsP); base.Bt = reinterpret_cast<const float *>(BsP);
-            base.CP = reinterpret_cast<const float *>(CPP); base.cdiag = reinterpret_cast<const float *>(cdiag);
-            base.frozen = frozen; base.order = a.order; base.a = reinterpret_cast<float *>(abuf);
-            base.coef_all = coef_all; base.norm_in = reinterpret_cast<const float *>(ws + L.off_norm_in);
-            base.norm_out = reinterpret_cast<float *>(a.comp_norm); base.counter = counter;
-            base.stamps = reinterpret_cast<unsigned long long *>(counter + kCounters); base.s = s; base.k = kp; base.kout = k;
-            // up to kCounters workgroups: every workgroup sums all records itself in (B) - the pre-summing tail (a
-            // release fence + a serial reduction behind the slowest workgroup of a group) costs more than the second
-            // round of record loads it saves (measured at 32 workgroups: 17.7 -> 15.9 us per launch); beyond, groups
-            base.group = nslab <= kCounters ? nslab : ((nslab + 31) / 32 > kGroup ? (nslab + 31) / 32 : kGroup);
-            base.Dt_out = reinterpret_cast<float *>(a.Dt); base.subset = a.subset;
-            base.shards = nslab > MODL_ACC_SHARD_MIN ? kAccShards : 1;       // (one accumulator: 30 workgroups at the metric's shape)
-        }
-        // deferred statistics product riding along (launches 1 .. nblk carry cdiv(tiles, nblk) tiles each)
-        BcdRiderArgs rid;
-        rid.nslab = persist_rt ? nslab + 1 : nslab;                 // (the persistent launch: the resolver in front of the row workgroups)
-#ifdef MODL_DIAG
-        if (fused) rid.dbg = reinterpret_cast<unsigned long long *>(counter + kCounters) + 40;     // (stamps of the first riding tile)
-#endif
-        int ride_tiles = 0, ride_per = 0, ride_next = 0;
-        if (fused && a.rider) {
-            const StatsRider &R = *a.rider;
-            DenseOperand Xo, Cd;
-            Xo.ptr = R.X; Xo.si = 1; Xo.sk = R.ldx;                    // element (i = feature, kk = sample)
-            Cd.ptr = R.code; Cd.si = 1; Cd.sk = k;                     // element (i = atom, kk = sample)
-            EpiStatsSkip<float> epi{static_cast<float *>(R.Bt), k, R.stamp, R.step, (float)R.beta, (float)R.wt,
-                                    (float)R.bdiv, R.replace};
-            rid.P = plan_stats<EpiStatsSkip<float>>(Xo, Cd, R.p, k, R.b, epi);
-            // wide tiles (gemm_wide.hpp) keep their X tile in LDS for 128 atoms: X is fetched twice instead of eight
-            // times, and a tile is still short enough for the shadow of a block step.  (Very large feature counts do
-            // not ride at all: somf_step.hip runs their product as its own k-wide launch.)
-            const int wbm = 32;
-            if (R.p >= 2048) rid.W = plan_wide<32, EpiStatsSkip<float>, 128>(Xo, Cd, R.p, k, R.b, epi);
-            rid.wide = rid.W.ok ? wbm : 0;
-            if ((rid.P.ok || rid.wide) && R.p > 0) {
-                ride_tiles = rid.wide ? rid.W.tm * rid.W.tn : rid.P.tn * rid.P.tm;
-                // as few carrier launches as the idle compute units allow (a tile needs a compute unit to itself for
-                // most of a block step; more tiles than free units would queue and stretch the launch)
-                static const int ncu = [] {                             // one process per GPU: queried once
-                    int dev = 0;
-                    hipDeviceProp_t prop;
-                    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                        return prop.multiProcessorCount;
-                    return 256;
-                }();
-                const int free_cu = (ncu - rid.nslab > 64) ? ncu - rid.nslab : 64;
-                const int nblk_all = (int)cdiv(k, kNB);
-                int carriers = (int)cdiv(ride_tiles, free_cu);
-                if (carriers > nblk_all) carriers = nblk_all;
-                if (carriers < 1) carriers = 1;
-                ride_per = (int)cdiv(ride_tiles, carriers);
-                a.rider->consumed = 1;
-            }
-        }
-        // a launch that carries k-wide tiles needs their LDS (one workgroup per compute unit then)
-        auto lds_bytes = [&](int extra) {
-            size_t n = bcd_block_lds(GPW, RT);
-            if (extra > 0 && rid.wide) n = std::max(n, wide_lds_bytes<32, 128>());
-            return n;
-        };
-        auto ride = [&](BcdRiderArgs &r) {                             // the next share of tiles; returns their number
-            r = rid;
-            r.t0 = ride_next;
-            r.t1 = (ride_next + ride_per < ride_tiles) ? ride_next + ride_per : ride_tiles;
-            ride_next = r.t1;
-            return r.t1 - r.t0;
-        };
-        if (persist_rt) {
-            BcdPersistArgs pa;
-            pa.DsP = reinterpret_cast<const float *>(DsP); pa.BsP = reinterpret_cast<const float *>(BsP);
-            pa.CPP = reinterpret_cast<const float *>(CPP); pa.cdiag = reinterpret_cast<const float *>(cdiag);
-            pa.frozen = frozen; pa.order = a.order; pa.subset = a.subset;
-            pa.coef_all = coef_all; pa.qcoef = qcoef;
-            pa.norm_in = reinterpret_cast<const float *>(ws + L.off_norm_in);
-            pa.norm_out = reinterpret_cast<float *>(a.comp_norm);
-            pa.Dt_out = reinterpret_cast<float *>(a.Dt);
-            pa.acc = pacc;
-            pa.rec = reinterpret_cast<double *>(ws + L.off_prec);
-            pa.Sbuf = reinterpret_cast<double *>(ws + L.off_Sbuf);
-            pa.arrive = pflags; pa.sflag = pflags + kPersistBlocksMax; pa.err = pflags + 2 * kPersistBlocksMax;
-            pa.flags = a.persist_flags;
-            pa.C = reinterpret_cast<const float *>(a.C);
-            pa.expect = nslab;
-#ifdef MODL_DIAG
-            // diagnostics build only: 3 makes the resolver wait for a workgroup that never comes (the recovery path), 4 makes it
-            // wait for it from the SECOND block on (the unrecoverable path), tests/test_gpu_step.py
-            pa.inject = g_bcd_persist.load(std::memory_order_relaxed);
-#endif
-            pa.stamps = reinterpret_cast<unsigned long long *>(ws + L.off_pstamps);
-            pa.s = s; pa.k = kp; pa.kout = k; pa.nblk = (int)cdiv(k, kNB); pa.nrow = nslab; pa.shards = pshards;
-            BcdRiderArgs r = rid;                                       // every riding tile with the one launch
-            r.t0 = 0; r.t1 = ride_tiles;
-            int extra = ride_tiles;
-            if (a.stage && a.stage->src) {                              // + one workgroup: the next minibatch's parameters
-                r.stage = *a.stage;
-                a.stage->consumed = 1;
-                ++extra;
-            }
-            MODL_TRY(launch_bcd_persist(stream, pa, r, extra, (ride_tiles > 0 && rid.wide) ? wide_lds_bytes<32, 128>() : 0, persist_rt));
-            ++nl;
-            if (launches) *launches += nl;
-            return MODL_OK;
-        }
-        int blk_i = 0, j0_prev = 0, nb_prev = 0;
-        for (int j0 = 0; j0 < k; j0 += kNB, ++blk_i) {
-            const int nb = (k - j0 < kNB) ? k - j0 : kNB;
-            double *CAcur = CA[blk_i & 1], *CAprev = blk_i ? CA[(blk_i - 1) & 1] : nullptr;
-            if (fused) {
-                BcdBlockArgs ba = base;
-                ba.rec_out = partial + (size_t)(blk_i & 1) * rec_half; ba.rec_in = partial + (size_t)((blk_i + 1) & 1) * rec_half;
-                ba.grec_out = gpart + (size_t)(blk_i & 1) * grec_half; ba.grec_in = gpart + (size_t)((blk_i + 1) & 1) * grec_half;
-                ba.j0 = j0; ba.nb = nb; ba.j0_prev = j0_prev; ba.nb_prev = blk_i ? nb_prev : 0;
-                if (fused_acc) {
-                    ba.acc_out = fused_acc + (size_t)(blk_i % 3) * kAccShards * kAccWords;
-                    ba.acc_in = fused_acc + (size_t)((blk_i + 2) % 3) * kAccShards * kAccWords;
-                    ba.acc_zero = fused_acc + (size_t)((blk_i + 1) % 3) * kAccShards * kAccWords;
-                    ba.group = nslab;                                   // (no pre-summed groups: one accumulator)
-                }
-                BcdRiderArgs r = rid;
-                const int extra = blk_i ? ride(r) : 0;                 // (launch 0 is short: no resolver)
-                hipLaunchKernelGGL(blk, dim3(nslab + extra), dim3(384), lds_bytes(extra), stream, ba, r);
-                MODL_LAUNCH_CHECK();
-                ++nl;
-            } else {
-                if (CAprev) {
-                    hipLaunchKernelGGL((bcd_apply_kernel<T>), dim3((unsigned)cdiv(s, 64)), dim3(256), 0, stream, abuf,
-                                       CAprev, a.Dt, a.subset, a.order, s, k, j0_prev, nb_prev);
-                    MODL_LAUNCH_CHECK();
-                    ++nl;
-                }
-                Operand A, B;
-                A.ptr = a.Dt; A.si = k; A.sk = 1; A.gi = gather32(a.subset);
-                B.ptr = CP + j0; B.si = 1; B.sk = k;         // B(n = jj, kk = m) = CP[m][j0 + jj]
-                EpiBcdA<T> epi{abuf, a.Dt, a.Bt, cdiag, frozen, a.subset, a.order, k, j0};
-                SplitWs none;
-                MODL_TRY((launch_gemm<T, EpiBcdA<T>>(stream, A, B, s, nb, k, epi, none, &nl, 512, 1)));
-                hipLaunchKernelGGL((bcd_gram_kernel<T>), dim3(nslab), dim3(256), 0, stream, abuf, a.Dt, a.subset,
-                                   a.order, s, k, j0, nb, partial);
-                MODL_LAUNCH_CHECK();
-                hipLaunchKernelGGL((bcd_resolve_kernel<T>), dim3(1), dim3(256), 0, stream, partial, nslab, coef_all,
-                                   a.order, k, j0, nb, a.comp_norm, CAcur);
-                MODL_LAUNCH_CHECK();
-                nl += 2;
-            }
-            j0_prev = j0; nb_prev = nb;
-        }
-        // the last block's atoms
-        if (fused) {
-            BcdBlockArgs ba = base;                  // nb == 0: resolve and apply only
-            ba.rec_out = nullptr; ba.grec_out = nullptr;
-            ba.rec_in = partial + (size_t)((blk_i + 1) & 1) * rec_half; ba.grec_in = gpart + (size_t)((blk_i + 1) & 1) * grec_half;
-            ba.j0 = 0; ba.nb = 0; ba.j0_prev = j0_prev; ba.nb_prev = nb_prev;
-            if (fused_acc) {
-                ba.acc_out = nullptr; ba.acc_zero = nullptr;
-                ba.acc_in = fused_acc + (size_t)((blk_i + 2) % 3) * kAccShards * kAccWords;     // (blk_i: the blocks launched so far)
-                ba.group = nslab;
-            }
-            BcdRiderArgs r = rid;
-            ride_per = ride_tiles - ride_next;                         // whatever is left
-            int extra = ride(r);
-            if (a.stage && a.stage->src) {                             // + one workgroup: the next minibatch's parameters
-                r.stage = *a.stage;
-                a.stage->consumed = 1;
-                hipLaunchKernelGGL(blk, dim3(nslab + extra + 1), dim3(384), lds_bytes(extra), stream, ba, r);
-            } else
-            hipLaunchKernelGGL(blk, dim3(nslab + extra), dim3(384), lds_bytes(extra), stream, ba, r);
-            MODL_LAUNCH_CHECK();
-            nl += 1;
-        } else {
-            hipLaunchKernelGGL((bcd_apply_kernel<T>), dim3((unsigned)cdiv(s, 64)), dim3(256), 0, stream, abuf,
-                               CA[(blk_i - 1) & 1], a.Dt, a.subset, a.order, s, k, j0_prev, nb_prev);
-            MODL_LAUNCH_CHECK();
-            ++nl;
-        }
-    } else {
-        return dict_update_generic<T>(stream, a, launches);
-    }
-    if (launches) *launches += nl;
-    return MODL_OK;
-}
-
 // the last atom of a sweep of atom_step_kernel launches with staged rows: its values into the dictionary
 template <typename T>
 __global__ __launch_bounds__(256) void atom_stage_flush_kernel(T *Dt, const int32_t *subset, int64_t s, int k, int j,
@@ -3055,277 +2734,604 @@ __global__ __launch_bounds__(256) void atom_stage_flush_kernel(T *Dt, const int3
     if (f < s) Dt[sub_row(subset, f) * k + j] = stage[f];
 }
 
-// generic path: the sweep order is needed on the host (one launch pair per atom)
+// ---------------------------------------------------------------------- driver
+// Which kernels take a dictionary update is decided in one place, du_route - a pure function: the debug switches and the two facts
+// about the device (compute units, residency of the persistent launch) are arguments - and launched from one place, dict_update:
+// validate, route, workspace, a helper per family (du_sgd ... du_step).  dict_update_route names the route of a direct call.
+static int device_cu_count() {                                       // one process per GPU: queried once
+    static const int ncu = [] {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+    }();
+    return ncu;
+}
+
+struct DuSwitches { int persist, acc, tiny, few, mwg, pipe; };       // modl_debug_set's values, read once per route
+static DuSwitches du_route_switches() {
+    const auto get = [](const std::atomic<int> &x) { return x.load(std::memory_order_relaxed); };
+    return {get(g_bcd_persist), get(g_bcd_acc), get(g_bcd_tiny), get(g_bcd_few), get(g_atom_mwg), get(g_atom_pipe)};
+}
+
+// workgroups of a gradient launch of the per-atom paths: 4 waves each (the projection wants registers: 256 threads), one
+// feature per wave while the grid lasts
+static int atom_grad_wgs(int64_t s, const DuLayout &L) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(cdiv(s, 4), 512), L.nwg_grad));
+}
+static size_t atom_sweep_lds(size_t tsz, int64_t s, int k) { return sizeof(double) * (16 + (size_t)k) + tsz * (size_t)s + 16; }
+
+// L = du_layout(tsz, s, k).  persist_fits(kp, RT, nrow, extra_lds): can the resolver + nrow row workgroups of the persistent
+// launch be resident together (bcd_persist_fits on a device)?  wide_rider: a statistics rider of k-wide tiles comes along.
+template <class Fits>
+static DuRoute du_route(size_t tsz, int k, int64_t s, int optimizer, int comp_pos, double l1_ratio, bool has_order, bool wide_rider,
+                        bool allow_persist, const DuSwitches &sw, const DuLayout &L, int ncu, Fits &&persist_fits) {
+    DuRoute r;
+    const auto is = [&r](DuFamily f) { r.family = f; return r; };
+    r.KPL = k <= 64 ? 1 : k <= 128 ? 2 : k <= 256 ? 4 : k <= 512 ? 8 : 16;
+    r.nslab = (int)cdiv(s, kGramRows);                                // (sgd, unfused; block and persist: below)
+    if (optimizer == MODL_OPT_SGD) return is(DU_SGD);                 // (any k)
+    if (k > 1024) return is(DU_WIDE);
+    if (l1_ratio == 0.0 && !comp_pos) {                               // the blocked path
+        const int kp = (int)cdiv(k, 4) * 4;                           // atoms of the packed arrays (dead ones behind the k real)
+        r.GPW = kp <= 256 ? 8 : 16;
+        if (!(tsz == 4 && k <= 512)) {
+            r.nfew = (int)cdiv(s, kFewRows);
+            if (tsz == 8 && s > kTinyRows && r.nfew <= kFewMaxWg && sw.tiny && sw.few) return is(DU_FEW);
+            return is(tsz == 8 && s <= kTinyRows && sw.tiny ? DU_TINY : DU_UNFUSED);
+        }
+        r.family = DU_BLOCK;
+        r.RT = (s <= MODL_RT1_MAX || k > 256) ? 1 : 2;                // k > 256: 64-row tiles would spill registers
+        // one workgroup per compute unit (registers): a grid that is a few workgroups larger than the chip runs in two
+        // rounds, i.e. every block launch takes twice as long (s = 16.7 k: 261 workgroups of 64 features -> 174 of 96)
+        if (r.RT == 2 && cdiv(s, 64) > ncu && cdiv(s, 96) <= ncu) r.RT = 3;
+        // ONE persistent launch per dictionary update (bcd_persist.hip) when its workgroups - the resolver + one per 32 or 64
+        // sampled rows - can all be resident at once (reduction 1 at the metric's shape: 157 workgroups of 64 rows, 0.173 ->
+        // 0.138 ms per dictionary update); otherwise one launch per block of 32 atoms.  The LDS of riding k-wide tiles is part of
+        // the question: a launch that cannot carry them must not have marked them consumed
+        if (allow_persist && sw.persist && sw.acc && cdiv(k, kNB) <= kPersistBlocksMax) {
+            const size_t xl = wide_rider ? wide_lds_bytes<32, 128>() : 0;
+            const int64_t n1 = cdiv(s, 32), n2 = cdiv(s, 64);
+            const int rt = (n1 <= kPersistRowsMax && persist_fits(kp, 1, (int)n1, xl))              ? 1
+                           : (kp <= 256 && n2 <= kPersistRowsMax && persist_fits(kp, 2, (int)n2, xl)) ? 2 : 0;
+            if (rt) { r.family = DU_PERSIST; r.RT = rt; }
+        }
+        r.nslab = (int)cdiv(s, 32 * r.RT);
+        r.shards = r.nslab > MODL_ACC_SHARD_MIN ? kAccShards : 1;     // (one accumulator: 30 workgroups at the metric's shape)
+        r.acc = r.family == DU_BLOCK && sw.acc;
+        return r;
+    }
+    r.l1 = l1_ratio == 1.0;
+    // small problems: the whole sweep in one launch (u in LDS, atom_sweep_kernel); thread-per-row reads: only worth it when tiny
+    if (has_order && atom_sweep_lds(tsz, s, k) <= 64 * 1024 && (double)s * k <= 32e3) return is(DU_SWEEP);
+    // groups of atoms per launch pair while the vector fits the registers of the projecting workgroup
+    if (s <= (int64_t)kProjEpt * 256 && k <= 512) {
+        r.G = (s <= 20 * 256) ? 8 : 4;                                // (24 elements per thread: the changes of 3 atoms fit, not of 7)
+        r.EPT = r.G == 4 ? kProjEpt : (s <= 12 * 256 ? 12 : 20);
+        return is(DU_GROUPED);
+    }
+    r.lds = tsz * (size_t)s <= 60 * 1024;
+    if (!(r.lds && s > (int64_t)kProjEpt * 256)) return is(DU_STEP);
+    // beyond the register-resident projection: groups of kStepGroup atoms, compact rows (atom_grad4_kernel), a launch per atom
+    r.family = DU_STAGED;
+    r.G = kStepGroup;
+    const int nwg = atom_grad_wgs(s, L), nwg_corr = (int)cdiv(s, 256);     // (a thread per feature)
+    // l1 atoms on at most 64 workgroups: the projection spread over the launch (mwg_l1_project); its two exchange buffers
+    // (sentinels) and the abort word live in the blocked path's record space, unused here
+    r.spread = r.l1 && nwg_corr <= kMwgMaxWg && sw.mwg &&
+               sizeof(double) * 2 * (size_t)L.nslab_max * (kNB * kNB + kNB) >= sizeof(double) * 2 * kMwgWords + 64;
+    // MODL_DEBUG_ATOM_MWG = 1 (default): the launch's LAST workgroup projects the vector from registers (atom_project_regs: 20.2 ms
+    // per minibatch at the HCP shape); 3: the projection spread over the launch's workgroups (mwg_l1_project: 27.0 ms)
+    const bool regs = r.l1 && sw.mwg == 1 && s <= 64 * 256;
+    // the pipelined sweep: the gradient launch of group g + 1 rides on the atom launches of group g
+    r.pipelined = (r.spread || regs) && cdiv(k, r.G) >= 2 && sw.pipe != 0 && s > kPipeMinRows && (int64_t)2 * r.G * nwg <= L.nwg_grad;
+    if (r.pipelined) {
+        r.regs = regs ? (s <= 40 * 256 ? 40 : 64) : 0;
+        // two elements per thread beyond 32 workgroups: half as many slots to poll and sum per exchange (C6: 26.8 against 27.3 ms)
+        r.ept = (nwg_corr > 32 && !regs) ? 2 : 1;
+    }
+    return r;
+}
+
+static int du_route_name(const DuRoute &r, char *buf, size_t cap) {
+    int n = -1;
+    switch (r.family) {
+    case DU_SGD: n = snprintf(buf, cap, "sgd"); break;
+    case DU_WIDE: n = snprintf(buf, cap, "wide"); break;
+    case DU_TINY: n = snprintf(buf, cap, "tiny"); break;
+    case DU_FEW: n = snprintf(buf, cap, "few/nfew%d", r.nfew); break;
+    case DU_UNFUSED: n = snprintf(buf, cap, "unfused"); break;
+    case DU_BLOCK: n = snprintf(buf, cap, "block/RT%d/GPW%d/acc%d/shards%d", r.RT, r.GPW, r.acc ? 1 : 0, r.shards); break;
+    case DU_PERSIST: n = snprintf(buf, cap, "persist/RT%d", r.RT); break;
+    case DU_SWEEP: n = snprintf(buf, cap, "sweep"); break;
+    case DU_GROUPED: n = snprintf(buf, cap, "grouped/EPT%d/G%d/KPL%d/%s", r.EPT, r.G, r.KPL, r.l1 ? "l1" : "enet"); break;
+    case DU_STAGED:
+        if (r.pipelined && r.regs) n = snprintf(buf, cap, "staged_pipe/KPL%d/regs%d", r.KPL, r.regs);
+        else if (r.pipelined) n = snprintf(buf, cap, "staged_pipe/KPL%d/spread/ept%d", r.KPL, r.ept);
+        else n = snprintf(buf, cap, "staged/grad4KPL%d/%s", r.KPL, r.spread ? "spread" : (r.l1 ? "lds_l1" : "lds_enet"));
+        break;
+    case DU_STEP: n = snprintf(buf, cap, "step/KPL%d/%s", r.KPL, r.lds ? "lds" : "global"); break;
+    }
+    return (n >= 0 && (size_t)n < cap) ? MODL_OK : MODL_EINVAL;
+}
+
+// the route of a direct call (modl_dict_update_*: order and h_order given, no rider, no stage), under the current switches.
+// ncu > 0: that many compute units, one workgroup of the persistent launch on each - no device is touched; 0: the current device
+int dict_update_route(int dtype, int k, int64_t s, int optimizer, int comp_pos, double comp_l1_ratio, int ncu, char *buf, size_t cap) {
+    if ((dtype != MODL_F32 && dtype != MODL_F64) || k <= 0 || k > MODL_MAX_COMPONENTS || s <= 0 || ncu < 0 || !buf) return MODL_EINVAL;
+    const size_t tsz = dtype == MODL_F32 ? 4 : 8;
+    const DuLayout L = du_layout(tsz, s, k);
+    const bool allow_persist = DictUpdateArgs<float>{}.allow_persist;
+    const auto route = [&](int n, auto &&fits) {
+        return du_route(tsz, k, s, optimizer, comp_pos, comp_l1_ratio, true, false, allow_persist, du_route_switches(), L, n, fits);
+    };
+    const auto on_ncu = [ncu](int kp, int RT, int nrow, size_t extra_lds) {
+        return std::max(bcd_persist_lds(kp, RT), extra_lds) <= 160 * 1024 && nrow <= kPersistRowsMax && 1 + nrow <= ncu;
+    };
+    return du_route_name(ncu > 0 ? route(ncu, on_ncu) : route(device_cu_count(), bcd_persist_fits), buf, cap);
+}
+
+template <typename T> struct DuCtx {                                  // what every family's helper gets
+    hipStream_t stream;
+    const DictUpdateArgs<T> &a;
+    char *ws;                                                         // (a.ws)
+    const DuLayout &L;
+    const DuRoute &R;
+    int nl;                                                           // launches so far
+};
+template <typename U> static U *ws_at(char *ws, size_t off) { return reinterpret_cast<U *>(ws + off); }
+// a launch on the stream of the helper's context c, checked and counted
+#define DU_LAUNCH(kern, grid, block, lds, ...)                             \
+    do {                                                                   \
+        hipLaunchKernelGGL(kern, grid, block, lds, c.stream, __VA_ARGS__); \
+        MODL_LAUNCH_CHECK();                                               \
+        ++c.nl;                                                            \
+    } while (0)
+
+// KPL atoms per lane of the gradient kernels, as a constant: f(std::integral_constant<int, KPL>{}), KPL <= MAX
+template <int MAX = 16, class F> static void for_kpl(int kpl, F &&f) {
+    if (kpl == 1) f(std::integral_constant<int, 1>{});
+    else if (kpl == 2) f(std::integral_constant<int, 2>{});
+    else if (kpl == 4) f(std::integral_constant<int, 4>{});
+    else if (MAX == 8 || kpl == 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, MAX>{});
+}
+
+// the G atoms of the sweep order from position t0 on (the last group: its first atom repeated behind the n real ones; t0 = k:
+// no atoms).  dict_update has checked the whole order before the first launch.
+template <int G> static AtomGroupN<G> atom_group(const int64_t *h_order, int k, int t0) {
+    AtomGroupN<G> g;
+    g.n = t0 >= k ? 0 : (k - t0 < G ? k - t0 : G);
+    for (int x = 0; x < G; ++x) g.j[x] = g.n ? (int)h_order[t0 + (x < g.n ? x : 0)] : 0;
+    return g;
+}
+
+template <typename T> static int du_sgd(DuCtx<T> &c) {
+    const DictUpdateArgs<T> &a = c.a;
+    const int k = a.k, nslab = c.R.nslab;
+    double *colp = ws_at<double>(c.ws, c.L.off_colp);
+    T *Dnew = ws_at<T>(c.ws, c.L.off_Dnew);
+    DU_LAUNCH((col_norm_partial_kernel<T>), dim3(nslab), dim3(256), 0, a.Dt, a.subset, a.s, k, a.comp_l1_ratio, colp);
+    DU_LAUNCH((col_norm_add_kernel<T>), dim3((unsigned)cdiv(k, 256)), dim3(256), 0, colp, nslab, k, a.comp_norm);
+    Operand A, B;
+    A.ptr = a.Dt; A.si = k; A.sk = 1; A.gi = gather32(a.subset);
+    B.ptr = a.C; B.si = k; B.sk = 1;                 // B(n = j, kk = m) = C[j][m]
+    EpiSgd<T> epi{Dnew, a.Dt, a.Bt, a.subset, k, (T)(a.w * a.step_size)};
+    SplitWs none;
+    MODL_TRY((launch_gemm<T, EpiSgd<T>>(c.stream, A, B, a.s, k, k, epi, none, &c.nl, 512, 1)));
+    DU_LAUNCH((sgd_project_kernel<T>), dim3(k), dim3(256), 0, Dnew, a.Dt, a.subset, a.s, k, a.comp_l1_ratio, a.comp_norm);
+    return MODL_OK;
+}
+
+template <typename T> struct BlockedWs {                              // the blocked path's pieces of the workspace
+    T *CP, *cdiag, *abuf, *norm_in, *DsP, *BsP;
+    int32_t *frozen;
+    double *partial, *coef_all, *CA[2];
+    unsigned int *counter;
+    BlockedWs(char *ws, const DuLayout &L)
+        : CP(ws_at<T>(ws, L.off_CP)), cdiag(ws_at<T>(ws, L.off_cdiag)), abuf(ws_at<T>(ws, L.off_a)), norm_in(ws_at<T>(ws, L.off_norm_in)),
+          DsP(ws_at<T>(ws, L.off_Dnew)), BsP(ws_at<T>(ws, L.off_BsP)), frozen(ws_at<int32_t>(ws, L.off_frozen)),
+          partial(ws_at<double>(ws, L.off_partial)), coef_all(ws_at<double>(ws, L.off_coef)),
+          CA{ws_at<double>(ws, L.off_Tp), ws_at<double>(ws, L.off_Tp) + kResStride},
+          counter(reinterpret_cast<unsigned int *>(ws_at<double>(ws, L.off_Tp) + 2 * kResStride)) {}
+};
+
+// tiny, few, unfused: bcd_prepare_kernel, then the whole sweep by one workgroup (tiny), in one launch on a few workgroups
+// (few), or apply / product / Gram / resolve per block of 32 atoms
+template <typename T> static int du_unfused(DuCtx<T> &c) {
+    const DictUpdateArgs<T> &a = c.a;
+    const DuRoute &R = c.R;
+    const int k = a.k;
+    const int64_t s = a.s;
+    const BlockedWs<T> W(c.ws, c.L);
+    long long *few_x = R.family == DU_FEW ? ws_at<long long>(c.ws, c.L.off_few) : nullptr;
+    const long long few_words = 3LL * R.nfew * kFewRec;               // (the error word sits right behind them)
+    DU_LAUNCH((bcd_prepare_kernel<T>), dim3(k > kNB ? k : kNB), dim3(256), sizeof(int32_t) * (size_t)k, a.C, a.order, k, W.CP, W.cdiag,
+              W.frozen, W.coef_all, W.counter, a.comp_norm, W.norm_in, few_x, few_words);
+    if (R.family == DU_FEW) {
+        const size_t lds = bcd_tiny_lds(sizeof(T), kFewRows) + sizeof(T) * ((size_t)k + 1) + sizeof(int64_t) * kFewRows + 32;
+        MODL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bcd_few_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        DU_LAUNCH((bcd_few_kernel<T>), dim3(R.nfew), dim3(256), lds, a.Dt, a.Bt, W.CP, W.cdiag, W.frozen, W.coef_all, a.subset, a.order, (int)s,
+                  k, a.comp_norm, (const T *)W.norm_in, reinterpret_cast<double *>(few_x), reinterpret_cast<unsigned int *>(few_x + few_words),
+                  a.persist_flags);
+        return MODL_OK;
+    }
+    if (R.family == DU_TINY) {
+        MODL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bcd_tiny_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        DU_LAUNCH((bcd_tiny_kernel<T>), dim3(1), dim3(256), bcd_tiny_lds(sizeof(T), s), a.Dt, a.Bt, W.CP, W.cdiag, W.frozen, W.coef_all, a.subset,
+                  a.order, (int)s, k, a.comp_norm);
+        return MODL_OK;
+    }
+    int blk_i = 0, j0_prev = 0, nb_prev = 0;
+    for (int j0 = 0;; j0 += kNB, ++blk_i) {                           // (j0 >= k: the last block's atoms are applied, nothing more)
+        if (blk_i)
+            DU_LAUNCH((bcd_apply_kernel<T>), dim3((unsigned)cdiv(s, 64)), dim3(256), 0, W.abuf, W.CA[(blk_i - 1) & 1], a.Dt, a.subset, a.order,
+                      s, k, j0_prev, nb_prev);
+        if (j0 >= k) break;
+        const int nb = (k - j0 < kNB) ? k - j0 : kNB;
+        Operand A, B;
+        A.ptr = a.Dt; A.si = k; A.sk = 1; A.gi = gather32(a.subset);
+        B.ptr = W.CP + j0; B.si = 1; B.sk = k;         // B(n = jj, kk = m) = CP[m][j0 + jj]
+        EpiBcdA<T> epi{W.abuf, a.Dt, a.Bt, W.cdiag, W.frozen, a.subset, a.order, k, j0};
+        SplitWs none;
+        MODL_TRY((launch_gemm<T, EpiBcdA<T>>(c.stream, A, B, s, nb, k, epi, none, &c.nl, 512, 1)));
+        DU_LAUNCH((bcd_gram_kernel<T>), dim3(R.nslab), dim3(256), 0, W.abuf, a.Dt, a.subset, a.order, s, k, j0, nb, W.partial);
+        DU_LAUNCH((bcd_resolve_kernel<T>), dim3(1), dim3(256), 0, W.partial, R.nslab, W.coef_all, a.order, k, j0, nb, a.comp_norm, W.CA[blk_i & 1]);
+        j0_prev = j0; nb_prev = nb;
+    }
+    return MODL_OK;
+}
+
+// The deferred statistics product riding along the fused launches (launches 1 .. nblk carry cdiv(tiles, nblk) tiles each;
+// the persistent launch all of them): its plan, and the share of tiles of each carrier.  Marks the rider consumed.
+struct RidePlan {
+    BcdRiderArgs rid;
+    int tiles = 0, per = 0, next = 0;
+    int take(BcdRiderArgs &r) {                                       // the next share of tiles; returns their number
+        r = rid;
+        r.t0 = next;
+        next = r.t1 = (next + per < tiles) ? next + per : tiles;
+        return r.t1 - r.t0;
+    }
+    // a launch that carries k-wide tiles needs their LDS (one workgroup per compute unit then)
+    size_t lds(size_t own, int extra) const { return (extra > 0 && rid.wide) ? std::max(own, wide_lds_bytes<32, 128>()) : own; }
+};
+template <typename T> static RidePlan plan_ride(const DuCtx<T> &c, const BlockedWs<T> &W) {
+    RidePlan p;
+    const int k = c.a.k;
+    p.rid.nslab = c.R.family == DU_PERSIST ? c.R.nslab + 1 : c.R.nslab;   // (the persistent launch: the resolver in front of the row workgroups)
+#ifdef MODL_DIAG
+    p.rid.dbg = reinterpret_cast<unsigned long long *>(W.counter + kCounters) + 40;     // (stamps of the first riding tile)
+#endif
+    if (!c.a.rider) return p;
+    const StatsRider &R = *c.a.rider;
+    DenseOperand Xo, Cd;
+    Xo.ptr = R.X; Xo.si = 1; Xo.sk = R.ldx;                    // element (i = feature, kk = sample)
+    Cd.ptr = R.code; Cd.si = 1; Cd.sk = k;                     // element (i = atom, kk = sample)
+    EpiStatsSkip<float> epi{static_cast<float *>(R.Bt), k, R.stamp, R.step, (float)R.beta, (float)R.wt, (float)R.bdiv, R.replace};
+    p.rid.P = plan_stats<EpiStatsSkip<float>>(Xo, Cd, R.p, k, R.b, epi);
+    // wide tiles (gemm_wide.hpp) keep their X tile in LDS for 128 atoms: X is fetched twice instead of eight times, and a
+    // tile is still short enough for the shadow of a block step.  (Very large feature counts do not ride at all:
+    // somf_step.hip runs their product as its own k-wide launch.)
+    if (R.p >= 2048) p.rid.W = plan_wide<32, EpiStatsSkip<float>, 128>(Xo, Cd, R.p, k, R.b, epi);
+    p.rid.wide = p.rid.W.ok ? 32 : 0;
+    if ((p.rid.P.ok || p.rid.wide) && R.p > 0) {
+        p.tiles = p.rid.wide ? p.rid.W.tm * p.rid.W.tn : p.rid.P.tn * p.rid.P.tm;
+        // as few carrier launches as the idle compute units allow (a tile needs a compute unit to itself for most of a
+        // block step; more tiles than free units would queue and stretch the launch)
+        const int ncu = device_cu_count();
+        const int free_cu = (ncu - p.rid.nslab > 64) ? ncu - p.rid.nslab : 64;
+        const int carriers = std::max(1, std::min((int)cdiv(p.tiles, free_cu), (int)cdiv(k, kNB)));
+        p.per = (int)cdiv(p.tiles, carriers);
+        c.a.rider->consumed = 1;
+    }
+    return p;
+}
+
+// block, persist: the first launch.  acc / pacc + qcoef: the accumulators of the one or of the other, else null
+using BlockKernel = void (*)(BcdBlockArgs, BcdRiderArgs);
 template <typename T>
-int dict_update_generic(hipStream_t stream, const DictUpdateArgs<T> &a, int *launches) {
-    const int64_t *h_order = a.h_order;
-    if (!h_order) return MODL_EINVAL;
+static int du_setup(DuCtx<T> &c, const BlockedWs<T> &W, long long *acc, long long *pacc, double *qcoef, BlockKernel &blk) {
+    const DictUpdateArgs<T> &a = c.a;
+    const DuRoute &R = c.R;
+    const int k = a.k, kp = (int)cdiv(k, 4) * 4;
+    static_assert(sizeof(long long) * 3 * kAccShards * kAccWords <= sizeof(double) * 2 * (size_t)kCounters * (kNB * kNB + kNB), "accumulators fit");
+    blk = (R.RT == 1) ? (R.GPW == 8 ? bcd_block_kernel<1, 8> : bcd_block_kernel<1, 16>) : (R.RT == 2 ? bcd_block_kernel<2, 8> : bcd_block_kernel<3, 8>);
+    MODL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(blk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DU_LAUNCH((bcd_setup_kernel<T>), dim3((unsigned)(kNB + cdiv(kp, kSetupRows) + cdiv(a.s, kSetupRows))), dim3(256), 0, a.C, a.order, k, kp, W.CP,
+              W.cdiag, W.frozen, W.coef_all, W.counter, a.comp_norm, W.norm_in, a.Dt, a.Bt, a.subset, a.s, W.DsP, W.BsP, acc, pacc,
+              (long long)cdiv(k, kNB) * R.shards * kPAccWords, qcoef, ws_at<unsigned int>(c.ws, c.L.off_pflags),
+              ws_at<long long>(c.ws, c.L.off_Sbuf), pacc ? (long long)cdiv(k, kNB) * kNB * kNB : 0);
+    return MODL_OK;
+}
+
+template <typename T> static int du_persist(DuCtx<T> &c) {           // ONE launch for the whole sweep (bcd_persist.hip)
+    const DictUpdateArgs<T> &a = c.a;
+    const DuLayout &L = c.L;
+    const int k = a.k;
+    const BlockedWs<T> W(c.ws, L);
+    unsigned int *pflags = ws_at<unsigned int>(c.ws, L.off_pflags);
+    BlockKernel blk;
+    BcdPersistArgs pa;
+    double *qcoef = ws_at<double>(c.ws, L.off_qcoef);
+    pa.acc = ws_at<long long>(c.ws, L.off_pacc);
+    pa.qcoef = qcoef;
+    MODL_TRY(du_setup(c, W, nullptr, pa.acc, qcoef, blk));
+    RidePlan ride = plan_ride(c, W);
+    pa.DsP = reinterpret_cast<const float *>(W.DsP); pa.BsP = reinterpret_cast<const float *>(W.BsP);
+    pa.CPP = reinterpret_cast<const float *>(W.CP); pa.cdiag = reinterpret_cast<const float *>(W.cdiag);
+    pa.frozen = W.frozen; pa.order = a.order; pa.subset = a.subset; pa.coef_all = W.coef_all;
+    pa.norm_in = reinterpret_cast<const float *>(W.norm_in); pa.norm_out = reinterpret_cast<float *>(a.comp_norm);
+    pa.Dt_out = reinterpret_cast<float *>(a.Dt);
+    pa.rec = ws_at<double>(c.ws, L.off_prec); pa.Sbuf = ws_at<double>(c.ws, L.off_Sbuf);
+    pa.arrive = pflags; pa.sflag = pflags + kPersistBlocksMax; pa.err = pflags + 2 * kPersistBlocksMax;
+    pa.flags = a.persist_flags;
+    pa.C = reinterpret_cast<const float *>(a.C);
+    pa.expect = c.R.nslab;
+#ifdef MODL_DIAG
+    // diagnostics build only: 3 makes the resolver wait for a workgroup that never comes (the recovery path), 4 makes it
+    // wait for it from the SECOND block on (the unrecoverable path), tests/test_gpu_step.py
+    pa.inject = g_bcd_persist.load(std::memory_order_relaxed);
+#endif
+    pa.stamps = ws_at<unsigned long long>(c.ws, L.off_pstamps);
+    pa.s = a.s; pa.k = (int)cdiv(k, 4) * 4; pa.kout = k; pa.nblk = (int)cdiv(k, kNB); pa.nrow = c.R.nslab; pa.shards = c.R.shards;
+    BcdRiderArgs r = ride.rid;                                        // every riding tile with the one launch
+    int extra = r.t1 = ride.tiles;
+    if (a.stage && a.stage->src) {                                    // + one workgroup: the next minibatch's parameters
+        r.stage = *a.stage;
+        a.stage->consumed = 1;
+        ++extra;
+    }
+    MODL_TRY(launch_bcd_persist(c.stream, pa, r, extra, (ride.tiles > 0 && ride.rid.wide) ? wide_lds_bytes<32, 128>() : 0, c.R.RT));
+    ++c.nl;
+    return MODL_OK;
+}
+
+template <typename T> static int du_block(DuCtx<T> &c) {             // one launch per block of 32 atoms + one for the last block's atoms
+    const DictUpdateArgs<T> &a = c.a;
+    const DuLayout &L = c.L;
+    const int k = a.k, nslab = c.R.nslab;
+    const BlockedWs<T> W(c.ws, L);
+    // the Gram accumulators (three in rotation; in the space of the group sums, which they replace)
+    long long *acc = c.R.acc ? ws_at<long long>(c.ws, L.off_gpartial) : nullptr;
+    BlockKernel blk;
+    MODL_TRY(du_setup(c, W, acc, nullptr, nullptr, blk));
+    const size_t rec_half = (size_t)L.nslab_max * kResStride, grec_half = (size_t)kCounters * kResStride;   // >= the packed sizes
+    double *gpart = ws_at<double>(c.ws, L.off_gpartial);
+    BcdBlockArgs base;
+    base.acc_out = nullptr; base.acc_in = nullptr; base.acc_zero = nullptr;
+    base.Dt = reinterpret_cast<float *>(W.DsP); base.Bt = reinterpret_cast<const float *>(W.BsP);
+    base.CP = reinterpret_cast<const float *>(W.CP); base.cdiag = reinterpret_cast<const float *>(W.cdiag);
+    base.frozen = W.frozen; base.order = a.order; base.a = reinterpret_cast<float *>(W.abuf);
+    base.coef_all = W.coef_all; base.norm_in = reinterpret_cast<const float *>(W.norm_in);
+    base.norm_out = reinterpret_cast<float *>(a.comp_norm); base.counter = W.counter;
+    base.stamps = reinterpret_cast<unsigned long long *>(W.counter + kCounters); base.s = a.s; base.k = (int)cdiv(k, 4) * 4; base.kout = k;
+    // up to kCounters workgroups: every workgroup sums all records itself in (B) - the pre-summing tail (a release fence + a
+    // serial reduction behind the slowest workgroup of a group) costs more than the second round of record loads it saves
+    // (measured at 32 workgroups: 17.7 -> 15.9 us per launch); beyond, groups.  With the accumulator: no pre-summed groups
+    base.group = (acc || nslab <= kCounters) ? nslab : ((nslab + 31) / 32 > kGroup ? (nslab + 31) / 32 : kGroup);
+    base.Dt_out = reinterpret_cast<float *>(a.Dt); base.subset = a.subset; base.shards = c.R.shards;
+    RidePlan ride = plan_ride(c, W);
+    const size_t own_lds = bcd_block_lds(c.R.GPW, c.R.RT);
+    int blk_i = 0, j0_prev = 0, nb_prev = 0;
+    for (int j0 = 0;; j0 += kNB, ++blk_i) {
+        const bool last = j0 >= k;                                    // nb == 0: resolve and apply the last block's atoms only
+        BcdBlockArgs ba = base;
+        ba.rec_out = last ? nullptr : W.partial + (size_t)(blk_i & 1) * rec_half; ba.rec_in = W.partial + (size_t)((blk_i + 1) & 1) * rec_half;
+        ba.grec_out = last ? nullptr : gpart + (size_t)(blk_i & 1) * grec_half; ba.grec_in = gpart + (size_t)((blk_i + 1) & 1) * grec_half;
+        ba.j0 = last ? 0 : j0; ba.nb = last ? 0 : ((k - j0 < kNB) ? k - j0 : kNB); ba.j0_prev = j0_prev; ba.nb_prev = nb_prev;
+        if (acc) {                                                    // (blk_i: the blocks launched so far)
+            ba.acc_out = last ? nullptr : acc + (size_t)(blk_i % 3) * kAccShards * kAccWords;
+            ba.acc_in = acc + (size_t)((blk_i + 2) % 3) * kAccShards * kAccWords;
+            ba.acc_zero = last ? nullptr : acc + (size_t)((blk_i + 1) % 3) * kAccShards * kAccWords;
+        }
+        BcdRiderArgs r = ride.rid;
+        if (last) ride.per = ride.tiles - ride.next;                  // whatever is left
+        const int extra = blk_i ? ride.take(r) : 0;                   // (launch 0 is short: no resolver)
+        int stage_wg = 0;
+        if (last && a.stage && a.stage->src) {                        // + one workgroup: the next minibatch's parameters
+            r.stage = *a.stage;
+            a.stage->consumed = 1;
+            stage_wg = 1;
+        }
+        DU_LAUNCH(blk, dim3(nslab + extra + stage_wg), dim3(384), ride.lds(own_lds, extra), ba, r);
+        if (last) break;
+        j0_prev = j0; nb_prev = ba.nb;
+    }
+    return MODL_OK;
+}
+
+template <typename T> static int du_sweep(DuCtx<T> &c) {             // the whole sweep in one launch of one workgroup
+    const DictUpdateArgs<T> &a = c.a;
+    DU_LAUNCH((atom_sweep_kernel<T>), dim3(1), dim3(1024), atom_sweep_lds(sizeof(T), a.s, a.k), a.Dt, a.Bt, a.C, a.subset, a.order, a.s, a.k,
+              a.comp_pos, a.comp_l1_ratio, a.comp_norm);
+    return MODL_OK;
+}
+
+template <typename T> struct AtomWs {                                 // grouped, staged, step: their pieces of the workspace
+    T *u;
+    double *pold;
+    unsigned int *counter;                                            // (the last arriver re-arms it after each atom)
+    unsigned long long *stamps;
+    size_t u_lds;                                                     // the vector's copy in LDS, or 0: it stays in global memory
+    AtomWs(const DuCtx<T> &c)
+        : u(ws_at<T>(c.ws, c.L.off_u)), pold(ws_at<double>(c.ws, c.L.off_pold)),
+          counter(reinterpret_cast<unsigned int *>(ws_at<double>(c.ws, c.L.off_Tp) + 2 * kResStride)),
+          stamps(reinterpret_cast<unsigned long long *>(counter + kCounters)), u_lds(c.R.lds ? sizeof(T) * (size_t)c.a.s : 0) {}
+};
+
+template <typename T, int G> static int du_grouped(DuCtx<T> &c) {    // a launch pair per group of G atoms, the projected atoms staged
+    const DictUpdateArgs<T> &a = c.a;
+    const DuRoute &R = c.R;
+    const int k = a.k;
+    const int64_t s = a.s;
+    const AtomWs<T> W(c);
+    MODL_HIP(hipMemsetAsync(W.counter, 0, sizeof(unsigned int), c.stream));
+    const int nwg = (int)cdiv(s, 4 * kGradRows);                     // kGradRows rows per wavefront (<= 512: s <= 24 * 256)
+    const int64_t ldr = atom_row_stride(s);                           // rows of the group's scratch: whole passes of the projecting workgroup
+    double *num = ws_at<double>(c.ws, c.L.off_Dnew);
+    T *dold = reinterpret_cast<T *>(num + (size_t)G * ldr);
+    T *stage[2] = {dold + (size_t)G * ldr, dold + (size_t)2 * G * ldr};
+    unsigned long long *dbg = g_atom_stamps.load(std::memory_order_relaxed);
+    decltype(&atom_grad_group_kernel<T, 1, G>) grad = nullptr;
+    for_kpl<8>(R.KPL, [&](auto K) { grad = atom_grad_group_kernel<T, decltype(K)::value, G>; });
+    // EPT elements per thread of the projecting workgroup: 12 / 20 with groups of eight, kProjEpt with groups of four
+    constexpr int E0 = G == 8 ? 12 : kProjEpt, E1 = G == 8 ? 20 : kProjEpt;
+    const auto proj = R.EPT == E0 ? (R.l1 ? atom_project_group_kernel<T, E0, G, true> : atom_project_group_kernel<T, E0, G, false>)
+                                  : (R.l1 ? atom_project_group_kernel<T, E1, G, true> : atom_project_group_kernel<T, E1, G, false>);
+    AtomGroupN<G> gp = atom_group<G>(a.h_order, k, k);                // the group whose projected atoms are staged (none yet)
+    int gi = 0;
+    for (int t = 0; t < k; t += G, ++gi) {
+        const AtomGroupN<G> g = atom_group<G>(a.h_order, k, t);
+        DU_LAUNCH(grad, dim3(nwg), dim3(256), 0, a.Dt, a.Bt, a.C, a.subset, s, k, g, gp, stage[(gi + 1) & 1], a.comp_l1_ratio, num, dold, W.pold, ldr);
+        DU_LAUNCH(proj, dim3(1), dim3(256), 0, a.C, s, k, g, stage[gi & 1], a.comp_pos, a.comp_l1_ratio, num, dold, W.pold, nwg, a.comp_norm,
+                  a.level_hint, dbg);
+        gp = g;
+    }
+    DU_LAUNCH((atom_stage_flush_group_kernel<T, G>), dim3((unsigned)cdiv(s, 256)), dim3(256), 0, a.Dt, a.subset, s, k, gp, stage[(gi + 1) & 1], ldr);
+    return MODL_OK;
+}
+
+// Beyond the register-resident projection: groups of kStepGroup atoms (atom_grad4_kernel: one read of the dictionary per
+// group, compact rows), then a launch per atom.  Pipelined (atom_corr_project_kernel<KPL>): the gradient launch of group
+// g + 1 rides on the atom launches of group g, in scratch of its own (DuLayout::off_pipe): two staged groups, THREE sets of
+// old values (the riders write group g + 1's while the launches of group g still read group g - 1's), two sets of
+// numerators and of old-norm partial sums.  Not pipelined: a gradient launch per group, scratch in the a-tile's space.
+template <typename T> static int du_staged(DuCtx<T> &c) {
+    constexpr int G = kStepGroup;
+    static_assert(sizeof(T) * 3 * G + sizeof(double) * G <= sizeof(T) * kNB, "the group's rows fit the a-tile's space");
+    static_assert(G == 4 && kPipeMinRows == (int64_t)kProjEpt * 256, "du_layout sizes off_pipe for groups of four");
+    const DictUpdateArgs<T> &a = c.a;
+    const DuRoute &R = c.R;
+    const DuLayout &L = c.L;
+    const int k = a.k, ngroups = (int)cdiv(k, G);
+    const int64_t s = a.s, ldr = R.pipelined ? pipe_row_stride(s) : s;
+    const AtomWs<T> W(c);
+    MODL_HIP(hipMemsetAsync(W.counter, 0, sizeof(unsigned int), c.stream));
+    const int nwg = atom_grad_wgs(s, L);                              // workgroups of a gradient launch
+    const int nwg_p = (int)cdiv(s, 256 * R.ept);                      // ... of an atom launch: a thread per feature (spread, pipelined: per ept)
+    if (align_up(sizeof(T) * (size_t)3 * G * s, 16) + sizeof(double) * (size_t)G * s > sizeof(T) * (size_t)s * kNB) return MODL_ENOMEM;
+    if ((int64_t)G * nwg > L.nwg_grad) return MODL_ENOMEM;
+    // the exchange buffers of the spread projection and its abort word (the record space of the blocked path, unused here)
+    double *xch = ws_at<double>(c.ws, L.off_partial);
+    unsigned int *xabort = reinterpret_cast<unsigned int *>(xch + 2 * kMwgWords);
+    if (R.spread) {
+        MODL_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(xch), (int)kMwgSentinel32, 2 * (size_t)kMwgWords * 2, c.stream));
+        MODL_HIP(hipMemsetAsync(xabort, 0, sizeof(unsigned int), c.stream));
+    }
+    // two staged groups, the sets of old values (three when pipelined), then the f64 numerators (two sets when pipelined)
+    const size_t base_off = R.pipelined ? L.off_pipe : L.off_a;
+    const int nold = R.pipelined ? 3 : 1;
+    T *base = ws_at<T>(c.ws, base_off);
+    T *stage[2] = {base, base + (size_t)G * ldr};
+    T *dold[3] = {base + (size_t)2 * G * ldr, base + (size_t)3 * G * ldr, base + (size_t)4 * G * ldr};
+    double *num0 = ws_at<double>(c.ws, base_off + align_up(sizeof(T) * (size_t)(2 + nold) * G * ldr, 16));
+    double *num[2] = {num0, num0 + (size_t)G * ldr};
+    double *pold[2] = {W.pold, W.pold + (size_t)G * nwg};
+    decltype(&atom_grad4_kernel<T, 1>) grad4 = nullptr;
+    for_kpl(R.KPL, [&](auto K) { grad4 = atom_grad4_kernel<T, decltype(K)::value>; });
+    // the atom launches: the pipelined ones by KPL (they carry gradient workgroups), the others <0>
+    decltype(&atom_corr_project_kernel<T, 0>) corr = atom_corr_project_kernel<T, 0>;
+    if (R.pipelined) for_kpl(R.KPL, [&](auto K) { corr = atom_corr_project_kernel<T, decltype(K)::value>; });
+    unsigned long launch_no = 0;
+    const AtomGroupN<G> none = atom_group<G>(a.h_order, k, k);
+    AtomGroupN<G> gcur = atom_group<G>(a.h_order, k, 0), gnext = none, gprev = none;
+    if (R.pipelined)
+        DU_LAUNCH(grad4, dim3(nwg), dim3(256), 0, a.Dt, a.Bt, a.C, a.subset, s, k, gcur, none, (const T *)stage[1], a.comp_l1_ratio, num[0], dold[0],
+                  ldr, pold[0], nwg);
+    for (int gi = 0; gi < ngroups; ++gi) {
+        const bool has_next = gi + 1 < ngroups;
+        if (has_next) gnext = atom_group<G>(a.h_order, k, (gi + 1) * G);
+        // (not pipelined: one set of everything; the staged rows of the group before are folded in by this group's gradient launch)
+        const int cur = R.pipelined ? gi & 1 : 0, nxt = R.pipelined ? (gi + 1) & 1 : 0;
+        if (!R.pipelined)
+            DU_LAUNCH(grad4, dim3(nwg), dim3(256), 0, a.Dt, a.Bt, a.C, a.subset, s, k, gcur, gprev, (const T *)stage[(gi + 1) & 1], a.comp_l1_ratio,
+                      num[0], dold[0], ldr, pold[0], nwg);
+        for (int ai = 0; ai < gcur.n; ++ai) {
+            GradRide<T> ride{};
+            if (R.pipelined) {
+                if (has_next) {                                       // (then this group is a full one: G launches, a part each)
+                    const int lo = (int)((int64_t)ai * nwg / G), hi = (int)((int64_t)(ai + 1) * nwg / G);
+                    ride.Bt = a.Bt; ride.gn = gnext; ride.gfold = gprev; ride.stage_fold = stage[nxt];
+                    ride.num = num[nxt]; ride.dold = dold[(gi + 1) % 3]; ride.pold = pold[nxt];
+                    ride.part_stride = nwg; ride.vb0 = lo; ride.nvb = nwg; ride.nride = hi - lo;
+                }
+                ride.ept = R.ept;
+                ride.regs = R.regs ? 1 : 0;
+            }
+            // (bit 1 of the flags, MODL_DEBUG_ATOM_MWG = 2: a workgroup of the spread projection withholds its sums - the diagnostics' fallback path)
+            DU_LAUNCH(corr, dim3(nwg_p + ride.nride), dim3(256), W.u_lds, a.Dt, a.C, a.subset, s, k, gcur, ai, a.comp_pos, a.comp_l1_ratio, W.u,
+                      (const double *)num[cur], (const T *)dold[R.pipelined ? gi % 3 : 0], stage[gi & 1], ldr, (const double *)pold[cur], nwg,
+                      a.comp_norm, W.counter, W.stamps, a.level_hint, (R.spread && !R.regs) ? xch : nullptr, xabort,
+                      (int)(launch_no++ & 1) | (g_atom_mwg.load(std::memory_order_relaxed) == 2 ? 2 : 0), nwg_p, gprev,
+                      R.pipelined ? (const T *)stage[nxt] : (const T *)nullptr, R.pipelined ? (const T *)dold[(gi + 2) % 3] : (const T *)nullptr,
+                      ride);
+        }
+        gprev = gcur;
+        if (has_next) gcur = gnext;
+    }
+    // home: the staged rows nobody folds in any more - the last group's, and when pipelined the one before it (the riders of a
+    // group's launches put the group BEFORE it home; the last group has none)
+    for (int gi = R.pipelined ? ngroups - 2 : ngroups - 1; gi < ngroups; ++gi) {
+        const AtomGroupN<G> gf = atom_group<G>(a.h_order, k, gi * G);
+        for (int b = 0; b < gf.n; ++b)
+            DU_LAUNCH((atom_stage_flush_kernel<T>), dim3((unsigned)cdiv(s, 256)), dim3(256), 0, a.Dt, a.subset, s, k, gf.j[b],
+                      (const T *)(stage[gi & 1] + (size_t)b * ldr));
+    }
+    return MODL_OK;
+}
+
+template <typename T> static int du_step(DuCtx<T> &c) {              // a launch per atom: gradient row, projection, write-back
+    const DictUpdateArgs<T> &a = c.a;
+    const AtomWs<T> W(c);
+    MODL_HIP(hipMemsetAsync(W.counter, 0, sizeof(unsigned int), c.stream));
+    const int nwg = atom_grad_wgs(a.s, c.L);
+    decltype(&atom_step_kernel<T, 1>) step = nullptr;
+    for_kpl(c.R.KPL, [&](auto K) { step = atom_step_kernel<T, decltype(K)::value>; });
+    for (int t = 0; t < a.k; ++t)
+        DU_LAUNCH(step, dim3(nwg), dim3(256), W.u_lds, a.Dt, a.Bt, a.C, a.subset, a.s, a.k, (int)a.h_order[t], a.comp_pos, a.comp_l1_ratio, W.u,
+                  W.pold, a.comp_norm, W.counter, W.u_lds ? 1 : 0, W.stamps, a.level_hint);
+    return MODL_OK;
+}
+#undef DU_LAUNCH
+
+template <typename T>
+int dict_update(hipStream_t stream, const DictUpdateArgs<T> &a, int *launches) {
     const int k = a.k;
     const int64_t s = a.s;
     if (s <= 0 || k <= 0) return MODL_OK;
     if (k > MODL_MAX_COMPONENTS) return MODL_EINVAL;
-    if (k > 1024) return dict_update_wide<T>(stream, a, launches);
     const DuLayout L = du_layout(sizeof(T), s, k);
+    const DuRoute R = du_route(sizeof(T), k, s, a.optimizer, a.comp_pos, a.comp_l1_ratio, a.order != nullptr, a.rider && a.rider->p >= 2048,
+                               a.allow_persist, du_route_switches(), L, device_cu_count(), bcd_persist_fits);
+    // (the wide path checks for itself, a null h_order before the workspace)
+    if (R.family == DU_WIDE) return dict_update_wide<T>(stream, a, launches);
     if (L.total > a.ws_bytes) return MODL_ENOMEM;
-    char *ws = static_cast<char *>(a.ws);
-    T *u = reinterpret_cast<T *>(ws + L.off_u);
-    double *pold = reinterpret_cast<double *>(ws + L.off_pold);
-    // the whole sweep order is checked BEFORE the first launch: an index out of range in a later group would otherwise
-    // come back as MODL_EINVAL with earlier groups' norm budgets already updated and their projected atoms still in the
-    // staging rows
-    for (int t = 0; t < k; ++t)
-        if (h_order[t] < 0 || h_order[t] >= k) return MODL_EINVAL;
-    // small problems: the whole sweep in one launch (u in LDS, see atom_sweep_kernel)
-    const size_t lds = sizeof(double) * (16 + (size_t)k) + sizeof(T) * (size_t)s + 16;
-    if (a.order && lds <= 64 * 1024 && (double)s * k <= 32e3) {     // thread-per-row reads: only worth it when tiny
-        auto kern = atom_sweep_kernel<T>;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, stream, a.Dt, a.Bt, a.C, a.subset, a.order, s, k, a.comp_pos,
-                           a.comp_l1_ratio, a.comp_norm);
-        MODL_LAUNCH_CHECK();
-        if (launches) *launches += 1;
-        return MODL_OK;
+    if (R.family >= DU_SWEEP) {
+        // the sweep order is walked on the host, and all of it is checked BEFORE the first launch: an index out of range in a later group
+        // would otherwise come back with earlier groups' norm budgets updated and their atoms still in the staging rows
+        if (!a.h_order) return MODL_EINVAL;
+        for (int t = 0; t < k; ++t)
+            if (a.h_order[t] < 0 || a.h_order[t] >= k) return MODL_EINVAL;
     }
-    int nwg = (int)cdiv(s, 4);                       // 4 waves per workgroup (the projection wants registers: 256 threads), one feature per wave while the grid lasts
-    if (nwg > 512) nwg = 512;
-    if (nwg > L.nwg_grad) nwg = (int)L.nwg_grad;
-    if (nwg < 1) nwg = 1;
-    unsigned int *counter = reinterpret_cast<unsigned int *>(reinterpret_cast<double *>(ws + L.off_Tp) + 2 * kResStride);
-    MODL_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned int), stream));   // the last arriver re-arms it after each atom
-    const size_t u_lds = (sizeof(T) * (size_t)s <= 60 * 1024) ? sizeof(T) * (size_t)s : 0;
-    // groups of atoms per launch pair while the vector fits the registers of the projecting workgroup
-    if (s <= (int64_t)kProjEpt * 256 && k <= 512) {
-        const bool l1 = a.comp_l1_ratio == 1.0;
-        const int G = (s <= 20 * 256) ? 8 : 4;                           // (24 elements per thread: the changes of 3 atoms fit, not of 7)
-        nwg = (int)cdiv(s, 4 * kGradRows);                               // kGradRows rows per wavefront (<= 512: s <= 24 * 256)
-        const int64_t ldr = atom_row_stride(s);       // rows of the group's scratch: whole passes of the projecting workgroup
-        char *gb = ws + L.off_Dnew;
-        double *num = reinterpret_cast<double *>(gb);
-        T *dold = reinterpret_cast<T *>(num + (size_t)G * ldr);
-        T *stage[2] = {dold + (size_t)G * ldr, dold + (size_t)2 * G * ldr};
-        unsigned long long *dbg = g_atom_stamps.load(std::memory_order_relaxed);
-        auto run = [&](auto G_) -> int {
-            constexpr int GG = decltype(G_)::value;
-            AtomGroupN<GG> gp;                            // the group whose projected atoms are staged (none yet)
-            gp.n = 0;
-            for (int x = 0; x < GG; ++x) gp.j[x] = 0;
-            int gi = 0;
-            for (int t = 0; t < k; t += GG, ++gi) {
-                AtomGroupN<GG> g;
-                g.n = (k - t < GG) ? k - t : GG;
-                for (int x = 0; x < GG; ++x) {
-                    const int64_t j = h_order[t + (x < g.n ? x : 0)];
-                    if (j < 0 || j >= k) return MODL_EINVAL;
-                    g.j[x] = (int)j;
-                }
-#define MODL_GRAD(KPL)                                                                                                        \
-    hipLaunchKernelGGL((atom_grad_group_kernel<T, KPL, GG>), dim3(nwg), dim3(256), 0, stream, a.Dt, a.Bt, a.C, a.subset, s, k, g, \
-                       gp, stage[(gi + 1) & 1], a.comp_l1_ratio, num, dold, pold, ldr)
-                if (k <= 64) MODL_GRAD(1);
-                else if (k <= 128) MODL_GRAD(2);
-                else if (k <= 256) MODL_GRAD(4);
-                else MODL_GRAD(8);
-#undef MODL_GRAD
-                MODL_LAUNCH_CHECK();
-#define MODL_PROJ(EPT, L1)                                                                                                    \
-    hipLaunchKernelGGL((atom_project_group_kernel<T, EPT, GG, L1>), dim3(1), dim3(256), 0, stream, a.C, s, k, g, stage[gi & 1],   \
-                       a.comp_pos, a.comp_l1_ratio, num, dold, pold, nwg, a.comp_norm, a.level_hint, dbg)
-                if constexpr (GG == 8) {
-                    if (s <= 12 * 256) { if (l1) MODL_PROJ(12, true); else MODL_PROJ(12, false); }
-                    else { if (l1) MODL_PROJ(20, true); else MODL_PROJ(20, false); }
-                } else {
-                    if (l1) MODL_PROJ(kProjEpt, true); else MODL_PROJ(kProjEpt, false);
-                }
-#undef MODL_PROJ
-                MODL_LAUNCH_CHECK();
-                if (launches) *launches += 2;
-                gp = g;
-            }
-            hipLaunchKernelGGL((atom_stage_flush_group_kernel<T, GG>), dim3((unsigned)cdiv(s, 256)), dim3(256), 0, stream, a.Dt,
-                               a.subset, s, k, gp, stage[(gi + 1) & 1], ldr);
-            MODL_LAUNCH_CHECK();
-            if (launches) *launches += 1;
-            return MODL_OK;
-        };
-        return G == 8 ? run(std::integral_constant<int, 8>{}) : run(std::integral_constant<int, 4>{});
+    DuCtx<T> c{stream, a, static_cast<char *>(a.ws), L, R, 0};
+    int rc = MODL_EINVAL;
+    switch (R.family) {
+    case DU_WIDE: break;                                              // (taken above)
+    case DU_SGD: rc = du_sgd(c); break;
+    case DU_TINY: case DU_FEW: case DU_UNFUSED: rc = du_unfused(c); break;
+    case DU_BLOCK: rc = du_block(c); break;
+    case DU_PERSIST: rc = du_persist(c); break;
+    case DU_SWEEP: rc = du_sweep(c); break;
+    case DU_GROUPED: rc = R.G == 8 ? du_grouped<T, 8>(c) : du_grouped<T, 4>(c); break;
+    case DU_STAGED: rc = du_staged(c); break;
+    case DU_STEP: rc = du_step(c); break;
     }
-    // beyond the register-resident projection (24 elements per thread): groups of atoms, compact rows (atom_grad4_kernel)
-    const bool staged = u_lds != 0 && s > (int64_t)kProjEpt * 256;
-    if (staged) {
-        // groups of kStepGroup atoms (atom_step_group_kernel): one read of the dictionary per group; scratch in the a-tile's space
-        constexpr int G = kStepGroup;
-        static_assert(sizeof(T) * 3 * G + sizeof(double) * G <= sizeof(T) * kNB, "the group's rows fit the a-tile's space");
-        const int64_t ldr = s;
-        T *base = reinterpret_cast<T *>(ws + L.off_a);
-        T *stage[2] = {base, base + (size_t)G * ldr};
-        T *dold = base + (size_t)2 * G * ldr;
-        double *num = reinterpret_cast<double *>(ws + L.off_a + align_up(sizeof(T) * (size_t)3 * G * ldr, 16));
-        if (align_up(sizeof(T) * (size_t)3 * G * ldr, 16) + sizeof(double) * (size_t)G * ldr > sizeof(T) * (size_t)s * kNB) return MODL_ENOMEM;
-        if ((int64_t)G * nwg > L.nwg_grad) return MODL_ENOMEM;
-        const int nwg_corr = (int)cdiv(s, 256);                           // a thread per feature
-        // l1 atoms on at most 64 workgroups: the projection spread over the launch (mwg_l1_project); its two exchange buffers
-        // (sentinels) and the abort word live in the blocked path's record space, unused here
-        const bool mwg = a.comp_l1_ratio == 1.0 && nwg_corr <= kMwgMaxWg && g_atom_mwg.load(std::memory_order_relaxed) &&
-                         sizeof(double) * 2 * (size_t)L.nslab_max * (kNB * kNB + kNB) >= sizeof(double) * 2 * kMwgWords + 64;
-        double *xch = reinterpret_cast<double *>(ws + L.off_partial);
-        unsigned int *xabort = reinterpret_cast<unsigned int *>(xch + 2 * kMwgWords);
-        unsigned long launch_no = 0;
-        if (mwg) {
-            MODL_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(xch), (int)kMwgSentinel32, 2 * (size_t)kMwgWords * 2, stream));
-            MODL_HIP(hipMemsetAsync(xabort, 0, sizeof(unsigned int), stream));
-        }
-        AtomGroupN<G> g, gp;
-        gp.n = 0;
-        for (int b = 0; b < G; ++b) gp.j[b] = 0;
-        GradRide<T> no_ride{};
-        // ---- the pipelined sweep (round 6; atom_corr_project_kernel): the gradient launch of group g + 1 rides on the atom launches of
-        // group g.  Scratch of its own (DuLayout::off_pipe): two staged groups, THREE sets of old values
-        // (the riders write group g + 1's while the launches of group g still read group g - 1's), two sets of numerators and of
-        // old-norm partial sums.
-        const int ngroups = (int)cdiv(k, G);
-        static_assert(G == 4 && kPipeMinRows == (int64_t)kProjEpt * 256, "du_layout sizes off_pipe for groups of four");
-        // MODL_DEBUG_ATOM_MWG = 1 (default): the launch's LAST workgroup projects the vector from registers (atom_project_regs: 20.2 ms
-        // per minibatch at the HCP shape); 3: the projection spread over the launch's workgroups (mwg_l1_project: 27.0 ms)
-        const bool regs = a.comp_l1_ratio == 1.0 && g_atom_mwg.load(std::memory_order_relaxed) == 1 && s <= 64 * 256;
-        const bool pipelined = (mwg || regs) && ngroups >= 2 && g_atom_pipe.load(std::memory_order_relaxed) != 0 && s > kPipeMinRows &&
-                               (int64_t)2 * G * nwg <= L.nwg_grad;
-        if (pipelined) {
-            const int64_t ldr = pipe_row_stride(s);                       // (shadows the a-tile's stride: this scratch is its own)
-            // two elements per thread beyond 32 workgroups: half as many slots to poll and sum per exchange (C6: 26.8 against 27.3 ms)
-            const int ept = (nwg_corr > 32 && !regs) ? 2 : 1;
-            const int nwg_p = (int)cdiv(s, 256 * ept);
-            T *pb = reinterpret_cast<T *>(ws + L.off_pipe);
-            T *pstage[2] = {pb, pb + (size_t)G * ldr};
-            T *pdold[3] = {pb + (size_t)2 * G * ldr, pb + (size_t)3 * G * ldr, pb + (size_t)4 * G * ldr};
-            double *pnum0 = reinterpret_cast<double *>(ws + L.off_pipe + align_up(sizeof(T) * (size_t)5 * G * ldr, 16));
-            double *pnum[2] = {pnum0, pnum0 + (size_t)G * ldr};
-            double *ppold[2] = {pold, pold + (size_t)G * nwg};
-            auto group_of = [&](int gi_, AtomGroupN<G> &out) -> bool {
-                const int t0 = gi_ * G;
-                out.n = (k - t0 < G) ? k - t0 : G;
-                for (int b = 0; b < G; ++b) {
-                    out.j[b] = (int)h_order[t0 + (b < out.n ? b : 0)];
-                    if (out.j[b] < 0 || out.j[b] >= k) return false;
-                }
-                return true;
-            };
-            AtomGroupN<G> none;
-            none.n = 0;
-            for (int b = 0; b < G; ++b) none.j[b] = 0;
-            AtomGroupN<G> gcur, gnext, gprev = none;
-            if (!group_of(0, gcur)) return MODL_EINVAL;
-#define MODL_GRAD4(KPL)                                                                                               \
-    hipLaunchKernelGGL((atom_grad4_kernel<T, KPL>), dim3(nwg), dim3(256), 0, stream, a.Dt, a.Bt, a.C, a.subset, s, k, gcur, none,     \
-                       (const T *)pstage[1], a.comp_l1_ratio, pnum[0], pdold[0], ldr, ppold[0], nwg)
-            if (k <= 64) MODL_GRAD4(1);
-            else if (k <= 128) MODL_GRAD4(2);
-            else if (k <= 256) MODL_GRAD4(4);
-            else if (k <= 512) MODL_GRAD4(8);
-            else MODL_GRAD4(16);
-#undef MODL_GRAD4
-            MODL_LAUNCH_CHECK();
-            for (int gi = 0; gi < ngroups; ++gi) {
-                const bool has_next = gi + 1 < ngroups;
-                if (has_next && !group_of(gi + 1, gnext)) return MODL_EINVAL;
-                for (int ai = 0; ai < gcur.n; ++ai) {
-                    GradRide<T> ride{};
-                    int nride = 0;
-                    if (has_next) {                                       // (then this group is a full one: G launches, a part each)
-                        const int lo = (int)((int64_t)ai * nwg / G), hi = (int)((int64_t)(ai + 1) * nwg / G);
-                        nride = hi - lo;
-                        ride.Bt = a.Bt; ride.gn = gnext; ride.gfold = gprev; ride.stage_fold = pstage[(gi + 1) & 1];
-                        ride.num = pnum[(gi + 1) & 1]; ride.dold = pdold[(gi + 1) % 3]; ride.pold = ppold[(gi + 1) & 1];
-                        ride.part_stride = nwg; ride.vb0 = lo; ride.nvb = nwg; ride.nride = nride;
-                    }
-                    ride.ept = ept;
-                    ride.regs = regs ? 1 : 0;
-                    const int grid = nwg_p + nride;
-#define MODL_CORR(KPL)                                                                                                            \
-    hipLaunchKernelGGL((atom_corr_project_kernel<T, KPL>), dim3(grid), dim3(256), u_lds, stream, a.Dt, a.C, a.subset, s, k,       \
-                       gcur, ai, a.comp_pos, a.comp_l1_ratio, u, (const double *)pnum[gi & 1], (const T *)pdold[gi % 3], pstage[gi & 1], ldr,  \
-                       (const double *)ppold[gi & 1], nwg, a.comp_norm, counter,                                                                \
-                       reinterpret_cast<unsigned long long *>(counter + kCounters), a.level_hint, regs ? nullptr : xch, xabort,                \
-                       (int)(launch_no++ & 1) | (g_atom_mwg.load(std::memory_order_relaxed) == 2 ? 2 : 0), nwg_p, gprev,                       \
-                       (const T *)pstage[(gi + 1) & 1], (const T *)pdold[(gi + 2) % 3], ride)
-                    if (k <= 64) MODL_CORR(1);
-                    else if (k <= 128) MODL_CORR(2);
-                    else if (k <= 256) MODL_CORR(4);
-                    else if (k <= 512) MODL_CORR(8);
-                    else MODL_CORR(16);
-#undef MODL_CORR
-                    MODL_LAUNCH_CHECK();
-                }
-                if (has_next) { gprev = gcur; gcur = gnext; }
-            }
-            // home: the last two groups (the riders of a group's launches put the group BEFORE it home; the last group has none)
-            int nflush = 0;
-            for (int gi = ngroups - 2; gi < ngroups; ++gi) {
-                const AtomGroupN<G> &gf = (gi == ngroups - 1) ? gcur : gprev;
-                for (int b = 0; b < gf.n; ++b, ++nflush) {
-                    hipLaunchKernelGGL((atom_stage_flush_kernel<T>), dim3((unsigned)cdiv(s, 256)), dim3(256), 0, stream, a.Dt, a.subset, s, k,
-                                       gf.j[b], (const T *)(pstage[gi & 1] + (size_t)b * ldr));
-                    MODL_LAUNCH_CHECK();
-                }
-            }
-            if (launches) *launches += k + 1 + nflush;
-            return MODL_OK;
-        }
-        int gi = 0;
-        for (int t0 = 0; t0 < k; t0 += G, ++gi) {
-            g.n = (k - t0 < G) ? k - t0 : G;
-            for (int b = 0; b < G; ++b) {
-                g.j[b] = (int)h_order[t0 + (b < g.n ? b : 0)];
-                if (g.j[b] < 0 || g.j[b] >= k) return MODL_EINVAL;
-            }
-#define MODL_GRAD4(KPL)                                                                                               \
-    hipLaunchKernelGGL((atom_grad4_kernel<T, KPL>), dim3(nwg), dim3(256), 0, stream, a.Dt, a.Bt, a.C, a.subset, s, k, g, gp,          \
-                       (const T *)stage[(gi + 1) & 1], a.comp_l1_ratio, num, dold, ldr, pold, nwg)
-            if (k <= 64) MODL_GRAD4(1);
-            else if (k <= 128) MODL_GRAD4(2);
-            else if (k <= 256) MODL_GRAD4(4);
-            else if (k <= 512) MODL_GRAD4(8);
-            else MODL_GRAD4(16);
-#undef MODL_GRAD4
-            MODL_LAUNCH_CHECK();
-            for (int ai = 0; ai < g.n; ++ai) {
-                hipLaunchKernelGGL((atom_corr_project_kernel<T, 0>), dim3(nwg_corr), dim3(256), u_lds, stream, a.Dt, a.C, a.subset, s, k,
-                                   g, ai, a.comp_pos, a.comp_l1_ratio, u, (const double *)num, (const T *)dold, stage[gi & 1], ldr,
-                                   (const double *)pold, nwg, a.comp_norm, counter,
-                                   reinterpret_cast<unsigned long long *>(counter + kCounters), a.level_hint,
-                                   mwg ? xch : nullptr, xabort,
-                                   (int)(launch_no++ & 1) | (g_atom_mwg.load(std::memory_order_relaxed) == 2 ? 2 : 0), nwg_corr, gp,
-                                   (const T *)nullptr, (const T *)nullptr, no_ride);
-                MODL_LAUNCH_CHECK();
-            }
-            gp = g;
-        }
-        for (int b = 0; b < gp.n; ++b) {                                 // the last group's rows
-            hipLaunchKernelGGL((atom_stage_flush_kernel<T>), dim3((unsigned)cdiv(s, 256)), dim3(256), 0, stream, a.Dt, a.subset, s, k,
-                               gp.j[b], (const T *)(stage[(gi + 1) & 1] + (size_t)b * ldr));
-            MODL_LAUNCH_CHECK();
-        }
-        if (launches) *launches += k + gi + gp.n;
-        return MODL_OK;
-    }
-    for (int t = 0; t < k; ++t) {
-        const int j = (int)h_order[t];
-        if (j < 0 || j >= k) return MODL_EINVAL;
-#define MODL_STEP(KPL)                                                                                            \
-    hipLaunchKernelGGL((atom_step_kernel<T, KPL>), dim3(nwg), dim3(256), u_lds, stream, a.Dt, a.Bt, a.C, a.subset, s, k, j, \
-                       a.comp_pos, a.comp_l1_ratio, u, pold, a.comp_norm, counter, u_lds ? 1 : 0, \
-                       reinterpret_cast<unsigned long long *>(counter + kCounters), a.level_hint)
-        if (k <= 64) MODL_STEP(1);
-        else if (k <= 128) MODL_STEP(2);
-        else if (k <= 256) MODL_STEP(4);
-        else if (k <= 512) MODL_STEP(8);
-        else MODL_STEP(16);
-#undef MODL_STEP
-        MODL_LAUNCH_CHECK();
-    }
-    if (launches) *launches += k;
-    return MODL_OK;
+    if (rc == MODL_OK && launches) *launches += c.nl;
+    return rc;
 }
 
 template int dict_update<float>(hipStream_t, const DictUpdateArgs<float> &, int *);
 template int dict_update<double>(hipStream_t, const DictUpdateArgs<double> &, int *);
 
 }  // namespace modl
+

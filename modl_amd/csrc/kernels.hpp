@@ -238,6 +238,42 @@ struct DictUpdateArgs {
     double *level_hint = nullptr;  // optional [k], PERSISTENT across calls (zero-initialised): the soft-threshold level
                                    // each atom's l1 / elastic-net projection ended with, warm start of the next one
 };
+// Which kernels take a dictionary update and the parameters their launches need: decided by du_route (bcd.hip) and nowhere
+// else; dict_update switches on the family.
+enum DuFamily {                   // (the families that walk h_order last: dict_update tells them apart by that)
+    DU_SGD,       // du_sgd: col_norm_* + product + sgd_project_kernel
+    DU_WIDE,      // dict_update_wide: k > 1024
+    DU_TINY,      // du_unfused: bcd_prepare_kernel + bcd_tiny_kernel
+    DU_FEW,       // du_unfused: bcd_prepare_kernel + bcd_few_kernel
+    DU_UNFUSED,   // du_unfused: bcd_prepare_kernel, then apply / product / bcd_gram_kernel / bcd_resolve_kernel per block
+    DU_BLOCK,     // du_block: bcd_setup_kernel, then bcd_block_kernel<RT, GPW> per block
+    DU_PERSIST,   // du_persist: bcd_setup_kernel + the persistent launch (bcd_persist.hip)
+    DU_SWEEP,     // du_sweep: atom_sweep_kernel
+    DU_GROUPED,   // du_grouped: atom_grad_group_kernel<KPL, G> + atom_project_group_kernel<EPT, G, L1> per group
+    DU_STAGED,    // du_staged: atom_grad4_kernel<KPL> per group + atom_corr_project_kernel per atom
+    DU_STEP,      // du_step: atom_step_kernel<KPL> per atom
+};
+struct DuRoute {
+    DuFamily family = DU_STEP;
+    // block, persist: 32 RT sampled rows per workgroup, GPW contraction groups per worker wave, nslab workgroups, the
+    // accumulator's shards, acc: bcd_block_kernel sums into the fixed-point accumulator (the persistent launch always does).
+    // sgd, unfused: nslab slabs of kGramRows rows.  tiny, few, unfused: nfew = workgroups of bcd_few_kernel
+    int RT = 1, GPW = 8, nslab = 0, shards = 1, nfew = 0;
+    bool acc = false;
+    // the per-atom families: KPL atoms per lane of the gradient kernels, groups of G atoms, EPT elements per thread of the
+    // grouped projection, l1: comp_l1_ratio == 1
+    int KPL = 1, G = 0, EPT = 0;
+    bool l1 = false;
+    // staged: the pipelined sweep or a gradient launch per group; spread: the exchange buffers of mwg_l1_project are armed
+    // (not pipelined: it projects); pipelined: regs = 40 / 64 elements per thread of atom_project_regs, or 0: the spread
+    // projection with ept elements per thread
+    bool pipelined = false, spread = false;
+    int regs = 0, ept = 1;
+    bool lds = false;             // staged, step: the vector's copy in LDS (step: else in global memory)
+};
+// the route of a direct call as the string tests/test_dict_update_routes.py: expected_route spells (modl_dict_update_route)
+int dict_update_route(int dtype, int k, int64_t s, int optimizer, int comp_pos, double comp_l1_ratio, int ncu, char *buf,
+                      size_t cap);
 size_t dict_update_workspace(int dtype, int64_t s_max, int k);
 size_t dict_update_stamps_offset(int dtype, int64_t s_max, int k);
 size_t dict_update_persist_stamps_offset(int dtype, int64_t s_max, int k);

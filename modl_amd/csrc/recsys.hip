@@ -948,6 +948,10 @@ ABI_RECSYS(f64, double)
 #undef ABI_RECSYS
 
 size_t modl_dict_update_workspace(int dtype, int64_t s_max, int k) { return dict_update_workspace(dtype, s_max, k); }
+int modl_dict_update_route(int dtype, int k, int64_t s, int optimizer, int comp_pos, double comp_l1_ratio, int ncu, char *buf,
+                           size_t cap) {
+    return dict_update_route(dtype, k, s, optimizer, comp_pos, comp_l1_ratio, ncu, buf, cap);
+}
 
 int modl_recsys_plan_create(int dtype, int64_t p, int k, int64_t max_batch, int64_t max_entries, modl_recsys_plan **out) {
     if (!out || (dtype != MODL_F32 && dtype != MODL_F64) || p <= 0 || k <= 0 || max_batch <= 0 || max_entries < 0)

@@ -1,4 +1,4 @@
-"""The dictionary update (csrc/bcd.hip: dict_update, dict_update_generic) route by route, through modl_dict_update_f32 /
+"""The dictionary update (csrc/bcd.hip: du_route, dict_update) route by route, through modl_dict_update_f32 /
 _f64, against the CPU oracle's update_dict on inputs built to leave the projection's main branch.
 
 Three layers:
@@ -13,7 +13,8 @@ Three layers:
    routes mixes projected and copied atoms, and so that the budgets left (comp_norm) are not all at rounding level.
 2. CPU tests: the scenes are what they claim (`test_cases_are_what_they_claim`), the matrix of layer 3 holds every route
    and both neighbours of every numeric boundary of the dispatch (`test_route_table`, against `expected_route`, a
-   restatement of the dispatch conditions), and the acceptance rules of layer 3 reject six kinds of wrong result
+   restatement of the dispatch conditions, which is in turn held against the library's own answer, modl_dict_update_route,
+   on 256 and on 128 compute units: `library_route`), and the acceptance rules of layer 3 reject six kinds of wrong result
    (`test_acceptance_rule_rejects_mutants`); every l2 route and boundary neighbour has a case in which the oracle both clips
    and copies (`test_l2_cases_clip_and_copy`).
 3. GPU tests (`test_route`): CASES, about 200 direct calls.  f64: rel_fro < 1e-9 and comp_norm to rtol 1e-9 / atol 1e-12
@@ -34,11 +35,13 @@ plateaus, and asserts what it reaches: 15 passes in f64, 12 for f32-representabl
 `heavy` itself.  The cap is out of reach and the give-up branch of mwg_l1_project cannot be entered through the product
 library.  The constant was not lowered to make one.
 
-`expected_route` restates csrc/bcd.hip as of this commit: dict_update lines 2732-3048 (sgd :2743, the blocked l2 path
-:2764-3042 with the persistent launch :2792-2805 / :2936-2971, bcd_few_kernel :2830-2852, bcd_tiny_kernel :2853-2862) and
-dict_update_generic lines 3060-3326 (atom_sweep_kernel :3079-3087, the grouped update :3096-3150, the staged sweeps
-:3152-3308 with the pipelined one :3188-3271, atom_step_kernel :3309-3325); bcd_persist_fits is csrc/bcd_persist.hip
-:1086-1112.  The same table is in DESIGN.md, section 10 "Dictionary-update route matrix".
+`expected_route` restates du_route of csrc/bcd.hip, the one function that decides the route (a DuRoute of csrc/kernels.hpp:
+the family DU_SGD, DU_WIDE, DU_TINY, DU_FEW, DU_UNFUSED, DU_BLOCK, DU_PERSIST, DU_SWEEP, DU_GROUPED, DU_STAGED or DU_STEP
+and the launch parameters RT, GPW, acc, shards, nfew, EPT, G, KPL, l1, pipelined, regs, spread, ept, lds); dict_update
+switches on the family to du_sgd, dict_update_wide, du_unfused (tiny, few and unfused: they share their first launch),
+du_block, du_persist, du_sweep, du_grouped, du_staged (pipelined or not) and du_step.  The residency of the persistent
+launch is bcd_persist_fits of csrc/bcd_persist.hip.  The strings are the ones du_route_name writes for
+modl_dict_update_route.  The same table is in DESIGN.md, section 10 "Dictionary-update route matrix".
 """
 import os
 import zlib
@@ -76,7 +79,7 @@ def _cdiv(a, b):
 
 # ---------------------------------------------------------------------------------------------------- the dispatch, restated
 def expected_route(dt, k, s, update, switches=None, ncu=256):
-    """The route csrc/bcd.hip takes (see the module docstring for the lines restated), as 'family/variant/...'."""
+    """The route csrc/bcd.hip takes (du_route, see the module docstring), as 'family/variant/...'."""
     sw = switch_defaults()
     sw.update(switches or {})
     tsz = 4 if dt == 'f32' else 8
@@ -126,6 +129,19 @@ def expected_route(dt, k, s, update, switches=None, ncu=256):
         # (not pipelined: KPL is atom_grad4_kernel's; the atoms run atom_corr_project_kernel<T, 0>)
         return 'staged/grad4KPL%d/%s' % (kpl, 'spread' if mwg else ('lds_l1' if l1 else 'lds_enet'))
     return 'step/KPL%d/%s' % (kpl, 'lds' if tsz * s <= 60 * 1024 else 'global')
+
+
+def library_route(dt, k, s, update, ncu):
+    """modl_dict_update_route: the route the library's own du_route gives a direct call under the switches set now.
+    ncu > 0: on that many compute units, no device involved; 0: on the current device."""
+    import ctypes as C
+    from modl_amd import _lib
+    u = UPDATES[update]
+    buf = C.create_string_buffer(64)
+    _lib.check(_lib.lib.modl_dict_update_route(_lib.MODL_F32 if dt == 'f32' else _lib.MODL_F64, k, s, 1 if u.get('optimizer') == 'sgd' else 0,
+                                               int(u.get('comp_pos', False)), u.get('comp_l1_ratio', 0.0), ncu, buf, len(buf)),
+               'modl_dict_update_route')
+    return buf.value.decode()
 
 
 # ---------------------------------------------------------------------------------------------------- layer 1: the case builder
@@ -762,8 +778,50 @@ BOUNDARIES = [
 ]
 
 
-def test_route_table():
-    """The matrix holds every route and both neighbours of every boundary (on the 256 compute units of an MI355X)."""
+FAMILIES = ('tiny', 'few', 'unfused', 'persist', 'block', 'sweep', 'grouped', 'staged_pipe', 'staged', 'step', 'sgd', 'wide')
+
+
+def hold_restatement_to_library(put, ncu):
+    """expected_route == modl_dict_update_route on ncu compute units (the built library, no device): every case of the matrix
+    under its switches, both neighbours of every boundary, every combination of SWITCH_VALUES at one shape per family.
+    put: the debug_switches fixture.  Returns the number of comparisons."""
+    import itertools
+    count = [0]
+
+    def same(dt, k, s, update, sw):
+        full = switch_defaults()
+        full.update(sw)
+        put(full)
+        want, got = expected_route(dt, k, s, update, sw, ncu), library_route(dt, k, s, update, ncu)
+        assert got == want, 'the library takes %s, the restatement says %s: %s' % (got, want, (dt, k, s, update, sw, ncu))
+        count[0] += 1
+        return got
+
+    for c in CASES:
+        same(c.dt, c.k, c.s, c.update, c.sw)
+    for what, shared, lo, hi in BOUNDARIES:
+        for field, value, prefix in (lo, hi):
+            want = dict(shared)
+            want[field] = value
+            hits = [c for c in CASES if all(getattr(c, f) == v for f, v in want.items())]
+            got = [same(c.dt, c.k, c.s, c.update, c.sw) for c in hits]
+            assert hits and (ncu != 256 or any(r.startswith(prefix) for r in got)), (what, want, prefix, got)
+    shapes = {}
+    for dt, k, s, update in [(c.dt, c.k, c.s, c.update) for c in CASES] + [('f64', 1100, 1000, 'l1')]:
+        shapes.setdefault(expected_route(dt, k, s, update, dict(BCD_ACC=1), ncu).split('/')[0], (dt, k, s, update))
+    assert set(shapes) == set(FAMILIES), sorted(shapes)
+    names = sorted(SWITCH_VALUES)
+    for values in itertools.product(*(SWITCH_VALUES[n] for n in names)):
+        for shape in shapes.values():
+            same(*shape, dict(zip(names, values)))
+    return count[0]
+
+
+def test_route_table(debug_switches):
+    """The matrix holds every route and both neighbours of every boundary (on the 256 compute units of an MI355X), and the
+    library's du_route takes the routes this module says it takes."""
+    ncmp = hold_restatement_to_library(debug_switches, 256)
+    assert ncmp >= len(CASES) + 2 * len(BOUNDARIES) + 96 * len(FAMILIES), ncmp
     routes = [case_route(c, 256) for c in CASES]
     missing = [r for r in ROUTES_REQUIRED if r not in routes and r != 'wide']
     assert not missing, missing
@@ -812,7 +870,40 @@ def test_route_table():
             assert v in SWITCH_VALUES[name]
     assert len(set(case_id(c) for c in CASES)) == len(CASES) and 150 <= len(CASES) <= 250, len(CASES)
     assert sum(1 for c in CASES if c.k * c.k * c.s >= 512 * 512 * 8000) <= 12
-    print('%d cases, %d routes' % (len(CASES), len(set(routes))))
+    print('%d cases, %d routes, %d comparisons with the library' % (len(CASES), len(set(routes)), ncmp))
+
+
+def test_route_table_on_128_compute_units(debug_switches):
+    """The same comparison where the boundaries that depend on the device move: RT 2 | 3 of bcd_block_kernel at s = 64 ncu
+    and 96 ncu, the persistent launch at 32 (ncu - 1) sampled rows (RT 1) and 64 (ncu - 1) (RT 2).  Then what the probe
+    refuses."""
+    import ctypes as C
+    from modl_amd import _lib
+    ncu = 128
+    hold_restatement_to_library(debug_switches, ncu)
+    on = dict(BCD_ACC=1, BCD_PERSIST=1)
+    moved = {32 * (ncu - 1): 'persist/RT1', 32 * (ncu - 1) + 1: 'persist/RT2', 64 * (ncu - 1): 'persist/RT2',
+             64 * (ncu - 1) + 1: 'block/RT2/GPW8/acc1/shards4', 64 * ncu: 'block/RT2/GPW8/acc1/shards4',
+             64 * ncu + 1: 'block/RT3/GPW8/acc1/shards4', 96 * ncu: 'block/RT3/GPW8/acc1/shards4',
+             96 * ncu + 1: 'block/RT2/GPW8/acc1/shards4'}
+    for s, route in moved.items():
+        for k in (64, 260):                              # (kp > 256: RT 1 only, in one launch or per block)
+            for sw in (on, dict(on, BCD_PERSIST=0), dict(on, BCD_ACC=0)):
+                debug_switches(dict(switch_defaults(), **sw))
+                got = library_route('f32', k, s, 'l2', ncu)
+                assert got == expected_route('f32', k, s, 'l2', sw, ncu), (k, s, sw, got)
+                if k == 64 and sw is on:
+                    assert got == route, (s, got, route)
+    assert all(expected_route('f32', 64, s, 'l2', on, 256) != moved[s] for s in (32 * (ncu - 1) + 1, 64 * (ncu - 1) + 1, 64 * ncu + 1))
+    buf = C.create_string_buffer(64)
+    probe = _lib.lib.modl_dict_update_route
+    debug_switches(dict(switch_defaults(), **on))
+    assert probe(_lib.MODL_F32, 64, 1000, 0, 0, 0.0, ncu, buf, 64) == 0 and buf.value == b'persist/RT1'
+    assert probe(_lib.MODL_F32, 64, 1000, 0, 0, 0.0, ncu, buf, len('persist/RT1')) == -1          # no room for the terminator
+    for bad in ((2, 64, 1000, 0, 0, 0.0, ncu, buf, 64), (_lib.MODL_F32, 0, 1000, 0, 0, 0.0, ncu, buf, 64),
+                (_lib.MODL_F32, 4097, 1000, 0, 0, 0.0, ncu, buf, 64), (_lib.MODL_F32, 64, 0, 0, 0, 0.0, ncu, buf, 64),
+                (_lib.MODL_F32, 64, 1000, 0, 0, 0.0, -1, buf, 64), (_lib.MODL_F32, 64, 1000, 0, 0, 0.0, ncu, None, 64)):
+        assert probe(*bad) == -1, bad
 
 
 def clipped_and_copied(case, cn64):
@@ -1000,6 +1091,8 @@ def test_route(gpu, debug_switches, c):
     if c.dt == 'f32':
         refs['f32'] = reference(case, np.float32)
     debug_switches(c.sw)
+    took = library_route(c.dt, c.k, c.s, c.update, 0)
+    assert took == case_route(c), 'the test id names %s, on this device the library takes %s' % (case_route(c), took)
     Dt, cn = run_gpu(case)
     try:
         _judge(c, case, Dt, cn, refs)

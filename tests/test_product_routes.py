@@ -54,7 +54,7 @@ B = bcd.hip.
                          half the scratch each, the Gram symmetric; else one launch_gemm_dense each
   S:701     ride         a proper subset, Dx_agg != full, no MODL_FLAG_NO_RIDER, ceil(p / 64) < 1024: C_ and the sampled rows
                          of B_ (EpiStatsRows) now, the others under the dictionary update
-  B:2889-2921 rider      f32 and k <= 512: wide tiles 32 x 128 when p >= 2048 and plan_wide ok, else the 32 x 32 tiles of
+  B:plan_ride rider      f32 and k <= 512: wide tiles 32 x 128 when p >= 2048 and plan_wide ok, else the 32 x 32 tiles of
                          plan_stats, shared out over the carrier launches; otherwise completed after the update (S:929-937)
                          through stats_pair with EpiStatsSkip
 The launches of the code-product and statistics sections (modl_somf_prof_get: code_gemm, stats_gemm) are asserted against the
@@ -413,12 +413,12 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
         _leaf('no rider: p of 65472 or more')
     if ride:
         r, l = stats_pair(dt, k, s, s_pad, 0, b, ws, 'rows', resident=resident)
-        fused = dt == 'f32' and k <= 512                                     # B:2774
+        fused = dt == 'f32' and k <= 512                                     # B:du_route
         unal_c, unal_x = misaligned(dt, k), misaligned(dt, ldx, xbase)
-        if fused and p >= 2048 and plan_wide_ok(p, k, b, ldx, k, xbase):     # B:2901
+        if fused and p >= 2048 and plan_wide_ok(p, k, b, ldx, k, xbase):     # B:plan_ride
             _leaf('rider: wide128')
             rider = 'wide128'
-        elif fused and plan_stats_ok(dt, unal_x, unal_c, p, k, b):           # B:2896, 2903
+        elif fused and plan_stats_ok(dt, unal_x, unal_c, p, k, b):           # B:plan_ride
             _leaf('rider: stats32 unal') if unal_x or unal_c else _leaf('rider: stats32 al')
             rider = 'stats32/' + ('unal' if unal_x or unal_c else 'al')
         else:                                                                # S:929-937
