@@ -986,6 +986,49 @@ int modl_label_components(const uint8_t *d_mask, int64_t n0, int64_t n1, int64_t
 int modl_largest_component(const uint8_t *d_mask, int64_t n0, int64_t n1, int64_t n2, uint8_t *d_out, int64_t *d_info, void *d_ws,
                            size_t ws_bytes, void *stream);
 
+/* Connected regions of many maps at once (csrc/regions.hip): the device half of nilearn's
+ * connected_regions / RegionExtractor.  d_rows holds M maps as rows of V elements (leading dimension ldr >= V), one element
+ * per voxel of a mask; d_col (int32[n0][n1][n2], n2 fastest: the `col` of modl_smooth_mask) is the column of a box voxel or
+ * -1 (an entry outside 0 .. V-1 reads as -1; the CALLER sees to it that the columns 0 .. V-1 appear once each).
+ * modl_region_labels: an element v is foreground iff it is finite, v != 0 and |v| >= cutoff (compared in the dtype).  The
+ * foreground of every map is split into its 6-connected components in the box (scipy.ndimage.label, default structure;
+ * maps never interact, columns that are neighbours in the row but not in the box are not connected); a component of n voxels
+ * is kept iff n > min_voxels; the kept ones are numbered 1, 2, .. within their map in scipy's order, by the component's
+ * first voxel in the C order of the caller's (X, Y, Z) = (n2, n1, n0) array, index (i2 n1 + i1) n0 + i0.
+ *   d_labels (int32, M rows of V, ldl >= V)   0, or the number of the element's region within its map;
+ *   d_counts (int32[M])                        the regions of every map;
+ *   d_sizes (int32[M][size_cap], may be NULL with size_cap = 0)   d_sizes[m][j] = the voxels of region j + 1 of map m for
+ *                                              j < min(d_counts[m], size_cap); the other entries are not written.
+ *                                              size_cap = V / (max(min_voxels, 0) + 1) holds every region.
+ * The chunk of M maps is labelled by one set of launches with the map on a grid axis: the predicate is evaluated from
+ * d_rows[m][d_col[g]] inside the tile kernel (no volume is unmasked, no byte mask written), then the union-find of
+ * modl_label_components (tiles in LDS, merge across faces, flatten), sizes and first voxels with one integer add and one
+ * integer min per wavefront and distinct root, and the numbering by a prefix sum over flags at the first voxels.  All
+ * atomics are integer min / add: the same input gives the same bits.  d_rows and d_col are not written.
+ * d_ws: modl_region_labels_workspace(M, n0, n1, n2) bytes, 16 M n0 n1 n2 and a little (0 for bad arguments);
+ * modl_region_max_maps: the largest M <= 65535 whose workspace fits budget_bytes (0: not even one map, or a bad box).
+ * modl_region_gather: d_regions (R rows of V, ldo >= V) from the labels of M maps and d_offsets (int64[M + 1], device,
+ * ascending, d_offsets[0] = 0, d_offsets[M] = R: the first region row of every map): row d_offsets[m] + j holds d_rows[m][c]
+ * where d_labels[m][c] == j + 1, bit for bit, and 0 elsewhere.  One grid row per region, 16 bytes of neighbouring columns
+ * per thread, no atomics, no workspace.  R == 0 does nothing.
+ * All calls are asynchronous on `stream`.  MODL_EINVAL before any device work: a NULL pointer, M < 1 or M > 65535 (labels),
+ * V < 1, V above the box, a leading dimension below V, an extent < 1, a box above INT32_MAX elements or n0 above 65535
+ * tiles, a cutoff that is negative or NaN, size_cap < 0, R < 0, a pointer that is not aligned to an element (gather), any
+ * overlap of an output with an input, another output or the workspace.  d_ws NULL or short: MODL_ENOMEM; no device:
+ * MODL_ENOGPU. */
+size_t modl_region_labels_workspace(int64_t M, int64_t n0, int64_t n1, int64_t n2);
+int64_t modl_region_max_maps(int64_t n0, int64_t n1, int64_t n2, size_t budget_bytes);
+int modl_region_labels_f32(const float *d_rows, int64_t ldr, int64_t M, int64_t V, const int32_t *d_col, int64_t n0, int64_t n1,
+                           int64_t n2, float cutoff, int64_t min_voxels, int32_t *d_labels, int64_t ldl, int32_t *d_counts,
+                           int32_t *d_sizes, int64_t size_cap, void *d_ws, size_t ws_bytes, void *stream);
+int modl_region_labels_f64(const double *d_rows, int64_t ldr, int64_t M, int64_t V, const int32_t *d_col, int64_t n0, int64_t n1,
+                           int64_t n2, double cutoff, int64_t min_voxels, int32_t *d_labels, int64_t ldl, int32_t *d_counts,
+                           int32_t *d_sizes, int64_t size_cap, void *d_ws, size_t ws_bytes, void *stream);
+int modl_region_gather_f32(const float *d_rows, int64_t ldr, int64_t M, int64_t V, const int32_t *d_labels, int64_t ldl,
+                           const int64_t *d_offsets, int64_t R, float *d_regions, int64_t ldo, void *stream);
+int modl_region_gather_f64(const double *d_rows, int64_t ldr, int64_t M, int64_t V, const int32_t *d_labels, int64_t ldl,
+                           const int64_t *d_offsets, int64_t R, double *d_regions, int64_t ldo, void *stream);
+
 /* Resampling of a volume onto another grid (csrc/resample.hip; the masker's first step: nilearn's
  * resample_img, i.e. per frame scipy.ndimage.affine_transform(frame, A, offset=b, output_shape, order, mode='constant',
  * cval=fill)).  d_vol as for modl_smooth_mask: T frames of a box [n0][n1][n2], n2 fastest, frame_stride >= n0 n1 n2.

@@ -9,9 +9,11 @@ from .masker import ArrayMasker, smooth_mask, unmask, gaussian_weights  # noqa: 
 from .masker import resample, resample_mask, resample_host, voxel_size_of  # noqa: F401
 from .masker import (compute_epi_mask, compute_background_mask, compute_multi_epi_mask,  # noqa: F401
                      compute_multi_background_mask, intersect_masks, largest_connected_component)
+from .regions import Regions, connected_regions, region_labels, connected_regions_host, region_labels_host  # noqa: F401
 
 __all__ = ['DictFact', 'Coder', 'SparseCodes', 'amari_discrepency', 'mean_amari_discrepency', 'grid_origins', 'grid_patches',
            'reconstruct_from_patches', 'clean', 'cleaning_basis', 'butterworth', 'ArrayMasker', 'smooth_mask', 'unmask',
            'gaussian_weights', 'resample', 'resample_mask', 'resample_host', 'voxel_size_of', 'compute_epi_mask',
            'compute_background_mask', 'compute_multi_epi_mask', 'compute_multi_background_mask', 'intersect_masks',
-           'largest_connected_component']
+           'largest_connected_component', 'Regions', 'connected_regions', 'region_labels', 'connected_regions_host',
+           'region_labels_host']

@@ -192,6 +192,11 @@ def bind(lib):
         _sig('modl_resample_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, C.c_int, C.c_double, _i64, _i64,
              _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _sz, _vp)
         _sig('modl_frame_mean_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp)
+        _sig('modl_region_labels_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _ct, _i64, _vp, _i64, _vp, _vp,
+             _i64, _vp, _sz, _vp)
+        _sig('modl_region_gather_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp)
+    _sig('modl_region_labels_workspace', _sz, _i64, _i64, _i64, _i64)
+    _sig('modl_region_max_maps', _i64, _i64, _i64, _i64, _sz)
     _sig('modl_morph_workspace', _sz, _i64, _i64, _i64, _i64)
     _sig('modl_binary_morph', C.c_int, _vp, _i64, _i64, _i64, _i64, C.c_int, _vp, _vp, _sz, _vp)
     _sig('modl_label_tile', C.c_int, _vp)

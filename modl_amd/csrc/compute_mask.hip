@@ -12,26 +12,13 @@
 //                          write is an atomicMin; no workgroup waits for another;
 //   3. label_flatten_kernel root[g] = the root of g's chain = the smallest g of the component, -1 for a false voxel.
 // The kernel boundaries are the phase boundaries.  The representative depends on the mask alone.
-#include <climits>
 #include <cmath>
 
-#include "common.hpp"
+#include "label_uf.hpp"
 
 namespace modl {
 
-constexpr int kLT0 = 8, kLT1 = 8, kLT2 = 8;                 // the tile of phase 1 along n0, n1, n2
-constexpr int kMaxTilesPerAxis = 65535;                     // grid.y / grid.z
-constexpr int kLabelThreads = 512;                          // one thread per voxel of a tile
 constexpr size_t kLabelScalars = 256;                       // bytes: {largest size, components, winner's first user index}
-
-static inline bool mask_box_ok(int64_t n0, int64_t n1, int64_t n2) {
-    return n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= INT32_MAX / n1 && n0 * n1 <= INT32_MAX / n2;
-}
-
-static inline bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
 
 // ------------------------------------------------------------------------------------------------------ the mean
 template <typename T> __device__ __forceinline__ T finite_or_zero(T v) { return std::fabs(v) < (T)__builtin_inf() ? v : (T)0; }
@@ -120,46 +107,6 @@ static inline int64_t morph_launches(int64_t n0, int64_t n1, int64_t n2, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------------ labelling
-template <int SCOPE> __device__ __forceinline__ int uf_load(int *P, int x) {
-    return __hip_atomic_load(P + x, __ATOMIC_RELAXED, SCOPE);
-}
-
-// the root of x with path halving; every store is an atomic min of an ancestor, so parent[x] <= x holds throughout and x
-// descends strictly: at most `limit` (the number of elements) steps
-template <int SCOPE> __device__ __forceinline__ int uf_find(int *P, int x, int limit) {
-    for (int it = 0; it < limit; ++it) {
-        const int p = uf_load<SCOPE>(P, x);
-        if (p == x) return x;
-        const int gp = uf_load<SCOPE>(P, p);
-        if (gp == p) return p;
-        __hip_atomic_fetch_min(P + x, gp, __ATOMIC_RELAXED, SCOPE);
-        x = gp;
-    }
-    return x;
-}
-
-// unite the sets of a and b: the larger root is linked under the smaller by an atomic min; when the min displaces another
-// link the loop goes on with the displaced value, so no union is lost.  One of a, b descends every round.
-template <int SCOPE> __device__ __forceinline__ void uf_union(int *P, int a, int b, int limit) {
-    for (int64_t it = 0; it < 2 * (int64_t)limit; ++it) {
-        a = uf_find<SCOPE>(P, a, limit);
-        b = uf_find<SCOPE>(P, b, limit);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = __hip_atomic_fetch_min(P + a, b, __ATOMIC_RELAXED, SCOPE);      // a > b
-        if (old == a) return;
-        a = old;
-    }
-}
-
-struct LabelGeom {
-    int n[3];
-};
-
 // phase 1.  cnt / scal (may be NULL): the counters of modl_largest_component, reset here.
 __global__ __launch_bounds__(kLabelThreads) void label_tile_kernel(const uint8_t *__restrict__ mask, LabelGeom g,
                                                                    int *__restrict__ parent, int *__restrict__ cnt,
@@ -172,23 +119,14 @@ __global__ __launch_bounds__(kLabelThreads) void label_tile_kernel(const uint8_t
     const bool inside = i0 < g.n[0] && i1 < g.n[1] && i2 < g.n[2];
     const int64_t gi = ((int64_t)i0 * g.n[1] + i1) * g.n[2] + i2;
     const bool on = inside && mask[gi] != 0;
-    L[l] = on ? l : -1;
     if (scal && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && l < 3) scal[l] = l == 2 ? INT_MAX : 0;
-    __syncthreads();
-    constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP;
-    if (on) {
-        if (c > 0 && uf_load<WG>(L, l - 1) >= 0) uf_union<WG>(L, l, l - 1, T0 * T1 * T2);
-        if (b > 0 && uf_load<WG>(L, l - T2) >= 0) uf_union<WG>(L, l, l - T2, T0 * T1 * T2);
-        if (a > 0 && uf_load<WG>(L, l - T2 * T1) >= 0) uf_union<WG>(L, l, l - T2 * T1, T0 * T1 * T2);
-    }
-    __syncthreads();
+    const int r = uf_label_tile(L, l, on);
     if (!inside) return;
     if (cnt) cnt[gi] = 0;
     if (!on) {
         parent[gi] = -1;
         return;
     }
-    const int r = uf_find<WG>(L, l, T0 * T1 * T2);
     const int rc = r % T2, rb = (r / T2) % T1, ra = r / (T2 * T1);
     parent[gi] = (int)(((int64_t)(blockIdx.z * T0 + ra) * g.n[1] + (blockIdx.y * T1 + rb)) * g.n[2] + (blockIdx.x * T2 + rc));
 }
@@ -200,10 +138,8 @@ __global__ __launch_bounds__(256) void label_merge_kernel(const uint8_t *__restr
     if (gi >= box || mask[gi] == 0) return;
     const int i2 = (int)(gi % g.n[2]), i1 = (int)((gi / g.n[2]) % g.n[1]), i0 = (int)(gi / ((int64_t)g.n[2] * g.n[1]));
     const int s1 = g.n[2], s0 = g.n[1] * g.n[2];
-    constexpr int AG = __HIP_MEMORY_SCOPE_AGENT;
-    if (i2 > 0 && i2 % kLT2 == 0 && mask[gi - 1]) uf_union<AG>(parent, (int)gi, (int)gi - 1, box);
-    if (i1 > 0 && i1 % kLT1 == 0 && mask[gi - s1]) uf_union<AG>(parent, (int)gi, (int)gi - s1, box);
-    if (i0 > 0 && i0 % kLT0 == 0 && mask[gi - s0]) uf_union<AG>(parent, (int)gi, (int)gi - s0, box);
+    uf_merge_faces(parent, (int)gi, g, i2 > 0 && i2 % kLT2 == 0 && mask[gi - 1], i1 > 0 && i1 % kLT1 == 0 && mask[gi - s1],
+                   i0 > 0 && i0 % kLT0 == 0 && mask[gi - s0]);
 }
 
 // phase 3: the chains are walked (and halved on the way, for the threads that follow) and the root is written apart
@@ -212,17 +148,6 @@ __global__ __launch_bounds__(256) void label_flatten_kernel(int *parent, int box
     if (gi >= box) return;
     constexpr int AG = __HIP_MEMORY_SCOPE_AGENT;
     root[gi] = uf_load<AG>(parent, (int)gi) < 0 ? -1 : uf_find<AG>(parent, (int)gi, box);
-}
-
-__device__ __forceinline__ int wave_min_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int wave_max_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
 }
 
 // sizes: one add per wavefront and distinct root (a ballot loop over the roots present in the wavefront, at most 64 rounds)

@@ -43,6 +43,7 @@ from sklearn.utils import check_random_state
 from .device import gather_rows
 from .dict_fact import DictFact, Coder
 from .masker import ArrayMasker, unmask, compute_strategy_mask, _check_strategy
+from .regions import connected_regions
 from .signal import clean, clean_host, cleaning_basis, _destination_rows
 
 METHODS = {'masked': {'G_agg': 'masked', 'Dx_agg': 'masked'},           # fmri.py:440-445
@@ -245,6 +246,27 @@ class _RecordStager:
             self.pool.shutdown(wait=True)
 
 
+def _extract_regions(est, min_region_size, threshold, thresholding_strategy):
+    """`extract_regions` of both estimators: the connected regions of `components_` under the fitted masker's mask, with its
+    voxel volume (the affine's when the masker has one)"""
+    if not hasattr(est, 'components_'):
+        raise ValueError('%s is not fitted: call fit() first' % type(est).__name__)
+    masker = getattr(est, 'masker_', None)
+    if masker is None:
+        raise ValueError('extract_regions needs the mask of the volume: this estimator was fitted without `mask` (2-D records), '
+                         'so its maps have no box to be connected in; pass `mask` to the estimator, or call '
+                         'modl_amd.regions.connected_regions(est.components_, mask)')
+    grid = dict(voxel_size=masker.voxel_size_) if masker.mask_affine_ is None else dict(mask_affine=masker.mask_affine_)
+    found = connected_regions(est.components_, masker.maps_, min_region_size=min_region_size, threshold=threshold,
+                              thresholding_strategy=thresholding_strategy, **grid)
+    est.regions_, est.regions_index_ = found.regions, found.index
+    if found.regions.shape[0]:
+        est.regions_img_ = unmask(found.regions, masker.maps_)
+    else:
+        est.regions_img_ = np.zeros(masker.maps_.mask.shape + (0,), dtype=found.regions.dtype)
+    return found
+
+
 class fMRIDictFact(BaseEstimator):
     """Constructor arguments follow fmri.py:273-291 (masking arguments dropped).
 
@@ -441,6 +463,14 @@ class fMRIDictFact(BaseEstimator):
         lens = np.array([a.shape[0] for a in arrays])
         return np.sum(scores * lens) / np.sum(lens)
 
+    def extract_regions(self, min_region_size=1350, threshold=None, thresholding_strategy=None):
+        """The connected regions of the learned maps (nilearn's RegionExtractor with extractor='connected_components';
+        modl_amd.regions.connected_regions) under the fitted masker's mask and voxel volume: returns
+        Regions(regions (R, V), index (R,), sizes (R,)) and sets `regions_`, `regions_index_` and `regions_img_`
+        ((X, Y, Z, R), through `unmask`).  `fMRICoder(dictionary=est.regions_, mask=est.mask_)` then gives region signals.
+        ValueError: an estimator fitted without `mask`."""
+        return _extract_regions(self, min_region_size, threshold, thresholding_strategy)
+
 
 def _cleaned_records(coder, records, confounds, detrend, standardize, low_pass=None, high_pass=None, t_r=None,
                      masker=None, affines=None):
@@ -506,6 +536,14 @@ class fMRICoder(BaseEstimator):
         if masker is not None:
             self.components_img_ = unmask(self.components_, masker.maps_)
         return self
+
+    def extract_regions(self, min_region_size=1350, threshold=None, thresholding_strategy=None):
+        """The connected regions of the maps (nilearn's RegionExtractor with extractor='connected_components';
+        modl_amd.regions.connected_regions) under the fitted masker's mask and voxel volume: returns
+        Regions(regions (R, V), index (R,), sizes (R,)) and sets `regions_`, `regions_index_` and `regions_img_`
+        ((X, Y, Z, R), through `unmask`).
+        ValueError: an estimator fitted without `mask`."""
+        return _extract_regions(self, min_region_size, threshold, thresholding_strategy)
 
     def _records(self, records):
         if isinstance(records, str) or (isinstance(records, np.ndarray) and records.ndim in (2, 4)):
