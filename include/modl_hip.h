@@ -1099,6 +1099,25 @@ int modl_amari_f32(const float *const *h_d_dicts, const int64_t *h_k, int n, int
 int modl_amari_f64(const double *const *h_d_dicts, const int64_t *h_k, int n, int64_t p, double *d_pair, double *d_rowmax,
                    double *d_colmax, void *d_ws, size_t ws_bytes, void *stream, int *launches);
 
+/* One sweep of symmetric FastICA for many restarts at once (csrc/ica.hip), all in f64.
+ * d_X1: k rows of V whitened values, ldx >= V.  d_W: unmixing matrices, each k x k row-major, one after the other; d_active:
+ * R int32 indices of the matrices to sweep (device; every entry indexes a matrix that d_W holds, and no entry repeats).
+ * For each listed restart r, with y = W_r x per voxel:
+ *   d_M[r]  (k x k) = (1 / V) sum_v g(y_v) x_v^T,        d_gp[r] (k) = (1 / V) sum_v g'(y_{i, v});
+ * the slots of d_M and d_gp of restarts that are not listed are not written.  fun: 0 cube (g = y^3, g' = 3 y^2), 1 logcosh
+ * (g = tanh(alpha y), g' = alpha (1 - g^2)), 2 exp (g = y exp(-y^2 / 2), g' = (1 - y^2) exp(-y^2 / 2)); alpha is read by
+ * logcosh alone.  The k x V sources stay in registers between the two matrix-core products; the sums are per-workgroup
+ * partials in d_ws added in a fixed order, no floating-point atomics: the same input gives the same bits, and the voxel
+ * chunking depends on V alone, so a restart's outputs are the same bits whichever other restarts are listed with it.  Nothing is read
+ * beyond column V of a row.  Asynchronous on `stream`.  MODL_EINVAL before any device work: a NULL pointer (d_ws apart), k < 1
+ * or k > modl_ica_max_components() = 128, V < 1, R < 1 or R > 65535, ldx < V, an unknown fun, a pointer that is not aligned
+ * to its element.  d_ws NULL or ws_bytes below modl_ica_sweep_workspace(V, k, R) (0 for bad arguments): MODL_ENOMEM; no
+ * device: MODL_ENOGPU. */
+int modl_ica_max_components(void);
+size_t modl_ica_sweep_workspace(int64_t V, int k, int R);
+int modl_ica_sweep_f64(const double *d_X1, int64_t ldx, int64_t V, int k, const double *d_W, const int32_t *d_active, int R, int fun,
+                       double alpha, double *d_M, double *d_gp, void *d_ws, size_t ws_bytes, void *stream);
+
 /* layout helpers: out[c][r] = in[r][c]  (components_ <-> Dt) */
 int modl_transpose_f32(const float *d_in, float *d_out, int64_t rows, int64_t cols, void *stream);
 int modl_transpose_f64(const double *d_in, double *d_out, int64_t rows, int64_t cols, void *stream);

@@ -10,10 +10,13 @@ from .masker import resample, resample_mask, resample_host, voxel_size_of  # noq
 from .masker import (compute_epi_mask, compute_background_mask, compute_multi_epi_mask,  # noqa: F401
                      compute_multi_background_mask, intersect_masks, largest_connected_component)
 from .regions import Regions, connected_regions, region_labels, connected_regions_host, region_labels_host  # noqa: F401
+from .canica import (IcaMaps, Canica, reduce_record, group_components, fastica_maps, threshold_maps, canica,  # noqa: F401
+                     reduce_record_host, group_components_host, fastica_maps_host, threshold_maps_host, canica_host)
 
 __all__ = ['DictFact', 'Coder', 'SparseCodes', 'amari_discrepency', 'mean_amari_discrepency', 'grid_origins', 'grid_patches',
            'reconstruct_from_patches', 'clean', 'cleaning_basis', 'butterworth', 'ArrayMasker', 'smooth_mask', 'unmask',
            'gaussian_weights', 'resample', 'resample_mask', 'resample_host', 'voxel_size_of', 'compute_epi_mask',
            'compute_background_mask', 'compute_multi_epi_mask', 'compute_multi_background_mask', 'intersect_masks',
            'largest_connected_component', 'Regions', 'connected_regions', 'region_labels', 'connected_regions_host',
-           'region_labels_host']
+           'region_labels_host', 'IcaMaps', 'Canica', 'reduce_record', 'group_components', 'fastica_maps', 'threshold_maps',
+           'canica', 'reduce_record_host', 'group_components_host', 'fastica_maps_host', 'threshold_maps_host', 'canica_host']

@@ -197,6 +197,9 @@ def bind(lib):
         _sig('modl_region_gather_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp)
     _sig('modl_region_labels_workspace', _sz, _i64, _i64, _i64, _i64)
     _sig('modl_region_max_maps', _i64, _i64, _i64, _i64, _sz)
+    _sig('modl_ica_max_components', C.c_int)
+    _sig('modl_ica_sweep_workspace', _sz, _i64, C.c_int, C.c_int)
+    _sig('modl_ica_sweep_f64', C.c_int, _vp, _i64, _i64, C.c_int, _vp, _vp, C.c_int, C.c_int, _f64, _vp, _vp, _vp, _sz, _vp)
     _sig('modl_morph_workspace', _sz, _i64, _i64, _i64, _i64)
     _sig('modl_binary_morph', C.c_int, _vp, _i64, _i64, _i64, _i64, C.c_int, _vp, _vp, _sz, _vp)
     _sig('modl_label_tile', C.c_int, _vp)
