@@ -1118,6 +1118,49 @@ size_t modl_ica_sweep_workspace(int64_t V, int k, int R);
 int modl_ica_sweep_f64(const double *d_X1, int64_t ldx, int64_t V, int k, const double *d_W, const int32_t *d_active, int R, int fun,
                        double alpha, double *d_M, double *d_gp, void *d_ws, size_t ws_bytes, void *stream);
 
+/* Functional connectivity (csrc/connectivity.hip).
+ *
+ * modl_conn_covariance_*: the covariance matrices of S records of R region signals in one call.  d_X: the records stacked,
+ * h_offsets[S] rows of R values, ldx >= R; record s is rows h_offsets[s] .. h_offsets[s + 1] - 1 (T_s of them).  h_offsets is
+ * HOST memory (S + 1 int64): it is checked here and copied into the workspace, which is what the kernels read.  Per record,
+ * all in f64 (f32 is converted on load: an f32 record and its f64 copy give the same bits), with Xc = X - column means (formed
+ * first, in a fixed order; the centred values enter the product, there is no raw-moment correction), E = Xc^T Xc / T, p = R:
+ *   estimator 0 (empirical):   cov = E, shrinkage 0;
+ *   estimator 1 (Ledoit-Wolf): mu = trace(E) / p, delta_ = sum_ij (Xc^T Xc)_ij^2 / T^2, beta_ = sum_t (sum_i Xc_ti^2)^2,
+ *                              beta = min((beta_ / T - delta_) / (p T), delta), delta = (delta_ - 2 mu trace(E) + p mu^2) / p,
+ *                              shrinkage = beta == 0 ? 0 : beta / delta, cov = (1 - shrinkage) E + shrinkage mu I
+ *                              (sklearn.covariance.LedoitWolf; R = 1: shrinkage 0, as sklearn answers);
+ *   output 0: d_cov[s] (R x R row-major, one after the other) = cov; output 1: cov_ij / sqrt(cov_ii cov_jj), diagonal exactly 1.
+ * d_shrinkage: S doubles.  The product runs on v_mfma_f64_16x16x4_f64, one workgroup per record and 64 x 64 block of the upper
+ * triangle over the whole T of the record; the lower triangle is mirrored, so the output is exactly symmetric.  Partial sums
+ * are added in a fixed order, no floating-point atomics: the same input gives the same bits, and a record's bits do not depend
+ * on which other records are in the call nor on their order.  Nothing is read beyond column R of a row.  Asynchronous on
+ * `stream` once the offsets have been handed to the copy.  MODL_EINVAL before any device work: a NULL pointer (d_ws apart),
+ * R < 1 or R > modl_conn_max_regions() = 512 (8 x 8 blocks of 64; the finishing kernel keeps a record's diagonal in LDS),
+ * S < 1 or S > 65535, h_offsets[0] < 0, offsets not increasing by at least 2 (a record needs two time points), ldx < R, an
+ * unknown estimator or output, a pointer that is not aligned to its element.  d_ws NULL or ws_bytes below
+ * modl_conn_covariance_workspace(S, R) (0 for bad arguments): MODL_ENOMEM; no device: MODL_ENOGPU.
+ *
+ * modl_conn_seed_maps_*: the seed-to-voxel correlation maps of one record.  d_X: T rows of V values, ldx >= V; d_seeds: T rows
+ * of R PREPARED seeds, contiguous (every column centred and of unit 2-norm, in the record's dtype); d_out: R rows of V, ldo >= V:
+ *   d_out[r][v] = clip((sum_t seeds[t][r] X[t][v]) / sqrt(ss_v), -1, 1),   ss_v = sum_t x_tv^2 - (sum_t x_tv)^2 / T,
+ * both sums of ss_v in f64, accumulated while X is staged for the product; a voxel with ss_v <= 8 T 2^-53 sum_t x_tv^2 (constant
+ * to rounding) gives an exact 0.  The product runs on the matrix cores in the record's dtype (f32: exact FMA chains, t
+ * ascending), one workgroup per 64 voxels over the whole T, no K split: deterministic by construction.  For R <= 128 X is read
+ * once; beyond, the workgroup's block of X is re-read (from the caches) once per further 128 seeds.  Nothing is read or written
+ * beyond column V of a row.  MODL_EINVAL: a NULL pointer, R < 1 or R > modl_conn_max_regions(), T < 2, V < 1, ldx < V, ldo < V,
+ * a pointer that is not aligned to its element; no device: MODL_ENOGPU. */
+int modl_conn_max_regions(void);
+size_t modl_conn_covariance_workspace(int S, int R);
+int modl_conn_covariance_f32(const float *d_X, int64_t ldx, const int64_t *h_offsets, int S, int R, int estimator, int output,
+                             double *d_cov, double *d_shrinkage, void *d_ws, size_t ws_bytes, void *stream);
+int modl_conn_covariance_f64(const double *d_X, int64_t ldx, const int64_t *h_offsets, int S, int R, int estimator, int output,
+                             double *d_cov, double *d_shrinkage, void *d_ws, size_t ws_bytes, void *stream);
+int modl_conn_seed_maps_f32(const float *d_X, int64_t ldx, int64_t T, int64_t V, const float *d_seeds, int R, float *d_out, int64_t ldo,
+                            void *stream);
+int modl_conn_seed_maps_f64(const double *d_X, int64_t ldx, int64_t T, int64_t V, const double *d_seeds, int R, double *d_out, int64_t ldo,
+                            void *stream);
+
 /* layout helpers: out[c][r] = in[r][c]  (components_ <-> Dt) */
 int modl_transpose_f32(const float *d_in, float *d_out, int64_t rows, int64_t cols, void *stream);
 int modl_transpose_f64(const double *d_in, double *d_out, int64_t rows, int64_t cols, void *stream);

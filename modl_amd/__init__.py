@@ -12,6 +12,9 @@ from .masker import (compute_epi_mask, compute_background_mask, compute_multi_ep
 from .regions import Regions, connected_regions, region_labels, connected_regions_host, region_labels_host  # noqa: F401
 from .canica import (IcaMaps, Canica, reduce_record, group_components, fastica_maps, threshold_maps, canica,  # noqa: F401
                      reduce_record_host, group_components_host, fastica_maps_host, threshold_maps_host, canica_host)
+from .connectivity import (covariances, ConnectivityMeasure, geometric_mean, sym_matrix_to_vec, vec_to_sym_matrix,  # noqa: F401
+                           seed_correlation, covariances_host, ConnectivityMeasureHost, geometric_mean_host,
+                           seed_correlation_host)
 
 __all__ = ['DictFact', 'Coder', 'SparseCodes', 'amari_discrepency', 'mean_amari_discrepency', 'grid_origins', 'grid_patches',
            'reconstruct_from_patches', 'clean', 'cleaning_basis', 'butterworth', 'ArrayMasker', 'smooth_mask', 'unmask',
@@ -19,4 +22,6 @@ __all__ = ['DictFact', 'Coder', 'SparseCodes', 'amari_discrepency', 'mean_amari_
            'compute_background_mask', 'compute_multi_epi_mask', 'compute_multi_background_mask', 'intersect_masks',
            'largest_connected_component', 'Regions', 'connected_regions', 'region_labels', 'connected_regions_host',
            'region_labels_host', 'IcaMaps', 'Canica', 'reduce_record', 'group_components', 'fastica_maps', 'threshold_maps',
-           'canica', 'reduce_record_host', 'group_components_host', 'fastica_maps_host', 'threshold_maps_host', 'canica_host']
+           'canica', 'reduce_record_host', 'group_components_host', 'fastica_maps_host', 'threshold_maps_host', 'canica_host',
+           'covariances', 'ConnectivityMeasure', 'geometric_mean', 'sym_matrix_to_vec', 'vec_to_sym_matrix', 'seed_correlation',
+           'covariances_host', 'ConnectivityMeasureHost', 'geometric_mean_host', 'seed_correlation_host']

@@ -45,6 +45,7 @@ from .dict_fact import DictFact, Coder
 from .masker import ArrayMasker, unmask, compute_strategy_mask, _check_strategy
 from .regions import connected_regions
 from .canica import Canica, IcaMaps, reduce_record, group_components, fastica_maps, threshold_maps, _check_ratio, _check_ica_scalars
+from .connectivity import seed_correlation
 from .signal import clean, clean_host, cleaning_basis, _destination_rows
 
 METHODS = {'masked': {'G_agg': 'masked', 'Dx_agg': 'masked'},           # fmri.py:440-445
@@ -651,6 +652,31 @@ class fMRICoder(BaseEstimator):
             step = self.transform_batch_size or X.shape[0] or 1
             parts = [self.coder_.transform(X[a:a + step]) for a in range(0, X.shape[0], step)]
             out.append(np.concatenate(parts) if parts else np.zeros((0, self.components_.shape[0]), dtype=X.dtype))
+        return out
+
+    def seed_correlation(self, records, confounds=None, affines=None):
+        """The seed-to-voxel correlation maps of each record with its own loadings: every record is masked and cleaned
+        exactly as `transform` does and stays staged on the device, is coded, and the Pearson correlation over time of every
+        component's loading with every voxel is formed by one fused pass over the staged record
+        (modl_amd.connectivity.seed_correlation).  Returns one (n_components, n_voxels) array per
+        record; with a fitted mask `seed_maps_img_` holds the last record's maps as a volume (X, Y, Z, n_components).
+        ValueError: a component whose loading is constant over a record."""
+        if not hasattr(self, 'coder_'):
+            raise ValueError('fMRICoder is not fitted: call fit() first')
+        out = []
+        records = self._records(records)
+        be = self.coder_._backend
+        on_gpu = getattr(be, 'device', None) is not None and be.device.type == 'cuda'
+        for rec, conf, aff in zip(records, self._confounds(confounds, records), _check_affines(affines, records)):
+            X = self._rows(rec, conf, aff)
+            if on_gpu:
+                X = _staged_2d(X, be)
+            step = self.transform_batch_size or X.shape[0] or 1
+            codes = np.concatenate([self.coder_.transform(X[a:a + step]) for a in range(0, X.shape[0], step)])
+            maps = seed_correlation(X, codes)
+            out.append(maps.cpu().numpy() if isinstance(maps, torch.Tensor) else maps)
+        if self.masker_ is not None and out:
+            self.seed_maps_img_ = unmask(out[-1], self.masker_.maps_)
         return out
 
     def score(self, records, confounds=None, affines=None):
