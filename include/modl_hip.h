@@ -120,7 +120,8 @@ int modl_rk_shuffle_i64(modl_rk *rk, int64_t *h_x, int64_t n);        /* random_
 /* random_fast.pyx:127: draws one swap sequence; h_trace[n] receives the
  * permutation, h_swaps[n] the swap targets to replay on other arrays. */
 int modl_rk_shuffle_trace(modl_rk *rk, int64_t n, int64_t *h_trace, int64_t *h_swaps);
-/* replays a swap sequence on the rows of a host array (random_fast.pyx:105-119) */
+/* replays a swap sequence on the rows of a host array (random_fast.pyx:105-119); a target outside 0..i is refused with
+ * MODL_EINVAL before any row moves (the device version too, which also wants row_bytes % 4 == 0) */
 int modl_apply_swaps_rows(void *h_base, int64_t n, size_t row_bytes, const int64_t *h_swaps);
 /* same on a DEVICE array (epoch shuffle of code_ / averages, dict_fact.py:359-379) */
 int modl_apply_swaps_rows_device(void *d_base, int64_t n, size_t row_bytes, const int64_t *h_swaps,
@@ -186,7 +187,10 @@ int modl_update_G_average_f64(double *d_G_average, const double *d_G, const doub
 /* enet_norm / enet_projection / enet_scale, modl/utils/math/enet.pyx:125,38,150,
  * batched over `rows` vectors of length n laid out with element stride `inc`
  * and vector stride `ld` (so atoms can be rows of D or columns of Dt).
- * d_radius[rows] (projection, scale), d_out_norm[rows] (norm). */
+ * d_radius[rows] (projection; scale takes one radius for every row), d_out_norm[rows] (norm).
+ * inc < 1 is refused with MODL_EINVAL.  The projection's d_out may be d_v.  A row whose enet norm is not finite (a
+ * NaN or an infinity among its entries) comes out NaN throughout from the projection and the scale, and as that norm
+ * (NaN or +inf) from the norm; no other row is touched. */
 int modl_enet_norm_f32(const float *d_v, int64_t rows, int64_t n, int64_t ld, int64_t inc, float l1_ratio,
                        float *d_out_norm, void *stream);
 int modl_enet_norm_f64(const double *d_v, int64_t rows, int64_t n, int64_t ld, int64_t inc, double l1_ratio,
@@ -1161,7 +1165,8 @@ int modl_conn_seed_maps_f32(const float *d_X, int64_t ldx, int64_t T, int64_t V,
 int modl_conn_seed_maps_f64(const double *d_X, int64_t ldx, int64_t T, int64_t V, const double *d_seeds, int R, double *d_out, int64_t ldo,
                             void *stream);
 
-/* layout helpers: out[c][r] = in[r][c]  (components_ <-> Dt) */
+/* layout helpers: out[c][r] = in[r][c]  (components_ <-> Dt).  ceil(rows / 32) is the grid's y extent: more than
+ * 32 * 65536 rows (65536: the y limit the MI355X reports) are refused with MODL_EINVAL before any launch. */
 int modl_transpose_f32(const float *d_in, float *d_out, int64_t rows, int64_t cols, void *stream);
 int modl_transpose_f64(const double *d_in, double *d_out, int64_t rows, int64_t cols, void *stream);
 

@@ -22,8 +22,19 @@ template <typename T>
 __global__ __launch_bounds__(256) void enet_projection_kernel(const T *v, T *out, int64_t n, int64_t ld, int64_t inc,
                                                               const T *radius, T l1_ratio) {
     __shared__ double red[4];
-    block_enet_project<T>(v + (int64_t)blockIdx.x * ld, inc, out + (int64_t)blockIdx.x * ld, inc, n,
-                          (double)radius[blockIdx.x], (double)l1_ratio, red);
+    const T *x = v + (int64_t)blockIdx.x * ld;
+    T *o = out + (int64_t)blockIdx.x * ld;
+    // A row whose enet norm is not finite (a NaN or an infinity among its entries) comes out NaN throughout, as a poisoned
+    // row does everywhere else in the library: block_enet_project alone would drop a NaN entry (`a > level` is false for
+    // it, `pos > 0 ? pos : 0` makes it 0) and project the rest.  One more scan of a cold entry point; the sum is complete
+    // before the first store, so `out` may still be `v`.
+    const double nrm = block_enet_norm<T>(x, inc, n, (double)l1_ratio, red);
+    if (!isfinite(nrm)) {
+        const T nan = (T)__builtin_nan("");
+        for (int64_t i = threadIdx.x; i < n; i += 256) o[i * inc] = nan;
+        return;
+    }
+    block_enet_project<T>(x, inc, o, inc, n, (double)radius[blockIdx.x], (double)l1_ratio, red);
 }
 
 template <typename T>
@@ -98,6 +109,9 @@ int launch_update_G_average(hipStream_t stream, T *G_average, const int64_t *idx
 }
 
 // out[c][r] = in[r][c] through a padded LDS tile (both sides coalesced)
+// ceil(rows / 32) is the grid's y extent: at most kMaxGridY, what the MI355X reports for that axis (maxGridSize[1])
+constexpr int64_t kMaxGridY = 65536;
+constexpr int64_t kTransposeMaxRows = 32 * kMaxGridY;
 template <typename T>
 __global__ __launch_bounds__(256) void transpose_kernel(const T *in, T *out, int64_t rows, int64_t cols) {
     __shared__ T tile[32][33];
@@ -163,17 +177,17 @@ extern "C" {
 #define ABI_ENET(SFX, T)                                                                                          \
     int modl_enet_norm_##SFX(const T *d_v, int64_t rows, int64_t n, int64_t ld, int64_t inc, T l1_ratio,          \
                              T *d_out_norm, void *stream) {                                                      \
-        if (!d_v || !d_out_norm || rows < 0 || n < 0) return MODL_EINVAL;                                         \
+        if (!d_v || !d_out_norm || rows < 0 || n < 0 || inc < 1) return MODL_EINVAL;                              \
         return launch_enet_norm<T>((hipStream_t)stream, d_v, rows, n, ld, inc, l1_ratio, d_out_norm);             \
     }                                                                                                             \
     int modl_enet_projection_##SFX(const T *d_v, T *d_out, int64_t rows, int64_t n, int64_t ld, int64_t inc,      \
                                    const T *d_radius, T l1_ratio, void *stream) {                                \
-        if (!d_v || !d_out || !d_radius || rows < 0 || n < 0) return MODL_EINVAL;                                 \
+        if (!d_v || !d_out || !d_radius || rows < 0 || n < 0 || inc < 1) return MODL_EINVAL;                      \
         return launch_enet_projection<T>((hipStream_t)stream, d_v, d_out, rows, n, ld, inc, d_radius, l1_ratio); \
     }                                                                                                             \
     int modl_enet_scale_##SFX(T *d_v, int64_t rows, int64_t n, int64_t ld, int64_t inc, T l1_ratio, T radius,     \
                               void *stream) {                                                                    \
-        if (!d_v || rows < 0 || n < 0) return MODL_EINVAL;                                                        \
+        if (!d_v || rows < 0 || n < 0 || inc < 1) return MODL_EINVAL;                                             \
         return launch_enet_scale<T>((hipStream_t)stream, d_v, rows, n, ld, inc, l1_ratio, radius);                \
     }                                                                                                             \
     int modl_update_G_average_##SFX(T *d_G_average, const T *d_G, const T *d_w_sample, int64_t b, int64_t k,      \
@@ -182,7 +196,7 @@ extern "C" {
         return launch_update_G_average<T>((hipStream_t)stream, d_G_average, nullptr, d_G, d_w_sample, b, k);      \
     }                                                                                                             \
     int modl_transpose_##SFX(const T *d_in, T *d_out, int64_t rows, int64_t cols, void *stream) {                 \
-        if (!d_in || !d_out || rows < 0 || cols < 0) return MODL_EINVAL;                                          \
+        if (!d_in || !d_out || rows < 0 || cols < 0 || rows > kTransposeMaxRows) return MODL_EINVAL;              \
         return launch_transpose<T>((hipStream_t)stream, d_in, d_out, rows, cols);                                 \
     }
 ABI_ENET(f32, float)

@@ -408,12 +408,13 @@ int modl_rk_shuffle_trace(modl_rk *rk, int64_t n, int64_t *h_trace, int64_t *h_s
 }
 int modl_apply_swaps_rows(void *h_base, int64_t n, size_t row_bytes, const int64_t *h_swaps) {
     if (n < 0 || (n > 1 && (!h_base || !h_swaps))) return MODL_EINVAL;
+    for (int64_t i = n - 1; i > 0; --i)                      // refused before the first row moves
+        if (h_swaps[i] < 0 || h_swaps[i] > i) return MODL_EINVAL;
     if (row_bytes == 0) return MODL_OK;
     std::vector<char> tmp(row_bytes);
     char *b = static_cast<char *>(h_base);
     for (int64_t i = n - 1; i > 0; --i) {
         const int64_t j = h_swaps[i];
-        if (j < 0 || j > i) return MODL_EINVAL;
         if (j == i) continue;
         std::memcpy(tmp.data(), b + i * row_bytes, row_bytes);
         std::memcpy(b + i * row_bytes, b + j * row_bytes, row_bytes);

@@ -169,6 +169,39 @@ def test_new_entry_points_validate_arguments_without_gpu(lib):
         assert lib.modl_recsys_plan_create(1, 10, 4, 2, 8, C.byref(h)) == -4                # MODL_ENOGPU
 
 
+def test_helper_entry_points_refuse_before_any_launch(lib):
+    """modl_enet_* refuse an element stride below 1, modl_transpose_* a row count whose tiles do not fit the grid's y axis
+    (65536 on the MI355X: 32 * 65536 rows), the swap replays a target outside 0..i - all in the argument check, so a host
+    pointer is never read and nothing moves; no GPU involved"""
+    x = np.arange(12, dtype=np.float64)
+    keep = x.copy()
+    px = x.ctypes.data_as(C.c_void_p)
+    for sfx, ct in (('f32', C.c_float), ('f64', C.c_double)):
+        for inc in (0, -1, -(1 << 40)):
+            assert getattr(lib, 'modl_enet_norm_' + sfx)(px, 2, 3, 3, inc, ct(0.5), px, None) == -1
+            assert getattr(lib, 'modl_enet_projection_' + sfx)(px, px, 2, 3, 3, inc, px, ct(0.5), None) == -1
+            assert getattr(lib, 'modl_enet_scale_' + sfx)(px, 2, 3, 3, inc, ct(0.5), ct(1.0), None) == -1
+        assert getattr(lib, 'modl_enet_norm_' + sfx)(px, -1, 3, 3, 1, ct(0.5), px, None) == -1
+        assert getattr(lib, 'modl_enet_norm_' + sfx)(px, 0, 3, 3, 1, ct(0.5), px, None) == 0          # no row: nothing to launch
+        tr = getattr(lib, 'modl_transpose_' + sfx)
+        assert tr(px, px, 32 * 65536 + 1, 1, None) == -1
+        assert tr(px, px, 1 << 40, 3, None) == -1
+        assert tr(px, px, -1, 3, None) == -1 and tr(None, px, 3, 3, None) == -1
+        assert tr(px, px, 0, 3, None) == 0 and tr(px, px, 32 * 65536, 0, None) == 0                  # empty: nothing to launch
+    assert_array_equal(x, keep)
+    rows = np.arange(21, dtype=np.int32).reshape(7, 3)
+    for i, j in ((3, 4), (6, 7), (1, -1), (6, -1)):
+        swaps = np.arange(7, dtype=np.int64)
+        swaps[6], swaps[i] = 0, j                                                                     # a valid swap first, then the bad one
+        got = rows.copy()
+        assert lib.modl_apply_swaps_rows(got.ctypes.data_as(C.c_void_p), 7, 12, swaps.ctypes.data_as(C.c_void_p)) == -1
+        assert_array_equal(got, rows)
+        assert lib.modl_apply_swaps_rows_device(got.ctypes.data_as(C.c_void_p), 7, 12, swaps.ctypes.data_as(C.c_void_p), None) == -1
+        assert_array_equal(got, rows)
+    assert lib.modl_apply_swaps_rows_device(rows.ctypes.data_as(C.c_void_p), 7, 6, np.arange(7, dtype=np.int64).ctypes.data_as(C.c_void_p),
+                                            None) == -1                                              # rows that are no whole words
+
+
 def test_rk_continues_numpy_legacy_stream():
     """modl_rk_set_mt_state / get_mt_state: a modl_rk loaded with numpy's legacy MT19937 state draws numpy's
     RandomState.permutation(k) bit for bit (legacy shuffle == randomkit's masked-rejection shuffle) and hands back a
