@@ -537,6 +537,27 @@ int modl_gather_rows_f32(const float *d_src, int64_t src_ld, const int64_t *d_id
 int modl_gather_rows_f64(const double *d_src, int64_t src_ld, const int64_t *d_idx, int64_t n_rows, int64_t cols,
                          double *d_dst, int64_t dst_ld, void *stream);
 
+/* Which matrix-core launches the library would run for a section of the work on a plan of this descriptor, under the current
+ * MODL_DEBUG_STATS_RESIDENT switch and desc->flags, written to buf[cap] as "kernel/alignment/tiles/..." ("dense/al/t2x2/edge/
+ * s7/kps160/last40/pipe/sym0", "prep+pair/Dx[...]/G[...]", "stats32/al/t7x2/ride:wide128", "resident16/scalar/ride:after[...]",
+ * ".../partialG[gather/small/...]": csrc/step_products.hip; the grammar is spelled out in tests/test_product_routes.py).
+ * Read-only: nothing is launched, no device memory is written, no plan is needed and no device is touched, so this works
+ * without a GPU.  section: MODL_ROUTE_TRANSFORM - Dx of ONE chunk of b rows of modl_somf_transform; MODL_ROUTE_FULL_GRAM -
+ * modl_somf_full_gram; MODL_ROUTE_CODE_PRODUCTS - Dx and G in front of the code solve of a step, with the Gram pass of the
+ * dictionary update for G_agg = full; MODL_ROUTE_STATS - the C_ and B_ statistics behind it, and how the rows of B_ that were
+ * not sampled are updated.  b, s, has_subset, has_idx, ldx: as the minibatch (or chunk) carries them; x_offset: where X
+ * starts, in elements from a 16-byte aligned address.  Every other buffer (Dt, code_, what the library allocates) is taken
+ * as 16-byte aligned.  MODL_EINVAL for a bad descriptor, section, b, s or ldx, or a buffer too small:
+ * MODL_PRODUCT_ROUTE_MAX bytes hold every route whose gather launches of 128 x 32 tiles have at most 256 row tiles (a
+ * misaligned p x k product with k <= 32 names the staging of every row tile: one character each). */
+#define MODL_ROUTE_TRANSFORM 0
+#define MODL_ROUTE_FULL_GRAM 1
+#define MODL_ROUTE_CODE_PRODUCTS 2
+#define MODL_ROUTE_STATS 3
+#define MODL_PRODUCT_ROUTE_MAX 512
+int modl_somf_product_route(const modl_somf_desc *desc, int section, int b, int64_t s, int has_subset, int has_idx,
+                            int64_t ldx, int64_t x_offset, char *buf, size_t cap);
+
 /* G_ = D D^T (prepare / set_params(G_agg='full'), dict_fact.py:355,477) */
 int modl_somf_full_gram(modl_somf_plan *plan, const void *d_Dt, void *d_G, void *stream);
 

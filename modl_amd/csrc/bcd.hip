@@ -2738,7 +2738,7 @@ __global__ __launch_bounds__(256) void atom_stage_flush_kernel(T *Dt, const int3
 // Which kernels take a dictionary update is decided in one place, du_route - a pure function: the debug switches and the two facts
 // about the device (compute units, residency of the persistent launch) are arguments - and launched from one place, dict_update:
 // validate, route, workspace, a helper per family (du_sgd ... du_step).  dict_update_route names the route of a direct call.
-static int device_cu_count() {                                       // one process per GPU: queried once
+int device_cu_count() {                                              // one process per GPU: queried once
     static const int ncu = [] {
         int dev = 0;
         hipDeviceProp_t prop;
@@ -3009,12 +3009,12 @@ template <typename T> static RidePlan plan_ride(const DuCtx<T> &c, const Blocked
     Cd.ptr = R.code; Cd.si = 1; Cd.sk = k;                     // element (i = atom, kk = sample)
     EpiStatsSkip<float> epi{static_cast<float *>(R.Bt), k, R.stamp, R.step, (float)R.beta, (float)R.wt, (float)R.bdiv, R.replace};
     p.rid.P = plan_stats<EpiStatsSkip<float>>(Xo, Cd, R.p, k, R.b, epi);
-    // wide tiles (gemm_wide.hpp) keep their X tile in LDS for 128 atoms: X is fetched twice instead of eight times, and a
-    // tile is still short enough for the shadow of a block step.  (Very large feature counts do not ride at all:
-    // somf_step.hip runs their product as its own k-wide launch.)
-    if (R.p >= 2048) p.rid.W = plan_wide<32, EpiStatsSkip<float>, 128>(Xo, Cd, R.p, k, R.b, epi);
-    p.rid.wide = p.rid.W.ok ? 32 : 0;
-    if ((p.rid.P.ok || p.rid.wide) && R.p > 0) {
+    // which tiles ride is rider_route's (step_products.hip); this launch carries them
+    const RiderKind kind = rider_route(/*proper_subset*/ true, /*dx_full*/ false, /*no_rider_flag*/ false, /*carried*/ true, R.p, k, R.b,
+                                       R.ldx, dense_unaligned<float>(Xo), dense_unaligned<float>(Cd)).kind;
+    if (kind == RIDER_WIDE) p.rid.W = plan_wide<32, EpiStatsSkip<float>, 128>(Xo, Cd, R.p, k, R.b, epi);
+    p.rid.wide = kind == RIDER_WIDE ? 32 : 0;
+    if (kind == RIDER_WIDE || kind == RIDER_TILES32) {
         p.tiles = p.rid.wide ? p.rid.W.tm * p.rid.W.tn : p.rid.P.tn * p.rid.P.tm;
         // as few carrier launches as the idle compute units allow (a tile needs a compute unit to itself for most of a
         // block step; more tiles than free units would queue and stretch the launch)
@@ -3301,7 +3301,7 @@ int dict_update(hipStream_t stream, const DictUpdateArgs<T> &a, int *launches) {
     if (s <= 0 || k <= 0) return MODL_OK;
     if (k > MODL_MAX_COMPONENTS) return MODL_EINVAL;
     const DuLayout L = du_layout(sizeof(T), s, k);
-    const DuRoute R = du_route(sizeof(T), k, s, a.optimizer, a.comp_pos, a.comp_l1_ratio, a.order != nullptr, a.rider && a.rider->p >= 2048,
+    const DuRoute R = du_route(sizeof(T), k, s, a.optimizer, a.comp_pos, a.comp_l1_ratio, a.order != nullptr, a.rider && rider_asks_wide_lds(a.rider->p),
                                a.allow_persist, du_route_switches(), L, device_cu_count(), bcd_persist_fits);
     // (the wide path checks for itself, a null h_order before the workspace)
     if (R.family == DU_WIDE) return dict_update_wide<T>(stream, a, launches);

@@ -19,6 +19,7 @@
 // gemm_reduce_kernel, so results are run-to-run deterministic.
 #pragma once
 #include "common.hpp"
+#include "gemm_plan.hpp"
 #include <type_traits>
 
 namespace modl {
@@ -321,33 +322,15 @@ template <typename T> struct TileCfg;
 template <> struct TileCfg<float> { static constexpr int BK = 16, BKT = 32, RB = 2, RS = 1, RT = 1; };
 template <> struct TileCfg<double> { static constexpr int BK = 16, BKT = 32, RB = 4, RS = 2, RT = 2; };
 
-// target_wgs: how many workgroups we would like in flight (256 CUs, a few per CU)
+// a product as plan_gather (gemm_plan.hpp) planned it with this scratch
 template <typename T, class Epi>
-int launch_gemm(hipStream_t stream, const Operand &A, const Operand &B, int64_t M, int64_t N, int64_t K,
-                const Epi &epi, const SplitWs &ws, int *launches = nullptr, int target_wgs = 512,
-                int max_splits = 64) {
-    if (M <= 0 || N <= 0) return MODL_OK;
+int launch_gemm_planned(hipStream_t stream, const GatherPlan &G, const Operand &A, const Operand &B, int64_t M, int64_t N, int64_t K,
+                        const Epi &epi, const SplitWs &ws, int *launches = nullptr) {
     using C = TileCfg<T>;
-    int cfg, bm, bn;                              // 0 big, 1 small, 2 tall
-    if (N <= 32) { cfg = 2; bm = 128; bn = 32; }
-    else if (cdiv(M, 128) * cdiv(N, 128) >= 512) { cfg = 0; bm = 128; bn = 128; }
-    else { cfg = 1; bm = 64; bn = 64; }
-    const int64_t tm = cdiv(M, bm), tn = cdiv(N, bn);
-    int64_t splits = 1;
-    if (K > 0 && tm * tn < target_wgs && max_splits > 1 && ws.ptr) {
-        splits = target_wgs / (tm * tn);
-        const int64_t max_by_k = K / (8 * C::BK) > 0 ? K / (8 * C::BK) : 1;   // >= 8 k-tiles per split
-        if (splits > max_by_k) splits = max_by_k;
-        if (splits > max_splits) splits = max_splits;
-        const int64_t max_by_ws = (int64_t)(ws.bytes / sizeof(T)) / (M * N);
-        if (splits > max_by_ws) splits = max_by_ws;
-        if (splits < 1) splits = 1;
-    }
-    const int64_t Kp = K > 0 ? K : 1;
-    const int bk = (cfg == 2) ? C::BKT : C::BK;
-    const int64_t kps = cdiv(cdiv(Kp, splits), bk) * bk;
-    splits = cdiv(Kp, kps);
-    dim3 grid((unsigned)tn, (unsigned)tm, (unsigned)splits);
+    static_assert(C::BK == kGatherBK && C::BKT == kGatherBKTall, "plan_gather plans with the kernels' K-tiles");
+    const int cfg = G.cfg;
+    const int64_t kps = G.kps, splits = G.splits;
+    dim3 grid((unsigned)G.tn, (unsigned)G.tm, (unsigned)splits);
     T *partial = static_cast<T *>(ws.ptr);
     if (cfg == 0)
         hipLaunchKernelGGL((gemm_kernel<T, C::RB, C::RB, 2, 2, C::BK, Epi>), grid, dim3(256), 0, stream, A, B, M, N, K,
@@ -367,6 +350,16 @@ int launch_gemm(hipStream_t stream, const Operand &A, const Operand &B, int64_t 
         if (launches) ++*launches;
     }
     return MODL_OK;
+}
+
+// target_wgs: how many workgroups we would like in flight (256 CUs, a few per CU)
+template <typename T, class Epi>
+int launch_gemm(hipStream_t stream, const Operand &A, const Operand &B, int64_t M, int64_t N, int64_t K,
+                const Epi &epi, const SplitWs &ws, int *launches = nullptr, int target_wgs = 512,
+                int max_splits = 64) {
+    if (M <= 0 || N <= 0) return MODL_OK;
+    return launch_gemm_planned<T, Epi>(stream, plan_gather(M, N, K, ws.ptr != nullptr, ws.bytes / sizeof(T), target_wgs, max_splits), A, B,
+                                       M, N, K, epi, ws, launches);
 }
 
 }  // namespace modl

@@ -400,7 +400,7 @@ __device__ __forceinline__ void gemm_dense_tile_auto(const DenseOperand &A, cons
                                                      int64_t K, int64_t kps, T *partial, const Epi &epi, int bx, int by, int bz,
                                                      int nsplit, T (*As)[BK][BM + 4], T (*Bs)[BK][BN + 4],
                                                      unsigned long long *dbg = nullptr) {
-    constexpr int NKT = 8;
+    constexpr int NKT = kDenseRkTiles;                       // (dense_tile_of, gemm_plan.hpp, names the same choice on the host)
     if constexpr (sizeof(T) == 4 && BM <= 64 && BN <= 64) {      // (128 x 128 tiles: 256 registers of operands - the pipelined tile only)
         const int64_t k_begin = (int64_t)bz * kps, k_end = (k_begin + kps < K) ? k_begin + kps : K;
         if (k_end - k_begin <= (int64_t)NKT * BK) {
@@ -439,45 +439,34 @@ template <typename T, class Epi> struct DenseProblem {
     unsigned long long *dbg = nullptr;                // diagnostics: shader-clock stamps of the FIRST tile (resident-K variant)
 };
 
+// the sizes and the split are plan_dense_sizes' (gemm_plan.hpp); here the operands, the scratch and the epilogue are attached
+template <typename T, class Epi>
+DenseProblem<T, Epi> dense_problem(const DensePlan &d, const DenseOperand &A, const DenseOperand &B, int64_t M, int64_t N, int64_t K,
+                                   const Epi &epi, T *ws) {
+    DenseProblem<T, Epi> P;
+    P.A = A; P.B = B; P.M = M; P.N = N; P.K = K; P.epi = epi;
+    P.A.unal = d.unal_a; P.B.unal = d.unal_b;
+    P.ok = d.ok;
+    if (!P.ok) return P;
+    P.kps = d.kps; P.splits = d.splits; P.tn = d.tn; P.tm = d.tm; P.sym = d.sym;
+    P.partial = ws;
+    return P;
+}
+template <typename T> bool dense_unaligned(const DenseOperand &o) {
+    const int64_t ld = (o.si == 1) ? o.sk : o.si;
+    return !((reinterpret_cast<uintptr_t>(o.ptr) % 16 == 0) && (ld % Vec4<T>::N == 0));
+}
+inline bool dense_contiguous(const DenseOperand &o) { return o.si == 1 || o.sk == 1; }
+
 template <typename T, class Epi>
 DenseProblem<T, Epi> plan_dense(const DenseOperand &A, const DenseOperand &B, int64_t M, int64_t N, int64_t K, const Epi &epi,
                                 T *ws, size_t ws_elems, int target_wgs = 512, int max_splits = 64, int bm = 64, int bn = 64,
                                 bool symmetric = false) {
-    DenseProblem<T, Epi> P;
-    P.A = A; P.B = B; P.M = M; P.N = N; P.K = K; P.epi = epi;
-    constexpr int VN = Vec4<T>::N;
-    auto contiguous = [](const DenseOperand &o) { return o.si == 1 || o.sk == 1; };
-    auto aligned = [](const DenseOperand &o) {
-        const int64_t ld = (o.si == 1) ? o.sk : o.si;
-        return (reinterpret_cast<uintptr_t>(o.ptr) % 16 == 0) && (ld % VN == 0);
-    };
-    P.ok = contiguous(A) && contiguous(B) && K > 0 && M > 0 && N > 0;
-    if (!P.ok) return P;
-    P.A.unal = !aligned(A);
-    P.B.unal = !aligned(B);
-    // (small misaligned products stay with the gather kernel: nothing to gain, and the toy-sized golden trajectories
-    //  recorded from the reference keep the summation order they were validated with)
-    if ((P.A.unal || P.B.unal) && M * N * K < (int64_t)1 << 22) { P.ok = false; return P; }
-    constexpr int BK = (sizeof(T) == 4) ? 32 : 16;
-    const int64_t tm = cdiv(M, bm), tn = cdiv(N, bn);
-    const bool sym = symmetric && M == N && bm == bn && A.ptr == B.ptr && A.si == B.si && A.sk == B.sk;
-    const int64_t ntile = sym ? tm * (tm + 1) / 2 : tm * tn;
-    int64_t splits = 1;
-    if (ntile < target_wgs && max_splits > 1 && ws) {
-        splits = target_wgs / ntile;
-        const int64_t max_by_k = K / (4 * BK) > 0 ? K / (4 * BK) : 1;       // >= 4 k-tiles per split
-        if (splits > max_by_k) splits = max_by_k;
-        if (splits > max_splits) splits = max_splits;
-        const int64_t max_by_ws = (int64_t)ws_elems / (M * N);
-        if (splits > max_by_ws) splits = max_by_ws;
-        if (splits < 1) splits = 1;
-    }
-    P.kps = cdiv(cdiv(K, splits), BK) * BK;
-    P.splits = (int)cdiv(K, P.kps);
-    P.tn = (int)tn; P.tm = (int)tm;
-    P.partial = ws;
-    P.sym = (sym && P.splits > 1) ? 1 : 0;              // (a direct store would need the mirrored epilogue: split-K only)
-    return P;
+    const bool same = A.ptr == B.ptr && A.si == B.si && A.sk == B.sk;
+    return dense_problem<T, Epi>(plan_dense_sizes(sizeof(T), dense_contiguous(A) && dense_contiguous(B), dense_unaligned<T>(A),
+                                                  dense_unaligned<T>(B), same, M, N, K, ws != nullptr, ws_elems, target_wgs, max_splits,
+                                                  bm, bn, symmetric),
+                                 A, B, M, N, K, epi, ws);
 }
 
 template <typename T, bool AI0, bool BI0, class Epi0, bool AI1, bool BI1, class Epi1, int BM1 = 64, int BN1 = 64, int BK1 = 0, int BM0 = 64,
@@ -609,7 +598,6 @@ int launch_gemm_dense_pair(hipStream_t stream, const DenseProblem<T, Epi0> &P0, 
 // times the workgroups of the 64 x 64 tiling and a quarter of the matrix-core work per wavefront.  These products
 // are latency-bound per tile, not throughput-bound (the head of the increment is 80 tiles of 64 x 64 on a
 // 256-CU chip), so the tile's critical path is what counts.  Same pairing / XCD renumbering as above.
-constexpr int kStatsTile = 32, kStatsBK = 64, kStatsNKT = 4;
 
 template <class Epi>
 __device__ __forceinline__ void gemm_stats_tile(const DenseProblem<float, Epi> &P, int id, char *smem,
@@ -646,7 +634,7 @@ DenseProblem<float, Epi> plan_stats(const DenseOperand &A, const DenseOperand &B
     DenseProblem<float, Epi> P;
     if (M > 0 && N > 0) P = plan_dense<float, Epi>(A, B, M, N, K, epi, nullptr, 0, 512, 1, kStatsTile, kStatsTile);
     P.epi = epi;
-    P.ok = (M <= 0 || N <= 0) || (P.ok && A.si == 1 && B.si == 1 && K <= (int64_t)kStatsNKT * kStatsBK);
+    P.ok = plan_stats_ok(A.si == 1 && B.si == 1, dense_unaligned<float>(A), dense_unaligned<float>(B), M, N, K);
     return P;
 }
 
@@ -663,19 +651,18 @@ int launch_gemm_stats_pair(hipStream_t stream, const DenseProblem<float, Epi0> &
 
 // Dense launcher.  Requires 16-byte aligned bases and leading strides that keep every vector
 // aligned; otherwise falls back to the generic gather kernel (gemm.hpp).
+// ... as plan_product (gemm_plan.hpp) planned it with this scratch: a caller that has the plan already launches from it
 template <typename T, class Epi>
-int launch_gemm_dense(hipStream_t stream, const DenseOperand &A, const DenseOperand &B, int64_t M, int64_t N, int64_t K,
-                      const Epi &epi, const SplitWs &ws, int *launches = nullptr, int target_wgs = 512,
-                      int max_splits = 64) {
+int launch_product(hipStream_t stream, const ProductLaunch &L, const DenseOperand &A, const DenseOperand &B, int64_t M, int64_t N,
+                   int64_t K, const Epi &epi, const SplitWs &ws, int *launches = nullptr) {
     if (M <= 0 || N <= 0) return MODL_OK;
-    const DenseProblem<T, Epi> P = plan_dense<T, Epi>(A, B, M, N, K, epi, static_cast<T *>(ws.ptr), ws.bytes / sizeof(T),
-                                                      target_wgs, max_splits);
-    if (!P.ok) {
+    if (!L.dense) {
         Operand a, b;
         a.ptr = A.ptr; a.si = A.si; a.sk = A.sk;
         b.ptr = B.ptr; b.si = B.si; b.sk = B.sk;
-        return launch_gemm<T, Epi>(stream, a, b, M, N, K, epi, ws, launches, target_wgs, max_splits);
+        return launch_gemm_planned<T, Epi>(stream, L.g, a, b, M, N, K, epi, ws, launches);
     }
+    const DenseProblem<T, Epi> P = dense_problem<T, Epi>(L.d, A, B, M, N, K, epi, static_cast<T *>(ws.ptr));
     dim3 grid((unsigned)P.tn, (unsigned)P.tm, (unsigned)P.splits);
     const bool ai = A.si == 1, bi = B.si == 1;
 #define MODL_GD(AI, BI) \
@@ -694,6 +681,16 @@ int launch_gemm_dense(hipStream_t stream, const DenseOperand &A, const DenseOper
         if (launches) ++*launches;
     }
     return MODL_OK;
+}
+template <typename T, class Epi>
+int launch_gemm_dense(hipStream_t stream, const DenseOperand &A, const DenseOperand &B, int64_t M, int64_t N, int64_t K,
+                      const Epi &epi, const SplitWs &ws, int *launches = nullptr, int target_wgs = 512,
+                      int max_splits = 64) {
+    if (M <= 0 || N <= 0) return MODL_OK;
+    return launch_product<T, Epi>(stream,
+                                  plan_product(sizeof(T), dense_contiguous(A) && dense_contiguous(B), dense_unaligned<T>(A),
+                                               dense_unaligned<T>(B), M, N, K, ws.ptr != nullptr, ws.bytes / sizeof(T), target_wgs, max_splits),
+                                  A, B, M, N, K, epi, ws, launches);
 }
 
 // ---- compaction kernels -------------------------------------------------------

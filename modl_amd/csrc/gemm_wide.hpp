@@ -20,7 +20,7 @@
 
 namespace modl {
 
-constexpr int kWideBK = 32, kWideKmax = 256;
+// (kWideBK, kWideKmax: gemm_plan.hpp)
 // LDS row padding of 16 floats: a fragment read takes 4 consecutive rows x 16 consecutive floats; with a row stride of
 // 16 (mod 32) banks the four rows fall on banks 0-15 / 16-31 alternately (2 lanes per bank, the minimum for 64 lanes);
 // a stride of 4 (mod 32) makes it a 4-way conflict
@@ -51,9 +51,8 @@ WideProblem<Epi> plan_wide(const DenseOperand &A, const DenseOperand &B, int64_t
     P.Cd = static_cast<const float *>(B.ptr); P.ldc = B.sk;
     P.M = M; P.N = (int)N; P.K = (int)K;
     P.tm = (int)cdiv(M, BM); P.tn = (int)cdiv(N, BN);
-    P.ok = A.si == 1 && B.si == 1 && M > 0 && N > 0 && K > 0 && K <= kWideKmax && M % 4 == 0 && N % 4 == 0 &&
-           A.sk % 4 == 0 && B.sk % 4 == 0 && reinterpret_cast<uintptr_t>(A.ptr) % 16 == 0 &&
-           reinterpret_cast<uintptr_t>(B.ptr) % 16 == 0;
+    P.ok = plan_wide_ok(A.si == 1 && B.si == 1, M, N, K, A.sk, B.sk, reinterpret_cast<uintptr_t>(A.ptr) % 16 == 0,
+                        reinterpret_cast<uintptr_t>(B.ptr) % 16 == 0);
     return P;
 }
 

@@ -1,6 +1,7 @@
 // Declarations shared between the translation units of libmodl_hip.
 #pragma once
 #include "common.hpp"
+#include "gemm_plan.hpp"
 
 namespace modl {
 
@@ -119,6 +120,91 @@ struct CodeScratch {
 template <typename T>
 int code_solve(hipStream_t stream, CdArgs<T> a, T *Dx, T code_alpha, double l1_ratio, const int64_t *h_gidx,
                const CodeScratch<T> &sc, int *launches);
+
+// ---- step_products.hip ------------------------------------------------------
+// Which matrix-core launches form the products of a minibatch step - Dx and G in front of the code solve, the C_ and B_
+// statistics behind it, the deferred rows of B_ (the rider), the Gram passes of G_agg = full - and of the transform:
+// decided by three pure functions (no device, no global: switches and flags are arguments) and nowhere else.  somf_step.hip
+// switches on their results; bcd.hip's plan_ride reads rider_route; modl_somf_product_route spells them as strings.
+// split-K scratch of a plan, in elements: the largest split product is max(b, k) x k (Dx, Gram, C increment) with up to
+// 64 splits; the p x k product (B increment) has >= 512 tiles at p >= 8k and is not split
+size_t split_scratch_elems(int64_t max_batch, int k, int64_t p);
+
+// The rider: the B_ update of the rows that were not sampled, deferred to the idle compute units of the dictionary
+// update's launches.  Both thresholds live here.
+constexpr int64_t kRiderMaxTiles = 1024;      // 64-feature tiles: from this many on (p > 65 472) nothing rides - the p x k
+                                              // product runs as its own k-wide launch, and stats_route's wide pair begins
+constexpr int64_t kRiderWideRows = 2048;      // features from which the rider takes k-wide tiles (32 x 128) instead of 32 x 32.
+// du_route is asked the residency question of the persistent launch with the wide tile's LDS whenever p >= kRiderWideRows,
+// even where plan_wide then declines and the rider takes the 32 x 32 tiles after all (p = 2402: not a multiple of 4).
+// That is how the update has always been routed; it stays.
+inline bool rider_too_tall(int64_t rows) { return cdiv(rows, 64) >= kRiderMaxTiles; }
+inline bool rider_asks_wide_lds(int64_t p) { return p >= kRiderWideRows; }
+enum RiderKind {
+    RIDER_NONE,       // every row of B_ in the statistics launch (why: RiderWhy)
+    RIDER_WIDE,       // rides as k-wide tiles of 32 features x 128 atoms
+    RIDER_TILES32,    // rides as 32 x 32 tiles
+    RIDER_AFTER,      // the dictionary update has no launch that carries it: completed behind the update, by stats_route
+};
+enum RiderWhy { RIDER_RIDES, RIDER_NO_PROPER_SUBSET, RIDER_DX_FULL, RIDER_FLAG, RIDER_TOO_TALL };
+struct RiderRoute { RiderKind kind = RIDER_NONE; RiderWhy why = RIDER_RIDES; };
+// proper_subset: a subset array with 0 < s < p that the step gathers; carried: the dictionary update runs the fused f32
+// block or persistent launches (du_carries_riders); unal_x / unal_c: X (leading stride ldx) / the code rows (stride k)
+// off 16 bytes
+bool du_carries_riders(size_t tsz, int k, int optimizer, int comp_pos, double comp_l1_ratio);
+RiderRoute rider_route(bool proper_subset, bool dx_full, bool no_rider_flag, bool carried, int64_t p, int k, int b, int64_t ldx,
+                       bool unal_x, bool unal_c);
+
+enum StatsKind { STATS_RESIDENT, STATS_WIDE_PAIR, STATS_PAIR32, STATS_DENSE_PAIR, STATS_EACH };
+enum StatsEpi { STATS_EPI_VEC4, STATS_EPI_ROWS };       // the epilogue takes 16 bytes at a time / is row-indirected or stamped
+struct StatsRoute {
+    StatsKind kind = STATS_EACH;
+    bool unal = false;            // an operand off 16 bytes
+    StatsEpi epi = STATS_EPI_ROWS; // resident: how the second product's epilogue stores
+    DensePlan P0, P1;             // dense pair: the two plans (P1 on kStatBM x kStatBN tiles)
+    ProductLaunch C, B;           // one launch each (C: only with M0 > 0): stats_pair launches from these plans
+};
+#ifndef MODL_STAT_BM
+#define MODL_STAT_BM 64
+#define MODL_STAT_BN 64
+#endif
+#ifndef MODL_STAT_BK
+#define MODL_STAT_BK 0
+#endif
+constexpr int kStatBM = MODL_STAT_BM, kStatBN = MODL_STAT_BN, kStatBK = MODL_STAT_BK;   // block tile of the p x k increment product
+constexpr int64_t kResidentMinRows = 4096;
+// code^T code (M0 x N; M0 == 0: none) and X^T code (M1 x N, X's leading stride ld1), both contracted over K samples.
+// unal_c / unal_x: operand off 16 bytes; stamps: diagnostics stamps are wanted (32 x 32 tiles only); resident_switch:
+// MODL_DEBUG_STATS_RESIDENT; epi: the second product's epilogue
+StatsRoute stats_route(size_t tsz, int64_t M0, int64_t N, int64_t M1, int64_t K, bool unal_c, bool unal_x, int64_t ld1, StatsEpi epi,
+                       bool stamps, bool resident_switch, size_t ws_elems);
+
+struct CodeProductsRoute {
+    bool need_sub = false;        // Ds = Dt[subset] (and Xs = X[:, subset]) are gathered
+    int n_norm = 0, n_rows = 0, n_cols = 0, n_code = 0, fuse_cols = 0, gx = 0;   // the prep launch's parts (workgroups)
+    int64_t s_pad = 0;
+    bool x_gathered = false;      // Dx contracts Xs (leading stride s_pad) instead of X
+    int64_t Kdim = 0;             // Dx's contraction length
+    bool want_G = false, paired = false;
+    DensePlan PD, PG;             // paired: Dx and G in one launch
+    ProductLaunch Dx, G;          // else one launch each: phase1 launches from these plans
+    bool g_average = false;       // rows of G_average are updated
+    bool track_G = false, partial_G = false;   // G_agg = full: G_ -= / += over the sampled rows when s < p / 2, else recomputed
+    GatherPlan gram;              // ... that launch (gram_of_rows)
+    RiderRoute rider;
+};
+// G_agg = full: the dictionary update subtracts the sampled rows' Gram before and adds it after (dict_fact.py:667, 711-715)
+// while they are fewer than half the features; else G_ is recomputed over all of p
+inline bool gram_is_partial(int64_t s, int64_t p) { return (double)s < (double)p / 2.0; }
+constexpr int kPrepRows = 8;      // rows per workgroup of prep_kernel's row gathers
+struct StepBases { bool x = true, dt = true, code = true; };   // the caller's X, Dt and code_ start on a 16-byte boundary
+// has_subset / has_idx: the minibatch carries a subset / sample-index array (with one, the code rows of the statistics
+// are the plan's compact copy)
+CodeProductsRoute code_products_route(const modl_somf_desc &d, int b, int64_t s, bool has_subset, bool has_idx, int64_t ldx,
+                                      const StepBases &al, size_t ws_elems);
+// modl_somf_product_route (section: MODL_ROUTE_*): the route as the string tests/test_product_routes.py: expected_route spells
+int product_route_name(const modl_somf_desc &d, int section, int b, int64_t s, bool has_subset, bool has_idx, int64_t ldx,
+                       int64_t x_offset, bool resident_switch, char *buf, size_t cap);
 
 // ---- enet.hip ---------------------------------------------------------------
 template <typename T>
@@ -274,6 +360,7 @@ struct DuRoute {
 // the route of a direct call as the string tests/test_dict_update_routes.py: expected_route spells (modl_dict_update_route)
 int dict_update_route(int dtype, int k, int64_t s, int optimizer, int comp_pos, double comp_l1_ratio, int ncu, char *buf,
                       size_t cap);
+int device_cu_count();            // compute units of the current device (one process per GPU: queried once)
 size_t dict_update_workspace(int dtype, int64_t s_max, int k);
 size_t dict_update_stamps_offset(int dtype, int64_t s_max, int k);
 size_t dict_update_persist_stamps_offset(int dtype, int64_t s_max, int k);

@@ -43,14 +43,6 @@ static const char *kSectionNames[SEC_COUNT] = {"code_gemm", "code_solve", "stats
 
 constexpr int kStageSlots = 8;
 constexpr int kProfPool = 2048;      // event pairs kept before a flush
-#ifndef MODL_STAT_BM
-#define MODL_STAT_BM 64
-#define MODL_STAT_BN 64
-#endif
-#ifndef MODL_STAT_BK
-#define MODL_STAT_BK 0
-#endif
-constexpr int kStatBM = MODL_STAT_BM, kStatBN = MODL_STAT_BN, kStatBK = MODL_STAT_BK;   // block tile of the p x k increment product
 
 template <typename T> struct EpiDxAverage {   // dict_fact.py:596-601
     T *Dx; T *avg; const int64_t *idx; const T *w_sample; int64_t k; T alpha;
@@ -130,7 +122,6 @@ template <typename T> struct PrepArgs {
     int32_t *stamp, *pos; int32_t step;                                       // stamp[subset[i]] = step, pos[subset[i]] = i
     int fuse_cols;        // the row-norm workgroups also gather the sampled columns of their row (n_cols == 0 then)
 };
-constexpr int kPrepRows = 8;      // rows per workgroup of prep_kernel's row gathers
 template <typename T>
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs<T> a) {
     __shared__ double red[4];
@@ -564,64 +555,36 @@ int solve_codes(modl_somf_plan *pl, hipStream_t st, const T *G, int64_t g_stride
     return code_solve<T>(st, a, Dx, (T)d.code_alpha, d.code_l1_ratio, h_gidx, sc, nl);
 }
 
-constexpr int64_t kResidentMinRows = 4096;
-
-// Two statistics products (contraction over the b samples of the minibatch, both operands contiguous along their
-// rows) in ONE launch; M0 == 0: only the second.  f32 with b <= 256 goes through the 32 x 32 / 16x16x4 tiling
-// (gemm_stats_pair_kernel), anything else through the generic pair kernel or, unaligned, the gather kernel.  Every
-// statistics product of the step comes through here, so that the fused, the two-phase and the riding variants of the
-// same product sum in the same order (bit-identical results).
+// Two statistics products in ONE launch where stats_route (step_products.hip) finds one: code^T code (M0 x N; M0 == 0: none)
+// and X^T code (M1 x N), contracted over the K samples of the minibatch, both operands contiguous along their rows.  Every
+// statistics product of the step comes through here, so that the fused, the two-phase and the riding variants of the same
+// product sum in the same order (bit-identical results).  The tiles' measurements: gemm_wide.hpp, gemm_resident.hpp.
 template <typename T, class Epi0, class Epi1>
-int stats_pair(hipStream_t st, const DenseOperand &A0, const DenseOperand &B0, int64_t M0, int64_t N0, const Epi0 &e0,
-               const DenseOperand &A1, const DenseOperand &B1, int64_t M1, int64_t N1, const Epi1 &e1, int64_t K,
-               const SplitWs &sws, int *launches, unsigned long long *dbg = nullptr) {
+int stats_pair(hipStream_t st, const DenseOperand &Cd, int64_t M0, const Epi0 &e0, const DenseOperand &X1, int64_t M1,
+               const Epi1 &e1, int64_t N, int64_t K, const SplitWs &sws, int *launches, unsigned long long *dbg = nullptr) {
+    const StatsRoute R = stats_route(sizeof(T), M0, N, M1, K, dense_unaligned<T>(Cd), dense_unaligned<T>(X1), X1.sk,
+                                     EpiHasVec4<Epi1>::value ? STATS_EPI_VEC4 : STATS_EPI_ROWS, dbg != nullptr, g_stats_resident.load(std::memory_order_relaxed) != 0, sws.bytes / sizeof(T));
     if constexpr (std::is_same<T, float>::value) {
-        auto P0 = plan_stats<Epi0>(A0, B0, M0, N0, K, e0);
-        // a VERY tall second problem (the whole p x k product at p >= 65 536): k-wide tiles, X read once (gemm_wide.hpp),
-        // 32 features x 256 atoms.  The tile is latency-bound (its code tiles come from L2 once per 32 features, its old
-        // values and its X tile from HBM), so what counts is how many workgroups share a compute unit: an 8-sample code
-        // tile and swizzled, unpadded LDS rows make it 48 KB - THREE per compute unit: 0.351 ms at p = 200 000 (75 TFLOP/s,
-        // 48 % of the f32 matrix peak); 16 samples, padded rows, two per unit: 0.385-0.397; 32 samples, one per unit:
-        // 0.489; 4 samples, four per unit: 0.387 (a barrier every 256 matrix-core cycles); 64 features, one per unit:
-        // 0.46.  At p = 10 000 the 32 x 32 tiles are faster (27 us against 37 us: ten times the workgroups to hide latency)
-        // a TALL second problem (the whole p x k product: reduction 1, or config 5's 200 000 features) with at most 256 atoms:
-        // persistent workgroups with the code matrix resident in registers (gemm_resident.hpp), tiles of 16 or 32 features -
-        // whichever leaves the slowest workgroup less to contract
-        if (P0.ok && M1 >= kResidentMinRows && N1 <= 256 && K % 4 == 0 && !dbg && g_stats_resident.load(std::memory_order_relaxed)) {
-            auto W = plan_wide<16, Epi1>(A1, B1, M1, N1, K, e1);
-            if (W.ok) {
-                static const int ncu = [] {
-                    int dev = 0;
-                    hipDeviceProp_t prop;
-                    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                        return prop.multiProcessorCount;
-                    return 256;
-                }();
-                return launch_gemm_stats_resident_pair<16, Epi0, Epi1>(st, P0, W, ncu, launches);
-            }
-        }
-        if (P0.ok && cdiv(M1, 64) >= 1024 && !dbg) {
-            auto W = plan_wide<32, Epi1>(A1, B1, M1, N1, K, e1);
-            if (W.ok) return launch_gemm_stats_wide_pair<32, Epi0, Epi1, 256, 8, 0, true>(st, P0, W, launches);
-        }   // (32 x 128 wide tiles as their own launch at p = 10 000: 40 us against 28 us for the 32 x 32 tiles, measured)
-        auto P1 = plan_stats<Epi1>(A1, B1, M1, N1, K, e1);
-        if (P0.ok && P1.ok) {
+        if (R.kind == STATS_RESIDENT || R.kind == STATS_WIDE_PAIR || R.kind == STATS_PAIR32) {
+            auto P0 = plan_stats<Epi0>(Cd, Cd, M0, N, K, e0);
+            if (R.kind == STATS_RESIDENT)
+                return launch_gemm_stats_resident_pair<16, Epi0, Epi1>(st, P0, plan_wide<16, Epi1>(X1, Cd, M1, N, K, e1), device_cu_count(),
+                                                                       launches);
+            // (32 x 128 wide tiles as their own launch at p = 10 000: 40 us against 28 us for the 32 x 32 tiles, measured)
+            if (R.kind == STATS_WIDE_PAIR)
+                return launch_gemm_stats_wide_pair<32, Epi0, Epi1, 256, 8, 0, true>(st, P0, plan_wide<32, Epi1>(X1, Cd, M1, N, K, e1), launches);
+            auto P1 = plan_stats<Epi1>(X1, Cd, M1, N, K, e1);
             P1.dbg = dbg;
             return launch_gemm_stats_pair<Epi0, Epi1>(st, P0, P1, launches);
         }
     }
-    DenseProblem<T, Epi0> P0;
-    P0.epi = e0;
-    bool ok0 = true;
-    if (M0 > 0) {
-        P0 = plan_dense<T, Epi0>(A0, B0, M0, N0, K, e0, nullptr, 0);
-        ok0 = P0.ok;
+    if (R.kind == STATS_DENSE_PAIR) {
+        DenseProblem<T, Epi0> P0 = dense_problem<T, Epi0>(R.P0, Cd, Cd, M0, N, K, e0, nullptr);
+        return launch_gemm_dense_pair<T, true, true, Epi0, true, true, Epi1, kStatBM, kStatBN, kStatBK>(
+            st, P0, dense_problem<T, Epi1>(R.P1, X1, Cd, M1, N, K, e1, nullptr), launches);
     }
-    auto P1 = plan_dense<T, Epi1>(A1, B1, M1, N1, K, e1, nullptr, 0, 512, 1, kStatBM, kStatBN);
-    if (ok0 && P1.ok)
-        return launch_gemm_dense_pair<T, true, true, Epi0, true, true, Epi1, kStatBM, kStatBN, kStatBK>(st, P0, P1, launches);
-    if (M0 > 0) MODL_TRY((launch_gemm_dense<T, Epi0>(st, A0, B0, M0, N0, K, e0, sws, launches)));
-    return launch_gemm_dense<T, Epi1>(st, A1, B1, M1, N1, K, e1, sws, launches);
+    if (M0 > 0) MODL_TRY((launch_product<T, Epi0>(st, R.C, Cd, Cd, M0, N, K, e0, sws, launches)));
+    return launch_product<T, Epi1>(st, R.B, X1, Cd, M1, N, K, e1, sws, launches);
 }
 
 // Codes of the minibatch, then the statistics update C <- (1 - w) C + (w / b_global) code^T code (the same for B_)
@@ -667,110 +630,58 @@ int phase1(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_batch
     T *cb = codeb;
     if (!d_idx) cb = code;                                             // rows 0..b-1 are already contiguous
 
-    T *ws_split = reinterpret_cast<T *>(sws.ptr);
-    const size_t ws_elems = sws.bytes / sizeof(T);
-    bool ride = false;
+    const auto on16 = [](const void *q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; };
+    const CodeProductsRoute R = code_products_route(d, b, s, d_subset != nullptr, d_idx != nullptr, bt->ldx,
+                                                    StepBases{on16(X), on16(Dt), on16(code)}, sws.bytes / sizeof(T));
+    const bool ride = R.rider.kind != RIDER_NONE;
     pl->ride_pending = false;
     pl->head_pending = false;
     {   // ---- Dx, G  (dict_fact.py:588-620)
         ProfScope ps(pl, st, SEC_CODE_GEMM);
-        // compaction: gather once, contract dense.  Ds = Dt[subset] (whole 1 KiB feature rows),
-        // Xs = X[:, subset].  With every feature sampled nothing is copied.  One launch for the row
-        // norms and every gather.
-        const T *Dsrc = Dt, *Xsrc = X;
-        int64_t ldxs = bt->ldx;
-        const bool need_sub = d_subset && (d.Dx_agg != MODL_AGG_FULL || d.G_agg != MODL_AGG_FULL);
+        // compaction: gather once, contract dense (code_products_route): one launch for the row norms and every gather
         PrepArgs<T> pa;
-        pa.X = X; pa.ldx = bt->ldx; pa.p = p; pa.b = b; pa.xnorm = xnorm; pa.n_norm = (d.code_l1_ratio != 0.0) ? b : 0;
-        pa.Dt = Dt; pa.subset = d_subset; pa.s = s; pa.k = k; pa.Ds = Dsb; pa.n_rows = need_sub ? (int)cdiv(s, kPrepRows) : 0;
-        pa.s_pad = s_pad; pa.Xs = Xsb; pa.gx = (int)std::min<int64_t>(cdiv(s_pad, 256), 64);
-        pa.n_cols = (need_sub && d.Dx_agg != MODL_AGG_FULL) ? pa.gx * b : 0;
-        // the column gather rides with the row norms when a row fits in LDS next to nothing else (<= 64 KB) and the
-        // rows are 16-byte aligned
-        const size_t row_bytes = sizeof(T) * (size_t)p;
-        pa.fuse_cols = (pa.n_cols > 0 && pa.n_norm == b && row_bytes <= 64 * 1024 &&
-                        reinterpret_cast<uintptr_t>(X) % 16 == 0 && (bt->ldx * sizeof(T)) % 16 == 0) ? 1 : 0;
-        if (pa.fuse_cols) pa.n_cols = 0;
-        pa.code = code; pa.idx = d_idx; pa.codeb = codeb; pa.n_code = (cd_on_compact && d_idx) ? (int)cdiv(b, kPrepRows) : 0;
-        const bool proper = need_sub && s > 0 && s < p;               // a proper subset, gathered
-        // only the sampled rows of B_ are needed by the dictionary update -> the rest of the B_ update is deferred
-        // and rides along its launches; the sampled features are stamped so that the rider leaves them alone
-        // (not for very large feature counts: at p = 200 000 the p x k product is 26 GFLOP, the launches of the
-        // dictionary update would wait for their riders - it runs as its own k-wide launch instead, X read once:
-        // 0.39 + 0.39 ms against 0.94 ms riding, measured)
-        ride = proper && d.Dx_agg != MODL_AGG_FULL && !(d.flags & MODL_FLAG_NO_RIDER) && cdiv(p, 64) < 1024;
+        pa.X = X; pa.ldx = bt->ldx; pa.p = p; pa.b = b; pa.xnorm = xnorm; pa.n_norm = R.n_norm;
+        pa.Dt = Dt; pa.subset = d_subset; pa.s = s; pa.k = k; pa.Ds = Dsb; pa.n_rows = R.n_rows;
+        pa.s_pad = s_pad; pa.Xs = Xsb; pa.gx = R.gx;
+        pa.n_cols = R.n_cols;
+        pa.fuse_cols = R.fuse_cols;
+        pa.code = code; pa.idx = d_idx; pa.codeb = codeb; pa.n_code = R.n_code;
+        // the rows of B_ that ride are told from the sampled ones by the stamps that the row gather leaves
         if (ride) pl->step_id = (pl->step_id == 0x7fffffff) ? 1 : pl->step_id + 1;
         pa.stamp = ride ? reinterpret_cast<int32_t *>(pl->dws + pl->off_stamp) : nullptr;
         pa.pos = reinterpret_cast<int32_t *>(pl->dws + pl->off_pos);
         pa.step = pl->step_id;
-        if (need_sub) {
-            Dsrc = Dsb;
-            if (d.Dx_agg != MODL_AGG_FULL) { Xsrc = Xsb; ldxs = s_pad; }
-        }
         const int n_prep = pa.n_norm + pa.n_rows + pa.n_cols + pa.n_code;
         if (n_prep > 0) {
-            hipLaunchKernelGGL((prep_kernel<T>), dim3((unsigned)n_prep), dim3(256), pa.fuse_cols ? row_bytes : 0, st, pa);
+            hipLaunchKernelGGL((prep_kernel<T>), dim3((unsigned)n_prep), dim3(256), pa.fuse_cols ? sizeof(T) * (size_t)p : 0, st, pa);
             MODL_LAUNCH_CHECK();
             ++ps.launches;
         }
-        DenseOperand A, B;
-        int64_t Kdim;
-        T scale;
-        if (d.Dx_agg == MODL_AGG_FULL) {                              // X . D^T
-            A.ptr = X; A.si = bt->ldx; A.sk = 1;
-            B.ptr = Dt; B.si = 1; B.sk = k;
-            Kdim = p; scale = 1;
-        } else {                                                       // X[:, subset] . D[:, subset]^T * reduction
-            A.ptr = Xsrc; A.si = ldxs; A.sk = 1;
-            B.ptr = Dsrc; B.si = 1; B.sk = k;
-            Kdim = s; scale = red;
-        }
-        // the Dx product and the Gram product are independent: one launch (+ one for both split-K sums)
-        DenseOperand Dg;
-        Dg.ptr = Dsrc; Dg.si = 1; Dg.sk = k;
-        const bool want_G = d.G_agg != MODL_AGG_FULL;
-        bool paired = false;
-        if (want_G && A.si != 1) {
-            EpiStore<T> epiG{Gbuf, k, red};
-            const size_t half = ws_elems / 2;
-            // the two products share the chip: 2 workgroups per compute unit in total (256 each) - with 512 each the
-            // split-K partials double and the minibatch at reduction 1 takes 0.352 instead of 0.344 ms (same box),
-            // with 192 or 384 each 0.354 / 0.358 ms
-            constexpr int kPairTarget = 256;
-            // (the Gram matrix is symmetric: only its tiles on and above the diagonal are computed, plan_dense `symmetric`)
-            auto PG = plan_dense<T, EpiStore<T>>(Dg, Dg, k, k, s, epiG, ws_split + half, ws_elems - half, kPairTarget, 64, 64, 64, true);
-            if (d.Dx_agg == MODL_AGG_AVERAGE) {
-                EpiDxAverage<T> epi{Dx, static_cast<T *>(stt->d_Dx_average), d_idx, d_wsample, k, scale};
-                auto PD = plan_dense<T, EpiDxAverage<T>>(A, B, b, k, Kdim, epi, ws_split, half, kPairTarget);
-                if (PD.ok && PG.ok) {
-                    MODL_TRY((launch_gemm_dense_pair<T, false, true, EpiDxAverage<T>, true, true, EpiStore<T>>(st, PD, PG,
-                                                                                                                &ps.launches)));
-                    paired = true;
-                }
-            } else {
-                EpiStore<T> epi{Dx, k, scale};
-                auto PD = plan_dense<T, EpiStore<T>>(A, B, b, k, Kdim, epi, ws_split, half, kPairTarget);
-                if (PD.ok && PG.ok) {
-                    MODL_TRY((launch_gemm_dense_pair<T, false, true, EpiStore<T>, true, true, EpiStore<T>>(st, PD, PG,
-                                                                                                            &ps.launches)));
-                    paired = true;
-                }
+        DenseOperand A, B, Dg;                                         // Dx = A . B^T, G = Dg . Dg^T
+        A.ptr = R.x_gathered ? Xsb : X; A.si = R.x_gathered ? s_pad : bt->ldx; A.sk = 1;
+        B.ptr = Dt; B.si = 1; B.sk = k;
+        Dg.ptr = R.need_sub ? Dsb : Dt; Dg.si = 1; Dg.sk = k;
+        if (d.Dx_agg != MODL_AGG_FULL) B = Dg;                         // X[:, subset] . D[:, subset]^T * reduction
+        const T scale = d.Dx_agg == MODL_AGG_FULL ? (T)1 : red;
+        const EpiStore<T> epiG{Gbuf, k, red};
+        const auto products = [&](const auto &epiDx) {                 // the two independent products, as the route says
+            using EpiDx = std::decay_t<decltype(epiDx)>;
+            if (R.paired) {
+                T *ws_split = reinterpret_cast<T *>(sws.ptr);
+                const size_t half = sws.bytes / sizeof(T) / 2;
+                return launch_gemm_dense_pair<T, false, true, EpiDx, true, true, EpiStore<T>>(
+                    st, dense_problem<T, EpiDx>(R.PD, A, B, b, k, R.Kdim, epiDx, ws_split),
+                    dense_problem<T, EpiStore<T>>(R.PG, Dg, Dg, k, k, s, epiG, ws_split + half), &ps.launches);
             }
-        }
-        if (!paired) {
-            if (d.Dx_agg == MODL_AGG_AVERAGE) {
-                EpiDxAverage<T> epi{Dx, static_cast<T *>(stt->d_Dx_average), d_idx, d_wsample, k, scale};
-                MODL_TRY((launch_gemm_dense<T, EpiDxAverage<T>>(st, A, B, b, k, Kdim, epi, sws, &ps.launches)));
-            } else {
-                EpiStore<T> epi{Dx, k, scale};
-                MODL_TRY((launch_gemm_dense<T, EpiStore<T>>(st, A, B, b, k, Kdim, epi, sws, &ps.launches)));
-            }
-            if (want_G) {
-                EpiStore<T> epi{Gbuf, k, red};
-                MODL_TRY((launch_gemm_dense<T, EpiStore<T>>(st, Dg, Dg, k, k, s, epi, sws, &ps.launches)));
-            }
-        }
-        if (d.G_agg == MODL_AGG_AVERAGE) {
+            MODL_TRY((launch_product<T, EpiDx>(st, R.Dx, A, B, b, k, R.Kdim, epiDx, sws, &ps.launches)));
+            if (R.want_G) MODL_TRY((launch_product<T, EpiStore<T>>(st, R.G, Dg, Dg, k, k, s, epiG, sws, &ps.launches)));
+            return (int)MODL_OK;
+        };
+        if (d.Dx_agg == MODL_AGG_AVERAGE)
+            MODL_TRY(products(EpiDxAverage<T>{Dx, static_cast<T *>(stt->d_Dx_average), d_idx, d_wsample, k, scale}));
+        else
+            MODL_TRY(products(EpiStore<T>{Dx, k, scale}));
+        if (R.g_average) {
             MODL_TRY(launch_update_G_average<T>(st, static_cast<T *>(stt->d_G_average), d_idx, Gbuf, d_wsample, b, k));
             ++ps.launches;
         }
@@ -815,18 +726,18 @@ int phase1(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_batch
             // C_ and the SAMPLED rows of B_ now (one small paired launch over the gathered columns of X) ...
             EpiStatsRows<T> eBs{Bt, k, d_subset, beta, wt, bdiv, replace, mB};
             const bool gstamps = (d.flags & MODL_FLAG_GEMM_STAMPS) != 0;      // (diagnostics)
-            MODL_TRY((stats_pair<T>(st, Cd, Cd, k, k, eC, Xso, Cd, s, k, eBs, b, sws, &ps.launches,
+            MODL_TRY((stats_pair<T>(st, Cd, k, eC, Xso, s, eBs, k, b, sws, &ps.launches,
                                     gstamps ? reinterpret_cast<unsigned long long *>(pl->dws + pl->off_gstamps) : nullptr)));
             // ... the other rows while the dictionary update runs
-            StatsRider &R = pl->rider;
-            R.X = X; R.ldx = bt->ldx; R.code = cb; R.b = b; R.p = p; R.Bt = stt->d_Bt;
-            R.stamp = reinterpret_cast<const int32_t *>(pl->dws + pl->off_stamp); R.step = pl->step_id;
-            R.beta = (double)beta; R.wt = (double)wt; R.bdiv = (double)bdiv; R.replace = replace; R.consumed = 0;
+            StatsRider &sr = pl->rider;
+            sr.X = X; sr.ldx = bt->ldx; sr.code = cb; sr.b = b; sr.p = p; sr.Bt = stt->d_Bt;
+            sr.stamp = reinterpret_cast<const int32_t *>(pl->dws + pl->off_stamp); sr.step = pl->step_id;
+            sr.beta = (double)beta; sr.wt = (double)wt; sr.bdiv = (double)bdiv; sr.replace = replace; sr.consumed = 0;
             pl->ride_pending = true;
         } else {
             // every row of B_ in this launch; without a subset array the head carries all of them
             EpiStats<T> eB{Bt, k, beta, wt, bdiv, replace, d_subset ? nullptr : mB};
-            MODL_TRY((stats_pair<T>(st, Cd, Cd, k, k, eC, Xo, Cd, p, k, eB, b, sws, &ps.launches)));
+            MODL_TRY((stats_pair<T>(st, Cd, k, eC, Xo, p, eB, k, b, sws, &ps.launches)));
             if (two_phase && d_subset && s > 0) {
                 hipLaunchKernelGGL((gather_rows_T_kernel<T, int32_t>), dim3((unsigned)s), dim3(256), 0, st, Bt, (int64_t)k,
                                    d_subset, s, s, (int64_t)k, mB, (int64_t)k);
@@ -895,7 +806,7 @@ int phase2(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_batch
     {
         ProfScope ps(pl, st, SEC_DICT);
         const bool track_G = d.G_agg == MODL_AGG_FULL;
-        const bool partial_G = track_G && (double)s < (double)p / 2.0;   // dict_fact.py:667, 711-715
+        const bool partial_G = track_G && gram_is_partial(s, p);
         if (partial_G) {
             EpiAxpby<T> epi{static_cast<T *>(stt->d_G), k, (T)-1, (T)1};
             MODL_TRY((gram_of_rows<T, EpiAxpby<T>>(pl, st, Dt, d_subset, s, epi, &ps.launches)));
@@ -926,14 +837,15 @@ int phase2(modl_somf_plan *pl, const modl_somf_state *stt, const modl_somf_batch
             pl->ahead_order.swap(njob.order);
         }
         MODL_TRY(rc_du);
-        if (pl->ride_pending && !pl->rider.consumed) {                 // this dictionary update has no fused path
+        // (rider_route's RIDER_AFTER; what decides is the word of the dictionary update itself: no launch of it took the rider)
+        if (pl->ride_pending && !pl->rider.consumed) {
             const StatsRider &R = pl->rider;
             DenseOperand Xo, Cd;
             Xo.ptr = R.X; Xo.si = 1; Xo.sk = R.ldx;
             Cd.ptr = R.code; Cd.si = 1; Cd.sk = k;
             EpiStatsSkip<T> epi{Bt, k, R.stamp, R.step, (T)R.beta, (T)R.wt, (T)R.bdiv, R.replace};
             SplitWs sws{pl->dws + pl->off_split, pl->split_bytes};
-            MODL_TRY((stats_pair<T>(st, Cd, Cd, 0, 0, epi, Xo, Cd, p, k, epi, R.b, sws, &ps.launches)));
+            MODL_TRY((stats_pair<T>(st, Cd, 0, epi, Xo, p, epi, k, R.b, sws, &ps.launches)));
         }
         pl->ride_pending = false;
         if (track_G) {
@@ -1070,10 +982,7 @@ int modl_somf_plan_create(const modl_somf_desc *desc, modl_somf_plan **out) {
     const bool per_sample = desc->G_agg == MODL_AGG_AVERAGE;
     pl->off_F = take(t * k * k * ((per_sample && k <= 512) ? b : 1)); // Cholesky factors (one per sample for G_average_)
     pl->off_Linv = take(t * chol_wide_scratch_elems(desc->k));        // inverted diagonal blocks (wide ridge systems)
-    // split-K partial tiles: the largest split product is max(b, k) x k (Dx, Gram, C increment) with
-    // up to 64 splits; the p x k product (B increment) has >= 512 tiles at p >= 8k and is not split
-    pl->split_bytes = t * std::max(b, k) * k * 64;
-    if (p * k < std::max(b, k) * k * 64) pl->split_bytes = std::max(pl->split_bytes, t * p * k * 8);
+    pl->split_bytes = t * split_scratch_elems(desc->max_batch, desc->k, desc->p);   // split-K partial tiles
     pl->off_split = take(pl->split_bytes);
     pl->du_bytes = dict_update_workspace(desc->dtype, (int64_t)p, desc->k);
     pl->off_du = take(pl->du_bytes);
@@ -1617,6 +1526,14 @@ int modl_somf_partial_fit_chunk(modl_somf_plan *pl, const modl_somf_state *st, c
     pl->ahead = false;
     if (n_done) *n_done = t;
     return MODL_OK;
+}
+
+int modl_somf_product_route(const modl_somf_desc *desc, int section, int b, int64_t s, int has_subset, int has_idx, int64_t ldx,
+                            int64_t x_offset, char *buf, size_t cap) {
+    MODL_TRY(validate_desc(desc));
+    if (x_offset < 0) return MODL_EINVAL;
+    return product_route_name(*desc, section, b, s, has_subset != 0, has_idx != 0, ldx, x_offset,
+                              g_stats_resident.load(std::memory_order_relaxed) != 0, buf, cap);
 }
 
 int modl_somf_full_gram(modl_somf_plan *pl, const void *d_Dt, void *d_G, void *stream) {

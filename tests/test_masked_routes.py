@@ -7,7 +7,7 @@ ROUTES (`GRAM_POINTS`, `STATS_POINTS`, `STEP_POINTS`; `test_route_table` holds e
 the dispatch, and every leaf of the restatement to at least one point; the same table is in DESIGN.md, section 24).  A leaf is a
 branch of the restatement, marked where it is taken by a call of `_leaf`; the list of all leaves is read out of this file's own
 text.  `UNREACHED` lists, with the reason, the leaves that no point takes.  Lines as of this commit, in modl_amd/csrc:
-G = masked_gram.hip, M = masked_stats.hip, S = somf_step.hip.
+G = masked_gram.hip, M = masked_stats.hip; somf_step.hip is cited by function name.
   G:49-53    tile        ntile = ceil(k / 64); ntile (ntile + 1) / 2 workgroups per sample, the upper triangle numbered row by row:
                          `while (tc >= ntile - ta)`; closed form ta = floor((2 ntile + 1 - sqrt((2 ntile + 1)^2 - 8 t)) / 2),
                          tc = t - ta ntile + ta (ta - 1) / 2 + ta (`gram_tile`, checked against the loop for ntile = 1 .. 16);
@@ -25,10 +25,10 @@ G = masked_gram.hip, M = masked_stats.hip, S = somf_step.hip.
   M:85-98    weights    seen = feature_n_iter[e] + c_e (read, never written here), w_e = min(1, w (c_e / b) (n_iter / seen)),
                          alpha = w_e / c_e, beta = 1 - w_e in f64, rounded to the dtype; c_e = 0: the row is not touched
   M:112-121  counts      feature_n_iter[e] += c_e where c_e > 0, count[e] = c_e when given, after the product on the stream
-  S:1204-07  chunk rows  clamp(256 MiB / (k k sizeof T), 1, 4096) - HipBackend.masked_chunk_rows in Python
-  S:1220-23  workspace   crows = min(chunk rows, max_batch); need_F = ridge codes and 128 < k <= 512 (neither the blocked nor the
+  masked_chunk_rows      clamp(256 MiB / (k k sizeof T), 1, 4096) - HipBackend.masked_chunk_rows in Python
+  masked_step            workspace: crows = min(chunk rows, max_batch); need_F = ridge codes and 128 < k <= 512 (neither the blocked nor the
                          one-launch factorisation): a second block of crows k k for the factors
-  S:1257-73  chunks      ceil(b / crows); chunk r0 uses X + r0 ldx, obs + r0 ldo, Dx + r0 k, nobs + r0, xnorm + r0, d_sweeps + r0
+  masked_step            chunks: ceil(b / crows); chunk r0 uses X + r0 ldx, obs + r0 ldo, Dx + r0 k, nobs + r0, xnorm + r0, d_sweeps + r0
                          and d_idx + r0 (or code + r0 k without h_sample_idx)
 
   gram k       (k, p) = (1, 33) (63, 17) (64, 16) (65, 36) (127, 15) (128, 200) (129, 20) (5, 1) (1023, 17) (1024, 36): ntile 1, 1,
@@ -233,7 +233,7 @@ def stats_route(k, p, b, rows, count):
     return SimpleNamespace(s=s, rc=0, R=R, BT=BT, grid=grid, NS=NS)
 
 
-def masked_chunk_rows(k, tsz):                                               # S:1204-1207
+def masked_chunk_rows(k, tsz):                                               # masked_chunk_rows
     r = (256 << 20) // (k * k * tsz)
     return 1 if r < 1 else (4096 if r > 4096 else r)
 
@@ -241,19 +241,19 @@ def masked_chunk_rows(k, tsz):                                               # S
 def step_route(dt, k, b, max_batch, l1_ratio, has_idx):
     tsz = 4 if dt == 'f32' else 8
     full = masked_chunk_rows(k, tsz)
-    crows = min(full, max_batch)                                             # S:1220
+    crows = min(full, max_batch)                                             # masked_step
     s = (_leaf('step/crows=chunk_rows') if crows == full else _leaf('step/crows=max_batch')) + '%d/' % crows
-    # need_F (S:1221) as far as the workspace needs it: ridge codes whose systems take neither the blocked factorisation
+    # need_F (masked_step) as far as the workspace needs it: ridge codes whose systems take neither the blocked factorisation
     # (chol_blocked, per-sample matrices: k > 512) nor the one-launch one (ridge_small_applies: k <= 128 in both types)
     need_F = l1_ratio == 0 and not k > 512 and not k <= 128
     s += (_leaf('step/ws2') if need_F else _leaf('step/ws1')) + '/'
-    chunks = cdiv(b, crows)                                                  # S:1257
+    chunks = cdiv(b, crows)                                                  # masked_step's chunk loop
     s += (_leaf('step/chunks') if chunks > 1 else _leaf('step/one_chunk')) + '%d/' % chunks
     if need_F and chunks > 1:
         s += _leaf('step/chunks+ws2') + '/'
-    s += (_leaf('step/xnorm') if l1_ratio != 0 else _leaf('step/ridge')) + '/'           # S:1256
-    s += _leaf('step/idx') if has_idx else _leaf('step/code+r0k')                          # S:1270
-    ws = (2 if need_F else 1) * cdiv(tsz * crows * k * k, 256) * 256 + cdiv(4 * max_batch, 256) * 256      # S:1222-1223
+    s += (_leaf('step/xnorm') if l1_ratio != 0 else _leaf('step/ridge')) + '/'
+    s += _leaf('step/idx') if has_idx else _leaf('step/code+r0k')
+    ws = (2 if need_F else 1) * cdiv(tsz * crows * k * k, 256) * 256 + cdiv(4 * max_batch, 256) * 256      # masked_step
     return SimpleNamespace(s=s, crows=crows, chunks=chunks, ws=ws, ranges=[(r0, min(crows, b - r0)) for r0 in range(0, b, crows)])
 
 

@@ -25,37 +25,38 @@ ROUTES (`ROUTES`; `test_route_table` holds every point to `expected_route`, a re
 the restated cascade to at least one point; the same table is in DESIGN.md, section 22).  A leaf is a branch of the
 restatement, marked where it is taken by a call of `_leaf`; the list of all leaves is read out of this file's own text, so a
 branch cannot be written down and left out.  A probe vouches only for the section whose result it judges: the statistics
-section of an S-code point does not count.  `UNREACHED` lists, with the reason, the branches that no point takes.  Lines as of
-this commit, in modl_amd/csrc: S = somf_step.hip, D = gemm_dense.hpp, G = gemm.hpp, W = gemm_wide.hpp, R = gemm_resident.hpp,
-B = bcd.hip.
-  D:443-481 plan_dense   operand misaligned = base % 16 bytes or leading stride % (16 / sizeof T) (D:450-453); misaligned and
-                         M N K < 2^22 -> not ok, the gather kernel (D:460); tiles bm x bn, BK = 32 (f32) / 16 (f64);
+section of an S-code point does not count.  `UNREACHED` lists, with the reason, the branches that no point takes.  The restatement
+is held, whole string by whole string, against the library's own answer (modl_somf_product_route: the planners of gemm_plan.hpp and
+the three route functions of step_products.hip, which somf_step.hip and bcd.hip launch from), at every point and on both sides of
+every numeric boundary (`test_route_table`, `test_route_boundaries`), on the CPU.  Functions are cited by name, in modl_amd/csrc.
+  plan_dense_sizes       operand misaligned = base % 16 bytes or leading stride % (16 / sizeof T) (dense_unaligned); misaligned and
+                         M N K < 2^22 -> not ok, the gather kernel; tiles bm x bn, BK = 32 (f32) / 16 (f64);
                          splits = min(target / tiles, max(1, K / (4 BK)), max_splits, scratch / (M N)) when tiles < target and
                          there is scratch; kps = ceil(ceil(K / splits) / BK) BK, splits = ceil(K / kps); sym = same operand
-                         twice, square, and splits > 1: tm (tm + 1) / 2 tiles, the reduce mirrors them (D:463-479, 553-577)
-  D:398-413 tile_auto    paired launches only: the resident-K tile when sizeof(T) == 4, tiles <= 64 x 64 and the split's
-                         length <= 8 BK, else the pipelined tile - decided split by split (D:405-406), so a short last split
+                         twice, square, and splits > 1: tm (tm + 1) / 2 tiles, the reduce mirrors them (gemm_reduce_pair_kernel)
+  dense_tile_of          paired launches only: the resident-K tile when sizeof(T) == 4, tiles <= 64 x 64 and the split's
+                         length <= 8 BK, else the pipelined tile - decided split by split (gemm_dense_tile_auto), so a short last split
                          of a long contraction takes the resident-K tile next to pipelined ones ("pipe+rk_last");
-                         launch_gemm_dense's own kernel is always pipelined (D:415-423)
-  D:70-101  TileLoader   a tile inside an aligned operand by 16-byte loads, every other (edge, K tail, misaligned operand)
-                         element by element, a lane outside the operand from element [0, 0] (D:97), zeros selected afterwards
-  G:326-370 launch_gemm  tall 128 x 32 (BK 32) when N <= 32, big 128 x 128 when ceil(M/128) ceil(N/128) >= 512, else small
+                         launch_gemm_dense's own kernel is always pipelined (gemm_dense_kernel)
+  TileLoader             a tile inside an aligned operand by 16-byte loads, every other (edge, K tail, misaligned operand)
+                         element by element, a lane outside the operand from element [0, 0], zeros selected afterwards
+  plan_gather            tall 128 x 32 (BK 32) when N <= 32, big 128 x 128 when ceil(M/128) ceil(N/128) >= 512, else small
                          64 x 64 (BK 16); splits = min(target / tiles, max(1, K / 128), max_splits, scratch / (M N)); tall tiles at
-                         least half full, no gather on K: "dense" staging from clamped coordinates (G:212-214, 135-161)
-  D:644-651 plan_stats   f32, 32 x 32 tiles of 16x16x4, K <= 256, no split (resident-K tile, 4 K-tiles of 64)
-  W:46-58   plan_wide    16-byte aligned operands, M, N, leading strides % 4 == 0, K <= 256
-  S:574-625 stats_pair   f32: resident (plan_stats(C) ok, rows >= 4096, k <= 256, b % 4 == 0, switch on, plan_wide ok; the
+                         least half full, no gather on K: "dense" staging from clamped coordinates (gemm_kernel, stage_tile)
+  plan_stats_ok          f32, 32 x 32 tiles of 16x16x4, K <= 256, no split (resident-K tile, 4 K-tiles of 64)
+  plan_wide_ok           16-byte aligned operands, M, N, leading strides % 4 == 0, K <= 256
+  stats_route            f32: resident (plan_stats(C) ok, rows >= 4096, k <= 256, b % 4 == 0, switch on, plan_wide ok; the
                          epilogue by 16 bytes for EpiStats, element by element for the row-indirected EpiStatsRows), else
                          wide pair (ceil(rows / 64) >= 1024, plan_wide ok: 32 features x 256 atoms per tile), else stats pair
                          (both plan_stats ok); any type: dense pair (both plan_dense ok, no split), else one launch each
                          (launch_gemm_dense: dense kernel, or gather kernel below 2^22)
-  S:682-776 phase1 code  need_sub = subset and not (G_agg == Dx_agg == full): prep_kernel gathers Ds = Dt[subset], Xs = X[:, subset]
+  code_products_route    need_sub = subset and not (G_agg == Dx_agg == full): prep_kernel gathers Ds = Dt[subset], Xs = X[:, subset]
                          (s_pad = ceil(s / 4) 4 columns); paired = G wanted and both plan_dense ok with 256 workgroups and
                          half the scratch each, the Gram symmetric; else one launch_gemm_dense each
-  S:701     ride         a proper subset, Dx_agg != full, no MODL_FLAG_NO_RIDER, ceil(p / 64) < 1024: C_ and the sampled rows
+  rider_route            a proper subset, Dx_agg != full, no MODL_FLAG_NO_RIDER, ceil(p / 64) < 1024: C_ and the sampled rows
                          of B_ (EpiStatsRows) now, the others under the dictionary update
-  B:plan_ride rider      f32 and k <= 512: wide tiles 32 x 128 when p >= 2048 and plan_wide ok, else the 32 x 32 tiles of
-                         plan_stats, shared out over the carrier launches; otherwise completed after the update (S:929-937)
+                         the update's launches carry it (du_carries_riders: f32, k <= 512, no l1, not sgd): wide tiles 32 x 128 when p >= 2048 and plan_wide ok, else the 32 x 32 tiles of
+                         plan_stats, shared out over the carrier launches; otherwise completed after the update (phase2)
                          through stats_pair with EpiStatsSkip
 The launches of the code-product and statistics sections (modl_somf_prof_get: code_gemm, stats_gemm) are asserted against the
 restated count on every S point: paired or not, split or not.  A rider that the dictionary update did not consume is completed
@@ -87,7 +88,7 @@ launches and are not counted: that they ran is seen in the rows of B_, which til
   S-stats sgd; three steps      p 600 s 200 (and p 2400 s 800, the wide rider), overlapping subsets, judged after each step
 Not reachable from the ABI: the big configuration in f64 (k > 2048 would need 8 k^2 64 bytes of scratch - run in f32 only, as the
 issue lists it); the "dense" staging of the A operand in probe G (M = N <= 32 there; probe T's b = 200 covers it).
-Not reached by these probes (`UNREACHED`): a subset with Dx_agg = full and G_agg != full (S:701 then denies the rider); the
+Not reached by these probes (`UNREACHED`): a subset with Dx_agg = full and G_agg != full (rider_route then denies the rider); the
 probes set G_agg = Dx_agg, which their formulas assume.
 
 SCENES
@@ -154,10 +155,11 @@ import pytest
 DT = {'f32': np.float32, 'f64': np.float64}
 LD = np.longdouble
 TSZ = {'f32': 4, 'f64': 8}
-VN = {'f32': 4, 'f64': 2}                      # elements of a 16-byte vector (D:52-54)
-BKD = {'f32': 32, 'f64': 16}                   # K-tile of the dense kernels (D:418)
+VN = {'f32': 4, 'f64': 2}                      # elements of a 16-byte vector (Vec4<T>::N)
+BKD = {'f32': 32, 'f64': 16}                   # K-tile of the dense kernels (dense_bk)
 FILL = 7.5
 NO_RIDER = 1                                   # MODL_FLAG_NO_RIDER
+GEMM_STAMPS = 2                                # MODL_FLAG_GEMM_STAMPS
 
 
 def cdiv(a, b):
@@ -181,24 +183,24 @@ def all_leaves():
 
 
 # ---------------------------------------------------------------------------------------------------- the dispatch, restated
-def split_scratch_elems(mb, k, p):             # S:1075-1076
+def split_scratch_elems(mb, k, p):             # split_scratch_elems
     e = max(mb, k) * k * 64
     if p * k < e:
         e = max(e, p * k * 8)
     return e
 
 
-def misaligned(dt, ld, base=0):                # D:450-453 (base: offset of the operand in elements from an aligned address)
+def misaligned(dt, ld, base=0):                # dense_unaligned (base: offset of the operand in elements from an aligned address)
     return (base * TSZ[dt]) % 16 != 0 or ld % VN[dt] != 0
 
 
 def plan_dense(dt, unal_a, unal_b, M, N, K, ws, target=512, max_splits=64, bm=64, bn=64, symmetric=False):
-    """D:443-481.  ws: elements of split-K scratch (0: none)."""
+    """plan_dense_sizes.  ws: elements of split-K scratch (0: none)."""
     P = SimpleNamespace(ok=K > 0 and M > 0 and N > 0, unal_a=unal_a, unal_b=unal_b, M=M, N=N, K=K, splits=1, kps=0, sym=0, tm=0,
                         tn=0, bm=bm, bn=bn)
     if not P.ok:
         return P
-    if (unal_a or unal_b) and M * N * K < 1 << 22:                       # D:460
+    if (unal_a or unal_b) and M * N * K < 1 << 22:
         _leaf('plan_dense: misaligned below 2^22, not ok')
         P.ok = False
         return P
@@ -208,13 +210,13 @@ def plan_dense(dt, unal_a, unal_b, M, N, K, ws, target=512, max_splits=64, bm=64
     sym = symmetric and M == N and bm == bn
     ntile = tm * (tm + 1) // 2 if sym else tm * tn
     splits = 1
-    if ntile < target and max_splits > 1 and ws > 0:                     # D:466-474
+    if ntile < target and max_splits > 1 and ws > 0:
         splits = min(target // ntile, max(1, K // (4 * BK)), max_splits, ws // (M * N))
         splits = max(splits, 1)
     P.kps = cdiv(cdiv(K, splits), BK) * BK
     P.splits = cdiv(K, P.kps)
     P.tm, P.tn = tm, tn
-    P.sym = 1 if sym and P.splits > 1 else 0                             # D:479
+    P.sym = 1 if sym and P.splits > 1 else 0
     _leaf('plan_dense: split-K') if P.splits > 1 else _leaf('plan_dense: one split')
     if sym:
         _leaf('plan_dense: symmetric, upper tiles mirrored') if P.sym else _leaf('plan_dense: symmetric but unsplit, every tile computed')
@@ -222,7 +224,7 @@ def plan_dense(dt, unal_a, unal_b, M, N, K, ws, target=512, max_splits=64, bm=64
     return P
 
 
-def dense_tile(dt, P, paired):                 # D:398-413; launch_gemm_dense's kernel: D:415-423
+def dense_tile(dt, P, paired):                 # dense_tile_of; launch_gemm_dense's own kernel is pipelined
     if not paired:
         _leaf('tile: pipelined (a launch of its own)')
         return 'pipe'
@@ -233,7 +235,7 @@ def dense_tile(dt, P, paired):                 # D:398-413; launch_gemm_dense's 
     if P.kps <= 8 * BKD[dt]:
         _leaf('tile: resident-K (paired, f32, splits of at most 8 BK)')
         return 'rk'
-    if P.splits > 1 and last <= 8 * BKD[dt]:                              # D:405-406 decide split by split
+    if P.splits > 1 and last <= 8 * BKD[dt]:                              # gemm_dense_tile_auto decides split by split
         _leaf('tile: pipelined, the short last split resident-K (paired, f32)')
         return 'pipe+rk_last'
     _leaf('tile: pipelined (paired, f32, every split longer than 8 BK)')
@@ -259,7 +261,7 @@ def dense_str(dt, P, paired):
 
 
 def launch_gemm(dt, M, N, K, ws, target=512, max_splits=64, gather_k=False):
-    """G:326-370 and the staging predicate of gemm_kernel (G:212-214): (route string, launches, splits)."""
+    """plan_gather and the staging predicate of gemm_kernel: (route string, launches, splits)."""
     if N <= 32:
         cfg, bm, bn, bk = 'tall', 128, 32, 32
     elif cdiv(M, 128) * cdiv(N, 128) >= 512:
@@ -294,7 +296,7 @@ def launch_gemm(dt, M, N, K, ws, target=512, max_splits=64, gather_k=False):
 
 
 def launch_gemm_dense(dt, unal_a, unal_b, M, N, K, ws, target=512, max_splits=64):
-    """D:666-697: (route string, launches, splits)"""
+    """launch_gemm_dense / product_launch: (route string, launches, splits)"""
     P = plan_dense(dt, unal_a, unal_b, M, N, K, ws, target, max_splits)
     if not P.ok:
         _leaf('launch_gemm_dense: gather kernel')
@@ -303,37 +305,37 @@ def launch_gemm_dense(dt, unal_a, unal_b, M, N, K, ws, target=512, max_splits=64
     return dense_str(dt, P, False), 1 + (P.splits > 1), P.splits
 
 
-def plan_stats_ok(dt, unal_a, unal_b, M, N, K):                           # D:644-651 (both operands row-contiguous here)
+def plan_stats_ok(dt, unal_a, unal_b, M, N, K):                           # plan_stats_ok (both operands row-contiguous here)
     if M <= 0 or N <= 0:
         return True
     return plan_dense(dt, unal_a, unal_b, M, N, K, 0, 512, 1, 32, 32).ok and K <= 256
 
 
-def plan_wide_ok(M, N, K, ld_a, ld_b, base_a=0):                          # W:46-58
+def plan_wide_ok(M, N, K, ld_a, ld_b, base_a=0):                          # plan_wide_ok
     return M > 0 and N > 0 and 0 < K <= 256 and M % 4 == 0 and N % 4 == 0 and ld_a % 4 == 0 and ld_b % 4 == 0 and \
         (base_a * 4) % 16 == 0
 
 
-def stats_pair(dt, k, M1, ld1, base1, K, ws, epi='stats', M0=None, resident=True):
-    """S:574-625: the products code^T code (M0 = k rows; 0: none) and X^T code (M1 rows of leading stride ld1) -> (route, launches)"""
+def stats_pair(dt, k, M1, ld1, base1, K, ws, epi='stats', M0=None, resident=True, stamps=False):
+    """stats_route: the products code^T code (M0 = k rows; 0: none) and X^T code (M1 rows of leading stride ld1) -> (route, launches)"""
     M0 = k if M0 is None else M0
     unal_c, unal_x = misaligned(dt, k), misaligned(dt, ld1, base1)
     if dt == 'f32':
         p0 = plan_stats_ok(dt, unal_c, unal_c, M0, k, K)
-        if p0 and M1 >= 4096 and k <= 256 and K % 4 == 0 and resident and plan_wide_ok(M1, k, K, ld1, k, base1):   # S:590-601
+        if p0 and M1 >= 4096 and k <= 256 and K % 4 == 0 and not stamps and resident and plan_wide_ok(M1, k, K, ld1, k, base1):
             _leaf('resident: vec4 epilogue') if epi == 'stats' else _leaf('resident: scalar row-indirected epilogue')
             return 'resident16/%s' % ('vec4' if epi == 'stats' else 'scalar'), 1
-        if p0 and cdiv(M1, 64) >= 1024 and plan_wide_ok(M1, k, K, ld1, k, base1):                                     # S:603-606
+        if p0 and cdiv(M1, 64) >= 1024 and not stamps and plan_wide_ok(M1, k, K, ld1, k, base1):
             _leaf('wide pair: one atom chunk') if k <= 256 else _leaf('wide pair: several atom chunks')
             return 'wide32/c%d' % cdiv(k, 256), 1
-        if p0 and plan_stats_ok(dt, unal_x, unal_c, M1, k, K):                                                        # S:607-611
+        if p0 and plan_stats_ok(dt, unal_x, unal_c, M1, k, K):
             _leaf('stats pair: misaligned') if unal_x or unal_c else _leaf('stats pair: aligned')
             return 'stats32/%s/t%dx%d' % ('unal' if unal_x or unal_c else 'al', cdiv(M1, 32), cdiv(k, 32)), 1
     ok0 = True
     if M0 > 0:
         ok0 = plan_dense(dt, unal_c, unal_c, M0, k, K, 0).ok
     P1 = plan_dense(dt, unal_x, unal_c, M1, k, K, 0, 512, 1, 64, 64)
-    if ok0 and P1.ok:                                                                                                 # S:621-622
+    if ok0 and P1.ok:
         _leaf('dense pair: C and B') if M0 > 0 else _leaf('dense pair: B alone (after the update)')
         return 'densepair/%s/%s' % ('unal' if unal_x or unal_c else 'al', dense_tile(dt, P1, True)), 1
     n, parts = 0, []
@@ -347,21 +349,22 @@ def stats_pair(dt, k, M1, ld1, base1, K, ws, epi='stats', M0=None, resident=True
     return 'each/' + '/'.join(parts), n + l
 
 
-def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, resident=True, has_idx=True, judged=('code', 'stats')):
-    """S:631-843 for ridge codes (no row norms, codes solved in place): the code-product and statistics sections.  Only the
+def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, resident=True, has_idx=True, judged=('code', 'stats'),
+           optimizer='variational'):
+    """code_products_route and phase1's statistics section for ridge codes (no row norms, codes solved in place): the code-product and statistics sections.  Only the
     branches of the sections in `judged` count as taken (HIT): a probe vouches for the section whose result it judges."""
     taken, mine = set(HIT), {}
     HIT.clear()
     ws = split_scratch_elems(mb, k, p)
     full = G_agg == 'full' and Dx_agg == 'full'
-    need_sub = subset and not full                                           # S:682
+    need_sub = subset and not full
     s_pad = cdiv(s, 4) * 4
     n = 0
-    if need_sub and s > 0:                                                   # S:710-715 (n_norm = n_code = 0 for ridge codes)
+    if need_sub and s > 0:                                                   # (n_norm = n_code = 0 for ridge codes)
         _leaf('phase1: prep_kernel gathers Ds and Xs')
         n += 1
     unal_d = misaligned(dt, k)
-    if Dx_agg == 'full':                                                     # S:719-727
+    if Dx_agg == 'full':
         _leaf('phase1: Dx over all of p')
         unal_a, Kdim = misaligned(dt, ldx, xbase), p
     elif need_sub:
@@ -371,7 +374,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
         _leaf('phase1: Dx over X as given (no subset)')
         unal_a, Kdim = misaligned(dt, ldx, xbase), s
     want_G, paired = G_agg != 'full', False
-    if want_G:                                                               # S:733-759
+    if want_G:
         half = ws // 2
         PG = plan_dense(dt, unal_d, unal_d, k, k, s, ws - half, 256, 64, 64, 64, True)
         PD = plan_dense(dt, unal_a, unal_d, b, k, Kdim, half, 256)
@@ -381,7 +384,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
             code = 'pair/Dx[%s]/G[%s]' % (dense_str(dt, PD, True), dense_str(dt, PG, True))
             n += 1 + (PD.splits > 1 or PG.splits > 1)
             splits = (PD.splits, PG.splits)
-    if not paired:                                                           # S:760-772
+    if not paired:
         sd, ld, spd = launch_gemm_dense(dt, unal_a, unal_d, b, k, Kdim, ws)
         code, splits = 'each/Dx[%s]' % sd, (spd, 1)
         n += ld
@@ -391,7 +394,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
             code += '/G[%s]' % sg
             n += lg
             splits = (spd, spg)
-    if G_agg == 'average':                                                   # S:773-776
+    if G_agg == 'average':
         _leaf('phase1: G_average rows updated')
         n += 1
     if need_sub:
@@ -399,10 +402,10 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
     out = SimpleNamespace(code=code, code_launches=n, splits=splits)
     mine['code'] = set(HIT)
     HIT.clear()
-    # ---- statistics (S:794-841)
+    # ---- statistics (phase1, rider_route)
     m = 1 if has_idx else 0                                                  # the gather of code_[idx] (ridge: not solved on compact rows)
     proper = need_sub and 0 < s < p
-    ride = proper and Dx_agg != 'full' and not (flags & NO_RIDER) and cdiv(p, 64) < 1024      # S:701
+    ride = proper and Dx_agg != 'full' and not (flags & NO_RIDER) and cdiv(p, 64) < 1024      # rider_route
     if not proper:
         _leaf('no rider: no proper subset')
     elif Dx_agg == 'full':
@@ -412,16 +415,18 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
     elif not ride:
         _leaf('no rider: p of 65472 or more')
     if ride:
-        r, l = stats_pair(dt, k, s, s_pad, 0, b, ws, 'rows', resident=resident)
-        fused = dt == 'f32' and k <= 512                                     # B:du_route
+        r, l = stats_pair(dt, k, s, s_pad, 0, b, ws, 'rows', resident=resident, stamps=bool(flags & GEMM_STAMPS))   # (the head launch alone)
+        fused = dt == 'f32' and k <= 512 and optimizer != 'sgd'              # du_carries_riders (the probes' updates have no l1 term)
+        if dt == 'f32' and k <= 512 and not fused:
+            _leaf('rider: the sgd update carries none')
         unal_c, unal_x = misaligned(dt, k), misaligned(dt, ldx, xbase)
-        if fused and p >= 2048 and plan_wide_ok(p, k, b, ldx, k, xbase):     # B:plan_ride
+        if fused and p >= 2048 and plan_wide_ok(p, k, b, ldx, k, xbase):     # rider_route
             _leaf('rider: wide128')
             rider = 'wide128'
-        elif fused and plan_stats_ok(dt, unal_x, unal_c, p, k, b):           # B:plan_ride
+        elif fused and plan_stats_ok(dt, unal_x, unal_c, p, k, b):           # rider_route
             _leaf('rider: stats32 unal') if unal_x or unal_c else _leaf('rider: stats32 al')
             rider = 'stats32/' + ('unal' if unal_x or unal_c else 'al')
-        else:                                                                # S:929-937
+        else:                                                                # phase2 completes it
             _leaf('rider: completed after the update')
             rider = 'after[%s]' % stats_pair(dt, k, p, ldx, xbase, b, ws, 'skip', M0=0, resident=resident)[0]
         out.stats = r + '/ride:' + rider
@@ -435,7 +440,7 @@ def phase1(dt, b, k, p, s, subset, G_agg, Dx_agg, ldx, mb, flags=0, xbase=0, res
     return out
 
 
-def partial_gram(dt, k, s, mb, p):             # S:897-902, 939-942 -> gram_of_rows (S:529-535) with the subset on K
+def partial_gram(dt, k, s, mb, p):             # phase2 -> gram_of_rows with the subset on K
     return launch_gemm(dt, k, k, s, split_scratch_elems(mb, k, p), gather_k=True)
 
 
@@ -446,29 +451,82 @@ def expected_route(probe, dt, **sh):
         ldx, base = sh.get('ldx', p), sh.get('base', 0)
         ws = split_scratch_elems(mb, k, p)
         chunks = []
-        for r0 in range(0, n, mb):                                           # S:976-986
+        for r0 in range(0, n, mb):                                           # transform_chunks
             b = min(mb, n - r0)
             _leaf('transform: a full chunk') if b == mb else _leaf('transform: a short last chunk')
             chunks.append(launch_gemm_dense(dt, misaligned(dt, ldx, base + r0 * ldx), misaligned(dt, k), b, k, p, ws)[0])
         return 'T:' + '|'.join(chunks)
     if probe == 'G':
         k, p = sh['k'], sh['p']
-        return 'G:' + launch_gemm(dt, k, k, p, split_scratch_elems(sh.get('mb', 64), k, p))[0]      # S:1622-1634
+        return 'G:' + launch_gemm(dt, k, k, p, split_scratch_elems(sh.get('mb', 64), k, p))[0]      # modl_somf_full_gram
     agg = sh.get('agg', 'masked')
     r = phase1(dt, sh['b'], sh['k'], sh['p'], sh.get('s', sh['p']), sh.get('s') is not None, agg, agg, sh.get('ldx', sh['p']),
-               sh['b'], sh.get('flags', 0), resident=sh.get('resident', True), judged=('code',) if probe == 'S-code' else ('stats',))
+               sh['b'], sh.get('flags', 0), resident=sh.get('resident', True), judged=('code',) if probe == 'S-code' else ('stats',),
+               optimizer=sh.get('optimizer', 'variational'))
     if probe == 'S-code':
-        tail = '/partialG[%s]' % partial_gram(dt, sh['k'], sh['s'], sh['b'], sh['p'])[0] if agg == 'full' else ''
+        tail = ''
+        if agg == 'full' and 2 * sh.get('s', sh['p']) < sh['p']:             # phase2, gram_is_partial: s < p / 2
+            _leaf('phase2: G_ -= and += the Gram of the sampled rows')
+            tail = '/partialG[%s]' % partial_gram(dt, sh['k'], sh['s'], sh['b'], sh['p'])[0]
+        elif agg == 'full':
+            _leaf('phase2: G_ recomputed over all of p')
+            tail = '/fullG[%s]' % launch_gemm(dt, sh['k'], sh['k'], sh['p'], split_scratch_elems(sh['b'], sh['k'], sh['p']))[0]
         return 'S-code:' + r.code + tail
     return 'S-stats:' + r.stats
+
+
+SECTION = {'T': 0, 'G': 1, 'S-code': 2, 'S-stats': 3}                        # MODL_ROUTE_*
+ROUTE_MAX = 512                                                             # MODL_PRODUCT_ROUTE_MAX
+
+
+def product_route(dt, section, k, p, n, mb, b, s=None, ldx=None, base=0, agg='masked', optimizer='variational', flags=0, has_idx=True,
+                  cap=ROUTE_MAX, rc=False):
+    """modl_somf_product_route for a plan of `Plan`'s descriptor: the library's own answer, no plan and no device involved"""
+    import ctypes as C
+    from modl_amd._lib import lib, check, SomfDesc, AGG, OPT
+    d = SomfDesc()
+    d.dtype, d.k, d.p, d.n_samples = (0 if dt == 'f32' else 1), k, p, n
+    d.G_agg = d.Dx_agg = AGG[agg]
+    d.optimizer, d.code_pos, d.comp_pos, d.max_iter = OPT[optimizer], 0, 0, 100
+    d.code_alpha, d.code_l1_ratio, d.comp_l1_ratio, d.tol, d.step_size = 1.0, 0.0, 0.0, 1e-3, 1e-3
+    d.max_batch, d.flags = mb, flags
+    buf = C.create_string_buffer(max(cap, 1))
+    code = lib.modl_somf_product_route(C.byref(d), section, b, p if s is None else s, int(s is not None), int(has_idx), p if ldx is None else ldx,
+                                       base, buf, cap)
+    if rc:
+        return code
+    check(code, 'modl_somf_product_route')
+    return buf.value.decode()
+
+
+def _resident(on):
+    from modl_amd._lib import lib, check, DEBUG_STATS_RESIDENT
+    check(lib.modl_debug_set(DEBUG_STATS_RESIDENT, 1 if on else 0))
+
+
+def library_route(probe, dt, **sh):
+    """the same string as `expected_route`, from the library (the transform: one call per chunk)"""
+    k, p = sh['k'], sh['p']
+    if probe == 'T':
+        n, mb, ldx, base = sh['b'], sh.get('mb', sh['b']), sh.get('ldx', p), sh.get('base', 0)
+        return 'T:' + '|'.join(product_route(dt, 0, k, p, n, mb, min(mb, n - r0), ldx=ldx, base=base + r0 * ldx) for r0 in range(0, n, mb))
+    if probe == 'G':
+        return 'G:' + product_route(dt, 1, k, p, 1, sh.get('mb', 64), 1)
+    try:
+        _resident(sh.get('resident', True))
+        return probe + ':' + product_route(dt, SECTION[probe], k, p, sh['b'] + 3, sh['b'], sh['b'], sh.get('s'), sh.get('ldx'), 0,
+                                           sh.get('agg', 'masked'), sh.get('optimizer', 'variational'), sh.get('flags', 0))
+    finally:
+        _resident(True)
 
 
 # ---------------------------------------------------------------------------------------------------- the table
 ROUTES = []
 
 
-def _route(probe, name, want, dts=('f32',), rep=False, **sh):
-    ROUTES.append(SimpleNamespace(probe=probe, name='%s-%s' % (probe, name), want=want, dts=dts, rep=rep, sh=sh))
+def _route(probe, name, want, dts=('f32',), rep=False, gpu=True, **sh):
+    """gpu=False: a point of the route table alone (`test_route_table`); no probe on the device judges it"""
+    ROUTES.append(SimpleNamespace(probe=probe, name='%s-%s' % (probe, name), want=want, dts=dts, rep=rep, gpu=gpu, sh=sh))
 
 
 BOTH = ('f32', 'f64')
@@ -508,6 +566,10 @@ _route('S-code', 'reduction1', ('pair/Dx[dense/unalA/',), agg='average', b=128, 
 _route('S-code', 'full_split', ('each/Dx[', 'partialG[gather/small/t2x2/s2/kps160/last140/Ag/Bg]'), dts=BOTH, rep=True, agg='full',
        b=16, k=70, p=900, s=300)
 _route('S-code', 'full_tall', ('each/Dx[', 'partialG[gather/tall/t1x1/s1/kps64/last64/Ag/Bg]'), dts=BOTH, agg='full', b=16, k=24, p=200, s=64)
+# s = p / 2 is no longer "fewer than half": G_ is recomputed over all of p (the judge of S-code/full assumes the partial passes)
+_route('S-code', 'full_regram', ('each/Dx[', 'fullG[gather/tall/t1x1/s1/kps224/last200/Ag/Bd]'), dts=BOTH, gpu=False, agg='full', b=16, k=24, p=200,
+       s=100)
+_route('S-stats', 'sgd_ride_after', ('stats32/al/t7x2/ride:after[stats32/al/t19x2]',), gpu=False, b=64, k=64, p=600, s=200, optimizer='sgd')
 for _b, _k in ((64, 64), (50, 64), (256, 64), (64, 68)):
     _route('S-stats', 'tiles32_b%d_k%d' % (_b, _k), ('stats32/al/t10x%d/noride' % cdiv(_k, 32),), rep=(_b, _k) == (50, 64), b=_b, k=_k, p=300)
 _route('S-stats', 'densepair_b260', ('densepair/al/pipe/noride',), rep=True, b=260, k=64, p=300)
@@ -536,9 +598,9 @@ _route('S-stats', 'sgd', ('stats32/al/t10x2/noride',), b=64, k=64, p=300, optimi
 _route('S-stats', 'three_steps', ('stats32/al/t7x2/ride:stats32/al',), b=64, k=64, p=600, s=200, steps=3)
 _route('S-stats', 'three_steps_wide', ('stats32/al/t25x2/ride:wide128',), b=64, k=64, p=2400, s=800, steps=3)
 ROUTE_BY_KEY = {(r.name, dt): r for r in ROUTES for dt in r.dts}
-POINTS = sorted(ROUTE_BY_KEY)
+POINTS = sorted(key for key, r in ROUTE_BY_KEY.items() if r.gpu)
 LEAVES = ('dense/al/', 'dense/unalA/', 'dense/unalB/', '/interior/', '/edge/', 'gather/tall/', 'gather/small/', 'gather/big/', '/Add/', '/Adg/', '/Ag/Bg',
-          '/Ag/Bd', '/rk', '/pipe', '/sym1/', '/sym0', '/rk/sym1', '/rk/sym0', '/pipe+rk_last/sym1', 'last272/pipe/sym1', 'pair/Dx[', 'each/Dx[', 'prep+', 'partialG[gather/small/', 'partialG[gather/tall/',
+          '/Ag/Bd', '/rk', '/pipe', '/sym1/', '/sym0', '/rk/sym1', '/rk/sym0', '/pipe+rk_last/sym1', 'last272/pipe/sym1', 'pair/Dx[', 'each/Dx[', 'prep+', 'partialG[gather/small/', 'partialG[gather/tall/', 'fullG[gather/tall/',
           'resident16/vec4', 'resident16/scalar', 'wide32/c1', 'wide32/c2', 'stats32/al/', 'stats32/unal/', 'densepair/al/pipe', 'each/C[gather/',
           '/B[gather/', '/B[dense/unalB/', '/noride', 'ride:stats32/al', 'ride:stats32/unal', 'ride:wide128', 'ride:after[densepair/')
 
@@ -550,7 +612,7 @@ UNREACHED = {
 
 
 def route_of(r, dt):
-    sh = {a: v for a, v in r.sh.items() if a not in ('optimizer', 'steps')}
+    sh = {a: v for a, v in r.sh.items() if a != 'steps'}
     return expected_route(r.probe, dt, **sh)
 
 
@@ -763,7 +825,7 @@ def tiled_product(A, B, K, bm, bn, bk, kps, sym, dt, out, mut=(), rmw=None, fetc
     with zeros SELECTED outside the operand, partial sums added in split order, tiles below the diagonal mirrored (sym).  A, B
     hold columns behind K (what the memory behind an operand row holds).  rmw = (beta, alpha): out = beta out + alpha v.
     fetch: what a lane outside the operand loads before the select - 'clamp' the nearest element inside or behind the row (the
-    gather kernel's clamped coordinates), 'base' element [0, 0] of the operand (the dense TileLoader, D:97)."""
+    gather kernel's clamped coordinates), 'base' element [0, 0] of the operand (the dense TileLoader)."""
     T = DT[dt]
     M, N = A.shape[0], B.shape[0]
     splits = cdiv(K, kps)
@@ -850,13 +912,19 @@ def stats_step(Bt, X, code, w, subset, stamp, step, dt, mut=()):
 
 # ---------------------------------------------------------------------------------------------------- CPU tests
 def test_route_table():
-    """ROUTES names what the restated dispatch does at every point, and every leaf of the cascade is hit."""
+    """ROUTES names what the restated dispatch does at every point, the library's own route (modl_somf_product_route, no device)
+    is that string at every point, and every leaf of the cascade is hit."""
     got = {}
     HIT.clear()
+    longest = 0
     for (name, dt), r in ROUTE_BY_KEY.items():
         s = got[name, dt] = route_of(r, dt)
         for want in r.want:
             assert want in s, (name, dt, want, s)
+        lib_s = library_route(r.probe, dt, **{a: v for a, v in r.sh.items() if a != 'steps'})
+        assert lib_s == s, ('the library routes this point otherwise', name, dt, lib_s, s)
+        longest = max([longest] + [len(part) for part in s.split(':', 1)[1].split('|')])
+    assert longest + 1 <= ROUTE_MAX, ('MODL_PRODUCT_ROUTE_MAX does not hold the longest route of the table', longest)
     hit = set(HIT)
     # every branch that the restatement marks with _leaf(...) - read from this file's text, not from a list kept by hand - is
     # taken by a point, but for those listed, with the reason, in UNREACHED
@@ -890,8 +958,101 @@ def test_route_table():
     assert len(ROUTE_BY_KEY) == sum(len(r.dts) for r in ROUTES)
 
 
-K_CODE = {r.sh.get('s', r.sh['p']) for r in ROUTES if r.probe == 'S-code'}          # contraction lengths of the probes
-K_STATS = {r.sh['b'] for r in ROUTES if r.probe == 'S-stats'}
+def test_route_boundaries():
+    """The library against the restatement on both sides of every numeric boundary of the dispatch (pure function calls, no
+    device), and the two sides on different routes where the boundary says so."""
+    def both(probe, dt, starts=None, has=None, **sh):
+        e, g = expected_route(probe, dt, **sh), library_route(probe, dt, **sh)
+        assert g == e, ('the library routes this otherwise', probe, dt, sh, g, e)
+        body = e.split(':', 1)[1]
+        assert starts is None or body.startswith(starts), (probe, dt, sh, e, starts)
+        assert has is None or has in body, (probe, dt, sh, e, has)
+        return body
+    n = 0
+    for dt in BOTH:
+        # misaligned operands: M N K = 2^22 - 1 (3 * 23 * 89 * 683) stays with the gather kernel, 2^22 takes the dense one
+        assert 69 * 89 * 683 == (1 << 22) - 1 and 128 * 128 * 256 == 1 << 22
+        both('T', dt, 'gather/', b=69, k=89, p=683)
+        both('T', dt, 'dense/unalA/', b=128, k=128, p=256, ldx=257)
+        # N = 32 | 33: the tall and the small tiles of the gather kernel
+        both('G', dt, 'gather/tall/', k=32, p=40)
+        both('G', dt, 'gather/small/', k=33, p=40)
+        # a split of 8 BK | 8 BK + 1 (and the short last split of the longer one), paired
+        tile = {'f32': ('/rk/', '/pipe+rk_last/', '/pipe/'), 'f64': ('/pipe/',) * 3}[dt]
+        s8 = 32 * 8 * BKD[dt]                                                # 32 splits (the scratch's bound) of 8 BK
+        both('S-code', dt, has='kps%d/last%d%ssym1' % (8 * BKD[dt], 8 * BKD[dt], tile[0]), agg='average', b=64, k=64, p=2 * s8, s=s8)
+        both('S-code', dt, has='kps%d/last%d%ssym1' % (9 * BKD[dt], 4 * BKD[dt] + 1, tile[1]), agg='average', b=64, k=64, p=2 * s8, s=s8 + 1)
+        both('S-code', dt, has='kps%d/last%d%ssym1' % (9 * BKD[dt], 9 * BKD[dt] - 8, tile[2]), agg='average', b=64, k=64, p=2 * s8,
+             s=30 * 9 * BKD[dt] + 9 * BKD[dt] - 8)                           # (31 splits of 9 BK, the last 8 short of one)
+        # s = p / 2 for G_agg = full: fewer than half the features -> the partial passes
+        both('S-code', dt, has='/partialG[', agg='full', b=16, k=24, p=200, s=99)
+        both('S-code', dt, has='/fullG[', agg='full', b=16, k=24, p=200, s=100)
+        both('S-code', dt, has='/fullG[', agg='full', b=16, k=24, p=200, s=101)
+        both('S-code', dt, has='/partialG[', agg='full', b=16, k=24, p=201, s=100)
+        n += 11
+    # the big tiles of the gather kernel from ceil(M / 128) ceil(N / 128) = 512: 511 | 512 tiles of 128 x 128 in a tall
+    # misaligned product below 2^22 (k = 33: one column tile), as B_ of the statistics and as Dx of a transform chunk
+    assert cdiv(65408, 128) == 511 and cdiv(65409, 128) == 512 and 65409 * 33 < 1 << 22
+    both('S-stats', 'f32', has='/B[gather/small/t1022x1/', b=1, k=33, p=65408)
+    both('S-stats', 'f32', has='/B[gather/big/t512x1/', b=1, k=33, p=65409)
+    both('T', 'f32', 'gather/small/t1022x1/', b=65408, k=33, p=1)
+    both('T', 'f32', 'gather/big/t512x1/', b=65409, k=33, p=1)
+    both('T', 'f64', 'gather/small/t1022x1/', b=65408, k=33, p=1)
+    both('T', 'f64', 'gather/big/t512x1/', b=65409, k=33, p=1)
+    both('G', 'f32', 'gather/small/t44x44/', k=2816, p=24)               # (and square: 22 x 22 | 23 x 23)
+    both('G', 'f32', 'gather/big/t23x23/', k=2817, p=24)
+    st = dict(b=64, k=64, p=300)
+    both('S-stats', 'f32', 'stats32/', **dict(st, b=256))                    # statistics K = b: 256 | 257
+    both('S-stats', 'f32', 'densepair/', **dict(st, b=257))
+    both('S-stats', 'f32', 'stats32/al/', **dict(st, p=4092))                # resident rows: 4096 (4095: also misaligned)
+    both('S-stats', 'f32', 'stats32/unal/', **dict(st, p=4095))
+    both('S-stats', 'f32', 'stats32/al/', **dict(st, p=4095, ldx=4096))
+    both('S-stats', 'f32', 'resident16/', **dict(st, p=4096))
+    both('S-stats', 'f32', 'resident16/', **dict(st, p=4096, k=256))         # resident k: 256 | 260
+    both('S-stats', 'f32', 'stats32/al/', **dict(st, p=4096, k=260))
+    both('S-stats', 'f32', 'resident16/', **dict(st, p=4096, b=20))          # resident K % 4: b = 20 | 22
+    both('S-stats', 'f32', 'stats32/al/', **dict(st, p=4096, b=22))
+    both('S-stats', 'f32', 'resident16/', **dict(st, p=4096, resident=True)) # the resident switch
+    both('S-stats', 'f32', 'stats32/al/', **dict(st, p=4096, resident=False))
+    both('S-stats', 'f32', 'stats32/al/', **dict(st, p=65472, k=260, b=24))  # 1023 | 1024 tiles of 64 features: the wide pair ...
+    both('S-stats', 'f32', 'stats32/unal/', **dict(st, p=65473, k=260, b=24))
+    both('S-stats', 'f32', 'wide32/c2', **dict(st, p=65476, k=260, b=24))
+    both('S-stats', 'f32', has='/ride:wide128', **dict(st, p=65472, s=800))  # ... and the end of the rider
+    both('S-stats', 'f32', has='/noride', **dict(st, p=65473, s=800))
+    both('S-stats', 'f32', has='/noride', **dict(st, p=65476, s=800))
+    both('S-stats', 'f32', has='/ride:stats32/al', **dict(st, p=2044, s=800))          # the rider's tiles: p = 2044 | 2048
+    both('S-stats', 'f32', has='/ride:wide128', **dict(st, p=2048, s=800))
+    both('S-stats', 'f32', has='/ride:wide128', **dict(st, p=2400, s=800, k=512))       # a launch that carries it: k = 512 | 516
+    both('S-stats', 'f32', has='/ride:after[', **dict(st, p=2400, s=800, k=516))
+    both('S-stats', 'f32', has='/ride:after[', **dict(st, p=2400, s=800, optimizer='sgd'))
+    both('S-stats', 'f64', has='/ride:after[', **dict(st, p=2400, s=800))
+    both('S-stats', 'f32', has='/noride', **dict(st, p=2400, s=800, flags=NO_RIDER))    # the flags
+    both('S-stats', 'f32', 'resident16/scalar/ride:wide128', **dict(st, p=16416, s=5472))
+    both('S-stats', 'f32', 'stats32/al/t171x2/ride:wide128', **dict(st, p=16416, s=5472, flags=GEMM_STAMPS))
+    both('S-stats', 'f32', 'resident16/vec4/noride', **dict(st, p=16416, s=5472, flags=GEMM_STAMPS | NO_RIDER))
+    print('%d boundary points agree' % (n + 39))
+
+
+def test_product_route_errors():
+    """modl_somf_product_route: MODL_EINVAL for a buffer one byte too small, a bad section, a bad descriptor or minibatch"""
+    kw = dict(k=68, p=1000, n=70, mb=70, b=70)
+    route = product_route('f32', 0, **kw)
+    assert route == 'dense/al/t2x2/edge/s7/kps160/last40/pipe/sym0'
+    assert product_route('f32', 0, cap=len(route) + 1, **kw) == route
+    assert product_route('f32', 0, cap=len(route), rc=True, **kw) == -1               # no room for the terminator
+    for section in (-1, 4):
+        assert product_route('f32', section, rc=True, **kw) == -1
+    assert product_route('f32', 0, rc=True, **dict(kw, k=0)) == -1 and product_route('f32', 0, rc=True, **dict(kw, k=4097)) == -1
+    assert product_route('f32', 0, rc=True, **dict(kw, b=71)) == -1 and product_route('f32', 0, rc=True, **dict(kw, b=0)) == -1
+    assert product_route('f32', 0, rc=True, ldx=999, **kw) == -1 and product_route('f32', 0, rc=True, base=-1, **kw) == -1
+    assert product_route('f32', 2, rc=True, s=1001, **kw) == -1
+    import ctypes as C
+    from modl_amd._lib import lib
+    assert lib.modl_somf_product_route(None, 0, 70, 1000, 0, 0, 1000, 0, C.create_string_buffer(64), 64) == -1
+
+
+K_CODE = {r.sh.get('s', r.sh['p']) for r in ROUTES if r.probe == 'S-code' and r.gpu}          # contraction lengths of the probes
+K_STATS = {r.sh['b'] for r in ROUTES if r.probe == 'S-stats' and r.gpu}
 K_TABLE = sorted({r.sh['p'] for r in ROUTES if r.probe in ('T', 'G')} | K_CODE | K_STATS)
 
 
@@ -1198,7 +1359,7 @@ def outside_kept(snaps, c):
 
 def judge_S(r, c, snaps, who=None):
     dt = c.dt
-    want = phase1(dt, c.b, c.k, c.p, r.sh.get('s', c.p), r.sh.get('s') is not None, c.agg, c.agg, c.ldx, c.b, c.flags, resident=c.resident)
+    want = phase1(dt, c.b, c.k, c.p, r.sh.get('s', c.p), r.sh.get('s') is not None, c.agg, c.agg, c.ldx, c.b, c.flags, resident=c.resident, optimizer=c.optimizer)
     for t in range(c.steps):
         before, after = snaps[t], snaps[t + 1]
         assert after.launches['code_gemm'] == want.code_launches and after.launches['stats_gemm'] == want.stats_launches, \
@@ -1239,7 +1400,7 @@ SMALL_POINTS = [c for c in POINTS if c[0] != 'G-big']
 
 def NAN_ROWS(b):
     """nan_row: row 0, so that element [0, 0] - what the K-tail and edge lanes of the dense TileLoader fetch for every row
-    before they select zeros (D:97) - is NaN.  (A NaN fetched for a ROW outside the operand lands in a tile row that is never
+    before they select zeros - is NaN.  (A NaN fetched for a ROW outside the operand lands in a tile row that is never
     stored, whatever the loader does: only the K direction can leak, and the poison behind each row covers the clamped fetch.)"""
     return (0,)
 
@@ -1255,6 +1416,8 @@ def _scenes_of(r):
 
 def _run_point(r, dt, dev):
     who = family(r, dt)
+    lib_s = library_route(r.probe, dt, **{a: v for a, v in r.sh.items() if a != 'steps'})
+    assert lib_s == route_of(r, dt), ('the library, next to the device, routes this point otherwise', lib_s, route_of(r, dt))
     for scene in _scenes_of(r):
         c = make_case(r, dt, scene)
         if r.probe == 'T':
@@ -1281,7 +1444,7 @@ def _run_point(r, dt, dev):
             again = _with_resident_switch(c, lambda: run_S(c, dev))
             assert state_bits(snaps, c) == state_bits(again, c), ('a second identical call gave other bits', scene)
             if 'ride:after[' in route_of(r, dt) and scene == 'gaussian':
-                # the rider that no launch of the dictionary update consumed is completed behind it (S:929-937), counted under
+                # the rider that no launch of the dictionary update consumed is completed behind it (phase2), counted under
                 # dict_update: as many launches more than the same step without a rider as stats_pair takes for B_ alone
                 extra = stats_pair(dt, c.k, c.p, c.ldx, c.base, c.b, split_scratch_elems(c.b, c.k, c.p), 'skip', M0=0)[1]
                 c.flags |= NO_RIDER
