@@ -1186,6 +1186,46 @@ int modl_conn_seed_maps_f32(const float *d_X, int64_t ldx, int64_t T, int64_t V,
 int modl_conn_seed_maps_f64(const double *d_X, int64_t ldx, int64_t T, int64_t V, const double *d_seeds, int R, double *d_out, int64_t ldo,
                             void *stream);
 
+/* Hard parcellation (csrc/kmeans.hip): the assignment step of Lloyd's k-means for many centre sets at
+ * once, and segmented sums over voxels grouped by label.  All calls are asynchronous on `stream`.
+ *
+ * modl_kmeans_assign_f64.  d_X: d rows of V doubles, ldx >= V.  d_C: n_sets centre sets, each K x d row-major, one after the
+ * other; d_active: R int32 indices of the sets to process (device; every entry lies in 0 .. n_sets - 1 and no entry repeats;
+ * an entry outside that range is skipped).  For each listed set r and voxel v:
+ *   d_score[r][v] = min_c (|C_c|^2 - 2 C_c . x_v),     d_labels[r][v] = the LOWEST c attaining the minimum (int32, 0-based),
+ * both arrays n_sets rows of V; the rows of sets that are not listed are not written.  A voxel whose column of X holds a
+ * non-finite value gets label -1 and score NaN, and touches no other voxel; the centres are assumed finite.  The product runs on
+ * v_mfma_f64_16x16x4_f64, the (min, argmin) is kept in registers over the centres in groups of 32: no V x K array exists, the
+ * workspace holds the R K squared centre norms.  No sums across workgroups, no atomics: the same input gives the same bits, and
+ * a set's outputs do not depend on which other sets are listed.  Nothing is read beyond column V of a row.
+ * MODL_EINVAL before any device work: a NULL pointer (d_ws apart), d < 1 or d > modl_kmeans_max_features() = 128
+ * (= modl_ica_max_components()), K < 1 or K > modl_kmeans_max_clusters() = 4096, V < 1, R < 1 or R > 65535, n_sets < R,
+ * ldx < V, a pointer that is not aligned to its element, an overlap of d_score or d_labels with each other, an input or the
+ * workspace, or of the workspace with an input.  d_ws NULL or ws_bytes below modl_kmeans_assign_workspace(V, d, K, R) (0 for
+ * bad arguments): MODL_ENOMEM; no device: MODL_ENOGPU.
+ *
+ * modl_label_sums_*.  d_X: `rows` rows of V values, ldx >= V.  d_order: n_order int32 voxel indices grouped by label, ascending
+ * within a label; d_offsets: int64[K + 1], label c owns d_order[d_offsets[c] .. d_offsets[c + 1] - 1] (the caller builds both
+ * with a stable sort of the labels and a count).  d_sums (double, `rows` rows of K, lds >= K):
+ *   d_sums[row][c] = sum over j in d_offsets[c] .. d_offsets[c + 1] - 1 of X[row][d_order[j]],
+ * accumulated in f64 (f32 is converted on load), an empty label gives 0.  No floating-point atomics; the order of the additions
+ * of one (row, label) is a function of the segment's length alone, so the bits of a label's sum do not depend on the other
+ * labels, on the other rows or on K.  A label's segment of d_order is staged once per workgroup and reused over a slab of rows;
+ * X is read once per element that belongs to a label, voxels in no segment are never read.  An index outside 0 .. V - 1 adds
+ * nothing, offsets are clamped to 0 .. n_order.  MODL_EINVAL before any device work: a NULL pointer, K < 1, rows < 0 or
+ * rows > 32 * 65535, V < 1 or V > INT32_MAX, n_order < 0, ldx < V, lds < K, a pointer that is not aligned to its element, an
+ * overlap of d_sums with an input.  rows == 0 or n_order == 0 does nothing (d_sums is not written) and returns MODL_OK; no
+ * device: MODL_ENOGPU. */
+int modl_kmeans_max_clusters(void);
+int modl_kmeans_max_features(void);
+size_t modl_kmeans_assign_workspace(int64_t V, int d, int K, int R);
+int modl_kmeans_assign_f64(const double *d_X, int64_t ldx, int64_t V, int d, const double *d_C, int K, int n_sets, const int32_t *d_active,
+                           int R, double *d_score, int32_t *d_labels, void *d_ws, size_t ws_bytes, void *stream);
+int modl_label_sums_f32(const float *d_X, int64_t ldx, int64_t rows, int64_t V, const int32_t *d_order, int64_t n_order,
+                        const int64_t *d_offsets, int K, double *d_sums, int64_t lds, void *stream);
+int modl_label_sums_f64(const double *d_X, int64_t ldx, int64_t rows, int64_t V, const int32_t *d_order, int64_t n_order,
+                        const int64_t *d_offsets, int K, double *d_sums, int64_t lds, void *stream);
+
 /* layout helpers: out[c][r] = in[r][c]  (components_ <-> Dt).  ceil(rows / 32) is the grid's y extent: more than
  * 32 * 65536 rows (65536: the y limit the MI355X reports) are refused with MODL_EINVAL before any launch. */
 int modl_transpose_f32(const float *d_in, float *d_out, int64_t rows, int64_t cols, void *stream);

@@ -15,6 +15,9 @@ from .canica import (IcaMaps, Canica, reduce_record, group_components, fastica_m
 from .connectivity import (covariances, ConnectivityMeasure, geometric_mean, sym_matrix_to_vec, vec_to_sym_matrix,  # noqa: F401
                            seed_correlation, covariances_host, ConnectivityMeasureHost, geometric_mean_host,
                            seed_correlation_host)
+from .parcellation import (KMeansParcels, Parcellation, kmeans_init, kmeans_parcels, label_signals, signals_to_rows,  # noqa: F401
+                           parcellate, kmeans_init_host, kmeans_parcels_host, label_signals_host, signals_to_rows_host,
+                           parcellate_host)
 
 __all__ = ['DictFact', 'Coder', 'SparseCodes', 'amari_discrepency', 'mean_amari_discrepency', 'grid_origins', 'grid_patches',
            'reconstruct_from_patches', 'clean', 'cleaning_basis', 'butterworth', 'ArrayMasker', 'smooth_mask', 'unmask',

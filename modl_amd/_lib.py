@@ -200,6 +200,12 @@ def bind(lib):
     _sig('modl_ica_max_components', C.c_int)
     _sig('modl_ica_sweep_workspace', _sz, _i64, C.c_int, C.c_int)
     _sig('modl_ica_sweep_f64', C.c_int, _vp, _i64, _i64, C.c_int, _vp, _vp, C.c_int, C.c_int, _f64, _vp, _vp, _vp, _sz, _vp)
+    _sig('modl_kmeans_max_clusters', C.c_int)
+    _sig('modl_kmeans_max_features', C.c_int)
+    _sig('modl_kmeans_assign_workspace', _sz, _i64, C.c_int, C.c_int, C.c_int)
+    _sig('modl_kmeans_assign_f64', C.c_int, _vp, _i64, _i64, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _sz, _vp)
+    for _sfx in ('f32', 'f64'):
+        _sig('modl_label_sums_' + _sfx, C.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _vp, C.c_int, _vp, _i64, _vp)
     _sig('modl_conn_max_regions', C.c_int)
     _sig('modl_conn_covariance_workspace', _sz, C.c_int, C.c_int)
     for _sfx in ('f32', 'f64'):

@@ -263,6 +263,20 @@ class _RecordStager:
             self.pool.shutdown(wait=True)
 
 
+def _reduced_records(est, records, confounds, affines, masker, be, k):
+    """The pass over the records that comes before a group decomposition (dict_init='canica', fMRIParcellation): every record
+    loaded, staged on the backend `be`, resampled / smoothed / masked and cleaned with the estimator's `detrend`,
+    `standardize`, `low_pass`, `high_pass`, `t_r` exactly as its fit will, then reduced to k rows
+    (modl_amd.canica.reduce_record).  Returns the list of (k, V) reductions."""
+    reduced = []
+    for rec, conf, aff in zip(records, confounds, affines):
+        rows = _staged_2d(_mask_record(np.asarray(_load(rec)), masker, be, aff), be)
+        cleaned = _clean_staged(rows, est.detrend, est.standardize, conf, low_pass=est.low_pass, high_pass=est.high_pass,
+                                t_r=est.t_r)
+        reduced.append(reduce_record(rows if cleaned is None else cleaned, k))
+    return reduced
+
+
 def _extract_regions(est, min_region_size, threshold, thresholding_strategy):
     """`extract_regions` of both estimators: the connected regions of `components_` under the fitted masker's mask, with its
     voxel volume (the affine's when the masker has one)"""
@@ -504,12 +518,7 @@ class fMRIDictFact(BaseEstimator):
         if dtype not in (np.float32, np.float64):
             dtype = np.dtype(np.float64)
         be = _Staging(getattr(self._dict_fact_class(n_components=k)._make_backend(), 'device', None), dtype)
-        reduced = []
-        for rec, conf, aff in zip(records, confounds, affines):
-            rows = _staged_2d(_mask_record(np.asarray(_load(rec)), masker, be, aff), be)
-            cleaned = _clean_staged(rows, self.detrend, self.standardize, conf, low_pass=self.low_pass, high_pass=self.high_pass,
-                                    t_r=self.t_r)
-            reduced.append(reduce_record(rows if cleaned is None else cleaned, k))
+        reduced = _reduced_records(self, records, confounds, affines, masker, be, k)
         comp, variance = group_components(reduced, k)
         del reduced
         ica = fastica_maps(comp, args['n_init'], args['fun'], 1.0, args['tol'], args['max_iter'], None, random_state)
@@ -690,6 +699,130 @@ class fMRICoder(BaseEstimator):
         scores = np.array([self.coder_.score(a) for a in arrays])
         lens = np.array([a.shape[0] for a in arrays])
         return float(np.sum(scores * lens) / np.sum(lens))
+
+
+class fMRIParcellation(BaseEstimator):
+    """Hard parcellation of raw records: every mask voxel gets one of `n_parcels` labels (k-means on the group-PCA basis of the
+    records, modl_amd.parcellation), and `transform` gives the per-parcel mean time series - nilearn's
+    `Parcellations(method='kmeans')` plus `NiftiLabelsMasker`, the baseline a dictionary of fMRIDictFact is compared with.
+
+    `n_parcels`, `n_components` (rows of every record's reduction and of the group basis; at most 128 and at most the shortest
+    record's length), `n_init` (k-means restarts, swept together), `tol`, `max_iter` (kmeans_parcels).  `mask`, `mask_affine`,
+    `smoothing_fwhm`, `voxel_size`, `standardize`, `detrend`, `low_pass`, `high_pass`, `t_r`: the masking and cleaning arguments
+    of fMRICoder; `mask` is an array or None - a strategy string is refused: compute the mask first (compute_epi_mask /
+    compute_background_mask).  `random_state` seeds the k-means++ draws.
+
+    After fit: `labels_` ((V,) int32 in 1 .. n_parcels), `parcel_sizes_` ((n_parcels,)), `kmeans_` (the KMeansParcels record),
+    `variance_` (of the group basis), and with a mask `labels_img_` ((X, Y, Z) int32, 0 outside the mask).  Without a GPU the
+    host twins run."""
+
+    def __init__(self, n_parcels=50, n_components=20, n_init=3, tol=1e-4, max_iter=300, mask=None, mask_affine=None,
+                 smoothing_fwhm=None, voxel_size=None, standardize=False, detrend=False, low_pass=None, high_pass=None, t_r=None,
+                 random_state=None, verbose=0):
+        self.n_parcels = n_parcels
+        self.n_components = n_components
+        self.n_init = n_init
+        self.tol = tol
+        self.max_iter = max_iter
+        self.mask = mask
+        self.mask_affine = mask_affine
+        self.smoothing_fwhm = smoothing_fwhm
+        self.voxel_size = voxel_size
+        self.standardize = standardize
+        self.detrend = detrend
+        self.low_pass = low_pass
+        self.high_pass = high_pass
+        self.t_r = t_r
+        self.random_state = random_state
+        self.verbose = verbose
+
+    def _staging(self, dtype):
+        from ._lib import lib
+        device = torch.device('cuda', torch.cuda.current_device()) if lib.modl_device_count() > 0 else None
+        return _Staging(device, dtype if dtype in (np.float32, np.float64) else np.float64)
+
+    def _make_masker(self):
+        if isinstance(self.mask, str):
+            raise ValueError('mask = %r: fMRIParcellation takes the mask as an array; compute it first with compute_epi_mask or '
+                             'compute_background_mask' % (self.mask,))
+        return _make_masker(self.mask, self.smoothing_fwhm, self.voxel_size, self.mask_affine)
+
+    def fit(self, records, y=None, confounds=None, affines=None):
+        """records, confounds, affines as for fMRIDictFact.fit.  One pass over the records - each loaded, staged, resampled /
+        smoothed / masked, cleaned and reduced to n_components rows on the device - then group_components and kmeans_parcels.
+        ValueError before any record is processed: n_components above 128 or above the shortest record's length, n_parcels
+        above the number of voxels."""
+        from .parcellation import kmeans_parcels, _check_parcels, _check_kmeans_scalars, _sizes, KMeansParcels
+        if records is None or len(records) < 1:
+            raise ValueError('fMRIParcellation needs at least one record')
+        confounds = _check_confounds(confounds, records)
+        affines = _check_affines(affines, records)
+        masker = self.masker_ = self._make_masker()
+        if masker is not None:
+            self.mask_ = masker.maps_.mask
+        k = self.n_components
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError('n_components must be a positive integer, got %r' % (k,))
+        _check_kmeans_scalars(k, self.n_init, self.tol, self.max_iter)
+        dtype, n_voxels = None, None
+        for i, rec in enumerate(records):                            # before any record is processed
+            arr = _load(rec, mmap=True)
+            n_rows, n_voxels = _record_shape(arr, masker)
+            dtype = arr.dtype
+            if k > n_rows:
+                raise ValueError('n_components = %d is larger than the %d time points of record %d, the shortest record bounds '
+                                 'the rows of a reduction' % (k, n_rows, i))
+        K = _check_parcels(self.n_parcels, n_voxels)
+        be = self._staging(dtype)
+        reduced = _reduced_records(self, records, confounds, affines, masker, be, k)
+        if self.verbose:
+            print('fMRIParcellation: %d records reduced to %d rows each' % (len(reduced), k))
+        comp, variance = group_components(reduced, k)
+        del reduced
+        km = kmeans_parcels(comp, K, self.n_init, None, self.tol, self.max_iter, check_random_state(self.random_state))
+        host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        self.kmeans_ = KMeansParcels(host(km.labels), host(km.centers), km.inertia, host(km.n_iter), host(km.converged), km.selected,
+                                     host(km.inertias))
+        self.labels_ = self.kmeans_.labels
+        self.parcel_sizes_ = _sizes(self.labels_, K)
+        self.variance_ = host(variance)
+        if masker is not None:
+            self.labels_img_ = np.zeros(masker.maps_.mask.shape, dtype=np.int32)
+            self.labels_img_[masker.maps_.mask] = self.labels_
+        return self
+
+    def _fitted(self):
+        if not hasattr(self, 'labels_'):
+            raise ValueError('fMRIParcellation is not fitted: call fit() first')
+
+    def transform(self, records, confounds=None, affines=None):
+        """The parcel signals of each record, one (T_i, n_parcels) array per record: `label_signals` (the mean over every
+        parcel) of the record masked and cleaned as in `fit`.  They go straight into ConnectivityMeasure."""
+        from .parcellation import label_signals
+        self._fitted()
+        if isinstance(records, str) or (isinstance(records, np.ndarray) and records.ndim in (2, 4)):
+            records = [records]
+        confounds = _check_confounds(confounds, records)
+        out = []
+        for rec, conf, aff in zip(records, confounds, _check_affines(affines, records)):
+            arr = np.asarray(_load(rec))
+            be = self._staging(arr.dtype)
+            rows = _staged_2d(_mask_record(arr, self.masker_, be, aff), be)
+            if rows.shape[1] != self.labels_.shape[0]:
+                raise ValueError('record has %d voxels, the parcellation has %d' % (rows.shape[1], self.labels_.shape[0]))
+            cleaned = _clean_staged(rows, self.detrend, self.standardize, conf, low_pass=self.low_pass, high_pass=self.high_pass,
+                                    t_r=self.t_r)
+            signals, _ = label_signals(rows if cleaned is None else cleaned, self.labels_, int(self.n_parcels))
+            out.append(signals.cpu().numpy() if isinstance(signals, torch.Tensor) else signals)
+        return out
+
+    def inverse_transform(self, signals):
+        """One (T_i, V) array per (T_i, n_parcels) array of signals: every voxel gets its parcel's signal."""
+        from .parcellation import signals_to_rows_host
+        self._fitted()
+        if isinstance(signals, np.ndarray) and signals.ndim == 2:
+            signals = [signals]
+        return [signals_to_rows_host(np.asarray(s), self.labels_) for s in signals]
 
 
 class rfMRIDictionaryScorer:
