@@ -35,7 +35,8 @@ import torch
 from sklearn.exceptions import ConvergenceWarning
 from sklearn.utils import check_random_state
 
-from ._lib import lib, check
+from ._lib import lib
+from .device import STREAM, as_float_tensor, call, have_gpu, is_cuda, like_input, scratch
 
 __all__ = ['IcaMaps', 'Canica', 'reduce_record', 'group_components', 'fastica_maps', 'threshold_maps', 'canica',
            'reduce_record_host', 'group_components_host', 'fastica_maps_host', 'threshold_maps_host', 'canica_host',
@@ -48,28 +49,6 @@ GRAM_CHUNK = 1 << 16                                        # voxels per f64 tem
 
 
 # ---- arguments
-def _is_cuda(a):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError('a numpy array or a CUDA tensor is expected, got a tensor on %s' % a.device)
-        return True
-    return False
-
-
-def _have_gpu():
-    return lib.modl_device_count() > 0
-
-
-def _to_device(a, device=None):
-    """a 2-D float tensor on the device, in its own dtype (float32 / float64; anything else becomes float64)"""
-    if isinstance(a, torch.Tensor):
-        return a if a.dtype in (torch.float32, torch.float64) else a.to(torch.float64)
-    a = np.asarray(a)
-    if a.dtype not in (np.float32, np.float64):
-        a = a.astype(np.float64)
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device or torch.device('cuda', torch.cuda.current_device()))
-
-
 def _check_2d(a, what):
     if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError('%s must be a 2-D array with at least one row and one column, got shape %s' % (what, tuple(a.shape)))
@@ -87,10 +66,6 @@ def _check_fun(fun):
     if fun not in FUNS:
         raise ValueError("fun must be 'cube', 'logcosh' or 'exp', got %r" % (fun,))
     return FUNS[fun]
-
-
-def _out(t, cuda):
-    return t if cuda else t.cpu().numpy()
 
 
 # ---- PCA through the Gram matrix
@@ -134,15 +109,15 @@ def reduce_record(rows, n_components):
     reduction_ratio='auto'), from the eigenvectors U of the T x T Gram matrix as U[:, :k]^T rows, accumulated in f64 over
     chunks of voxels.  Every row is signed so that the largest-magnitude entry of its temporal vector is positive.
     ValueError: n_components > T."""
-    cuda = _is_cuda(rows)
-    if not cuda and not _have_gpu():
+    cuda = is_cuda(rows)
+    if not cuda and not have_gpu():
         return reduce_record_host(rows, n_components)
-    rows = _to_device(rows)
+    rows = as_float_tensor(rows)
     _check_2d(rows, 'rows')
     k = _check_k(n_components, rows.shape[0], 'the record')
     with torch.cuda.device(rows.device):
         _, Ut = _top_eigh(_gram_f64(rows), k)
-        return _out(_project_f64(Ut, rows), cuda)
+        return like_input(_project_f64(Ut, rows), cuda)
 
 
 def reduce_record_host(rows, n_components):
@@ -168,7 +143,7 @@ def _stack(reduced, host):
     if host:
         return np.concatenate([np.asarray(r, dtype=np.float64) for r in reduced])
     device = next((r.device for r in reduced if isinstance(r, torch.Tensor)), None)
-    return torch.cat([_to_device(r, device).to(torch.float64) for r in reduced])
+    return torch.cat([as_float_tensor(r, device).to(torch.float64) for r in reduced])
 
 
 def group_components(reduced, n_components):
@@ -177,8 +152,8 @@ def group_components(reduced, n_components):
     values).  Same Gram route as `reduce_record`.  The group spectrum is nearly degenerate by construction, so only the
     subspace is defined: any orthonormal basis of it is a correct answer."""
     listed = [reduced] if isinstance(reduced, (np.ndarray, torch.Tensor)) else list(reduced)
-    cuda = any(_is_cuda(r) for r in listed)
-    if not cuda and not _have_gpu():
+    cuda = any(is_cuda(r) for r in listed)
+    if not cuda and not have_gpu():
         return group_components_host(listed, n_components)
     X = _stack(listed, False)
     k = _check_k(n_components, X.shape[0], 'the stacked reductions')
@@ -189,7 +164,7 @@ def group_components(reduced, n_components):
         if not bool((s2 > 0).all()):
             raise ValueError('the stacked reductions have rank below n_components = %d' % k)
         comp = _project_f64(Ut / s2.sqrt()[:, None], X)
-        return _out(comp, cuda), _out(s2, cuda)
+        return like_input(comp, cuda), like_input(s2, cuda)
 
 
 def group_components_host(reduced, n_components):
@@ -275,7 +250,6 @@ def _safe(W, ok):
 def ica_sweep(X1, W, active, fun='cube', alpha=1.0, M=None, gp=None, ws=None):
     """One launch of modl_ica_sweep_f64 on CUDA tensors: X1 (k, V) float64 with contiguous rows, W (n, k, k) float64
     contiguous, active (R,) int32 -> (M (n, k, k), gp (n, k)); only the slots of the listed restarts are written."""
-    from .device import ptr, stream_ptr
     k, V = X1.shape
     R = int(active.shape[0])
     if M is None:
@@ -284,12 +258,11 @@ def ica_sweep(X1, W, active, fun='cube', alpha=1.0, M=None, gp=None, ws=None):
         gp = torch.zeros(W.shape[:2], dtype=torch.float64, device=W.device)
     need = lib.modl_ica_sweep_workspace(V, k, R)
     if ws is None:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=W.device)
+        ws = scratch(need, W.device)
     elif ws.numel() < need:
         raise ValueError('ica_sweep: the workspace holds %d bytes, %d restarts need %d' % (ws.numel(), R, need))
-    with torch.cuda.device(X1.device):
-        check(lib.modl_ica_sweep_f64(ptr(X1), X1.stride(0) if k > 1 else V, V, k, ptr(W), ptr(active), R, _check_fun(fun), float(alpha),
-                                     ptr(M), ptr(gp), ptr(ws), ws.numel(), stream_ptr(X1.device)), 'modl_ica_sweep')
+    call('modl_ica_sweep_f64', X1, X1.stride(0) if k > 1 else V, V, k, W, active, R, _check_fun(fun), float(alpha), M, gp, ws,
+         ws.numel(), STREAM, device=X1.device)
     return M, gp
 
 
@@ -318,10 +291,10 @@ def fastica_maps(components, n_init=10, fun='cube', alpha=1.0, tol=1e-4, max_ite
 
     Returns IcaMaps(maps, W (n_init, k, k), n_iter, converged, failed (n_init,), selected): maps (k, V) = W[selected] X1, or
     with return_all=True the stack (n_init, k, V) (n_init k V 8 bytes; rows of failed restarts are NaN)."""
-    cuda = _is_cuda(components)
-    if not cuda and not _have_gpu():
+    cuda = is_cuda(components)
+    if not cuda and not have_gpu():
         return fastica_maps_host(components, n_init, fun, alpha, tol, max_iter, w_init, random_state, return_all)
-    X = _to_device(components).to(torch.float64)
+    X = as_float_tensor(components).to(torch.float64)
     _check_2d(X, 'components')
     k, V = X.shape
     w0 = _check_ica_args(k, n_init, fun, tol, max_iter, w_init, random_state)
@@ -337,7 +310,7 @@ def fastica_maps(components, n_init=10, fun='cube', alpha=1.0, tol=1e-4, max_ite
         n_iter = np.zeros(n, dtype=np.int64)
         converged = np.zeros(n, dtype=bool)
         M, gp = torch.zeros_like(W), torch.zeros((n, k), dtype=torch.float64, device=dev)
-        ws = torch.empty(max(lib.modl_ica_sweep_workspace(V, k, n), 8), dtype=torch.uint8, device=dev)
+        ws = scratch(lib.modl_ica_sweep_workspace(V, k, n), dev)
         run = running.cpu().numpy()
         for it in range(1, max_iter + 1):
             if not run.any():
@@ -498,10 +471,10 @@ def threshold_maps(maps, threshold='auto'):
     interpolated as scipy does; ratio = 1 for 'auto', otherwise the number given (0 < ratio <= k).  On the device the two
     order statistics come from torch.kthvalue and the interpolation is scipy's arithmetic on those two numbers, so the
     result equals the twin's bit for bit.  threshold=None only applies the sign rule."""
-    cuda = _is_cuda(maps)
-    if not cuda and not _have_gpu():
+    cuda = is_cuda(maps)
+    if not cuda and not have_gpu():
         return threshold_maps_host(maps, threshold)
-    m = _to_device(maps).to(torch.float64)
+    m = as_float_tensor(maps).to(torch.float64)
     _check_2d(m, 'maps')
     ratio = _check_ratio(threshold, m.shape[0])
     with torch.cuda.device(m.device):
@@ -518,7 +491,7 @@ def threshold_maps(maps, threshold='auto'):
             m = torch.where(m.abs() < float(cutoff), torch.zeros((), dtype=m.dtype, device=m.device), m)
         flip = m.amax(dim=1) < -m.amin(dim=1)
         m = torch.where(flip[:, None], -m, m)
-    return _out(m, cuda)
+    return like_input(m, cuda)
 
 
 def threshold_maps_host(maps, threshold='auto'):
@@ -535,15 +508,17 @@ def threshold_maps_host(maps, threshold='auto'):
 
 
 # ---- the pipeline
-def _check_records(records, n_components):
+def _check_records(records, n_components, what='canica', same_width=False):
     if isinstance(records, (np.ndarray, torch.Tensor)) and records.ndim == 2:
         records = [records]
     records = list(records)
     if not records:
-        raise ValueError('canica needs at least one record')
+        raise ValueError('%s needs at least one record' % what)
     for r in records:
         _check_2d(r, 'a record')
         _check_k(n_components, r.shape[0], 'the shortest record')
+        if same_width and r.shape[1] != records[0].shape[1]:
+            raise ValueError('the records must have one number of voxels, got %d and %d' % (records[0].shape[1], r.shape[1]))
     return records
 
 
@@ -552,12 +527,12 @@ def canica(records, n_components=20, n_init=10, threshold='auto', fun='cube', to
     Returns Canica(maps (k, V) float64, variance (k,), ica: the IcaMaps record).  The stacked reductions take
     n_records * k * V * 8 bytes.  ValueError: n_components larger than the shortest record."""
     records = _check_records(records, n_components)
-    cuda = any(_is_cuda(r) for r in records)
-    if not cuda and not _have_gpu():
+    cuda = any(is_cuda(r) for r in records)
+    if not cuda and not have_gpu():
         return canica_host(records, n_components, n_init, threshold, fun, tol, max_iter, random_state)
     _check_ratio(threshold, n_components)
     device = next((r.device for r in records if isinstance(r, torch.Tensor)), None)
-    reduced = [reduce_record(_to_device(r, device), n_components) for r in records]
+    reduced = [reduce_record(as_float_tensor(r, device), n_components) for r in records]
     comp, variance = group_components(reduced, n_components)
     del reduced
     ica = fastica_maps(comp, n_init, fun, 1.0, tol, max_iter, None, random_state)

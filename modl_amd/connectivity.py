@@ -28,7 +28,8 @@ import torch
 from sklearn.base import BaseEstimator
 from sklearn.exceptions import ConvergenceWarning
 
-from ._lib import lib, check
+from ._lib import lib
+from .device import STREAM, as_float_tensor, call, current_device, have_gpu, is_cuda, scratch
 
 __all__ = ['covariances', 'covariances_host', 'ConnectivityMeasure', 'ConnectivityMeasureHost', 'geometric_mean',
            'geometric_mean_host', 'sym_matrix_to_vec', 'vec_to_sym_matrix', 'seed_correlation', 'seed_correlation_host',
@@ -40,18 +41,6 @@ U64 = 2.0 ** -53
 
 
 # ---- arguments
-def _is_cuda(a):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError('a numpy array or a CUDA tensor is expected, got a tensor on %s' % a.device)
-        return True
-    return False
-
-
-def _have_gpu():
-    return lib.modl_device_count() > 0
-
-
 def _check_estimator(estimator):
     if estimator not in ESTIMATORS:
         raise ValueError("estimator must be 'empirical' or 'ledoit_wolf', got %r" % (estimator,))
@@ -79,24 +68,12 @@ def _device_of(arrays):
     for a in arrays:
         if isinstance(a, torch.Tensor):
             return a.device
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _as_tensor(a, device, dtype=None):
-    if not isinstance(a, torch.Tensor):
-        a = np.asarray(a)
-        if a.dtype not in (np.float32, np.float64):
-            a = a.astype(np.float64)
-        a = torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    elif a.dtype not in (torch.float32, torch.float64):
-        a = a.to(torch.float64)
-    return a if dtype is None else a.to(dtype)
+    return current_device()
 
 
 # ---- covariance
 def _covariances_device(signals, estimator, correlation):
     """(cov (S, R, R), shrinkage (S,)) float64 CUDA tensors of checked signals: one library call"""
-    from .device import ptr, stream_ptr
     est = _check_estimator(estimator)
     R = int(signals[0].shape[1])
     if R > lib.modl_conn_max_regions():
@@ -104,7 +81,7 @@ def _covariances_device(signals, estimator, correlation):
     if len(signals) > 65535:
         raise ValueError('covariances takes at most 65535 records in a call, got %d' % len(signals))
     device = _device_of(signals)
-    parts = [_as_tensor(s, device) for s in signals]
+    parts = [as_float_tensor(s, device) for s in signals]
     dtype = torch.float32 if all(p.dtype == torch.float32 for p in parts) else torch.float64
     with torch.cuda.device(device):
         X = parts[0].to(dtype).contiguous() if len(parts) == 1 else torch.cat([p.to(dtype) for p in parts])
@@ -113,11 +90,9 @@ def _covariances_device(signals, estimator, correlation):
         np.cumsum([p.shape[0] for p in parts], out=offsets[1:])
         cov = torch.empty((S, R, R), dtype=torch.float64, device=device)
         shrinkage = torch.empty(S, dtype=torch.float64, device=device)
-        need = lib.modl_conn_covariance_workspace(S, R)
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-        fn = lib.modl_conn_covariance_f32 if dtype == torch.float32 else lib.modl_conn_covariance_f64
-        check(fn(ptr(X), X.stride(0), offsets.ctypes.data, S, R, est, 1 if correlation else 0, ptr(cov), ptr(shrinkage), ptr(ws),
-                 ws.numel(), stream_ptr(device)), 'modl_conn_covariance')
+        ws = scratch(lib.modl_conn_covariance_workspace(S, R), device)
+        call('modl_conn_covariance', X, X.stride(0), offsets, S, R, est, 1 if correlation else 0, cov, shrinkage, ws, ws.numel(),
+             STREAM, device=device, dtype=X)
     return cov, shrinkage
 
 
@@ -128,8 +103,8 @@ def covariances(signals, estimator='ledoit_wolf'):
     (1 - shrinkage) E + shrinkage mu I with mu = trace(E) / R and sklearn.covariance.LedoitWolf's shrinkage (0 for R = 1).  All records go
     through one call of the library (csrc/connectivity.hip); CUDA tensors in give CUDA tensors out."""
     signals = _check_signals(signals)
-    cuda = any(_is_cuda(s) for s in signals)
-    if not cuda and not _have_gpu():
+    cuda = any(is_cuda(s) for s in signals)
+    if not cuda and not have_gpu():
         return covariances_host(signals, estimator)
     cov, shrinkage = _covariances_device(signals, estimator, False)
     return (cov, shrinkage) if cuda else (cov.cpu().numpy(), shrinkage.cpu().numpy())
@@ -255,7 +230,7 @@ def _stack_matrices(covs, host):
         if host or not any(isinstance(c, torch.Tensor) for c in covs):
             return np.stack([np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float64) for c in covs])
         device = _device_of(covs)
-        return torch.stack([_as_tensor(c, device, torch.float64) for c in covs])
+        return torch.stack([as_float_tensor(c, device, torch.float64) for c in covs])
     if isinstance(covs, torch.Tensor):
         return covs.cpu().numpy().astype(np.float64) if host else covs.to(torch.float64)
     return np.asarray(covs, dtype=np.float64)
@@ -267,8 +242,8 @@ def geometric_mean(covs, max_iter=10, tol=1e-7, return_norms=False):
     (every matrix function through eigh, batched over the records on the device); the step is halved when ||L||_F grows; it
     stops when ||L||_F / R^2 < tol.  Not stopping within max_iter: one ConvergenceWarning, G is kept.  A non-finite L:
     FloatingPointError.  return_norms=True: (G, the norm / R^2 compared with tol at every iteration)."""
-    cuda = any(_is_cuda(c) for c in covs) if isinstance(covs, (list, tuple)) else _is_cuda(covs)
-    if not cuda and not _have_gpu():
+    cuda = any(is_cuda(c) for c in covs) if isinstance(covs, (list, tuple)) else is_cuda(covs)
+    if not cuda and not have_gpu():
         return geometric_mean_host(covs, max_iter, tol, return_norms)
     C = _stack_matrices(covs, False)
     if not isinstance(C, torch.Tensor):
@@ -364,8 +339,8 @@ class ConnectivityMeasure(BaseEstimator):
             raise ValueError('kind must be one of %s, got %r' % (', '.join(repr(k) for k in KINDS), self.kind))
         _check_estimator(self.estimator)
         signals = _check_signals(signals)
-        cuda = any(_is_cuda(s) for s in signals)
-        host = self._host or (not cuda and not _have_gpu())
+        cuda = any(is_cuda(s) for s in signals)
+        host = self._host or (not cuda and not have_gpu())
         if not fit:
             if not hasattr(self, 'mean_'):
                 raise ValueError('ConnectivityMeasure is not fitted: call fit() first')
@@ -417,7 +392,7 @@ class ConnectivityMeasure(BaseEstimator):
             if dev is None:
                 pair.append(m.cpu().numpy() if isinstance(m, torch.Tensor) else m)
             else:
-                pair.append(_as_tensor(m, dev, torch.float64))
+                pair.append(as_float_tensor(m, dev, torch.float64))
         return pair
 
     def fit(self, signals, y=None):
@@ -494,13 +469,12 @@ def seed_correlation(rows, seeds):
     in f64 on the way, the division by sqrt(sum x^2 - (sum x)^2 / T) in the epilogue - no centred or normalised copy of the
     record exists.  A voxel that is constant to rounding gives an exact 0, results are clipped to [-1, 1].
     ValueError: a constant seed, T < 2, more than modl_conn_max_regions() seeds."""
-    from .device import ptr, stream_ptr
-    cuda = _is_cuda(rows)
-    if not cuda and not _have_gpu():
+    cuda = is_cuda(rows)
+    if not cuda and not have_gpu():
         return seed_correlation_host(rows, seeds)
     device = rows.device if cuda else _device_of([seeds])
-    X = _as_tensor(rows, device)
-    s = _check_seed_args(X, _as_tensor(seeds, device))
+    X = as_float_tensor(rows, device)
+    s = _check_seed_args(X, as_float_tensor(seeds, device))
     R, (T, V) = int(s.shape[1]), X.shape
     if R > lib.modl_conn_max_regions():
         raise ValueError('seed_correlation takes at most %d seeds, got %d' % (lib.modl_conn_max_regions(), R))
@@ -509,8 +483,7 @@ def seed_correlation(rows, seeds):
             X = X.contiguous()
         sh = _prepare_seeds(s).to(X.dtype).contiguous()
         out = torch.empty((R, V), dtype=X.dtype, device=device)
-        fn = lib.modl_conn_seed_maps_f32 if X.dtype == torch.float32 else lib.modl_conn_seed_maps_f64
-        check(fn(ptr(X), X.stride(0), T, V, ptr(sh), R, ptr(out), V, stream_ptr(device)), 'modl_conn_seed_maps')
+        call('modl_conn_seed_maps', X, X.stride(0), T, V, sh, R, out, V, STREAM, device=device, dtype=X)
     return out if cuda else out.cpu().numpy()
 
 

@@ -41,7 +41,8 @@ def gen_batches(n, batch_size):
         yield slice(start, n)
 
 from ._lib import lib, check, SomfDesc, SomfState, SomfBatch, ProfEntry, AGG, OPT
-from .device import (default_device, dtype_id, sfx, torch_dtype, ptr, stream_ptr, to_device, transpose_to, gather_rows)
+from .device import (STREAM, call, default_device, dtype_id, scratch, torch_dtype, ptr, stream_ptr, to_device, transpose_to,
+                     gather_rows)
 from .randomkit import RandomState, Sampler, batch_weight
 from .utils import get_sub_slice
 
@@ -215,14 +216,13 @@ class HipBackend:
             setattr(self, name, new.clone())
 
     def scale_atoms(self, l1_ratio, radius=1.0):      # enet_scale on every atom (dict_fact.py:465-468)
-        f = getattr(lib, 'modl_enet_scale_' + sfx(self.dtype))
-        with torch.cuda.device(self.device):
-            check(f(ptr(self.Dt), self.k, self.p, 1, self.k, l1_ratio, radius, stream_ptr(self.device)), 'modl_enet_scale')
+        call('modl_enet_scale', self.Dt, self.k, self.p, 1, self.k, l1_ratio, radius, STREAM, device=self.device,
+             dtype=self.dtype)
 
     def full_gram(self):
         if self.G is None:
             self.G = torch.zeros((self.k, self.k), dtype=torch_dtype(self.dtype), device=self.device)
-        check(lib.modl_somf_full_gram(self.plan, ptr(self.Dt), ptr(self.G), stream_ptr(self.device)), 'modl_somf_full_gram')
+        call('modl_somf_full_gram', self.plan, self.Dt, self.G, STREAM, device=self.device)
 
     def n_rows(self, name):
         return getattr(self, name).shape[0]
@@ -230,9 +230,7 @@ class HipBackend:
     def shuffle_rows(self, name, swaps):
         t = getattr(self, name)
         row_bytes = t[0].numel() * t.element_size()
-        with torch.cuda.device(self.device):
-            check(lib.modl_apply_swaps_rows_device(ptr(t), t.shape[0], row_bytes, swaps.ctypes.data_as(C.c_void_p),
-                                                   stream_ptr(self.device)), 'modl_apply_swaps_rows_device')
+        call('modl_apply_swaps_rows_device', t, t.shape[0], row_bytes, swaps, STREAM, device=self.device)
 
     # -- data ---------------------------------------------------------------
     def stage_X(self, X):
@@ -249,10 +247,8 @@ class HipBackend:
         idx = torch.from_numpy(np.ascontiguousarray(indices_3d, dtype=np.int64)).to(self.device)
         n = idx.shape[0]
         out = torch.empty((n, x * y * z), dtype=d_image.dtype, device=self.device)
-        f = getattr(lib, 'modl_image_patches_' + ('f32' if d_image.dtype == torch.float32 else 'f64'))
-        with torch.cuda.device(self.device):
-            check(f(ptr(d_image), H, W, Cc, ptr(idx), n, x, y, z, int(bool(with_mean)), int(bool(with_std)), ptr(out),
-                    x * y * z, stream_ptr(self.device)), 'modl_image_patches')
+        call('modl_image_patches', d_image, H, W, Cc, idx, n, x, y, z, int(bool(with_mean)), int(bool(with_std)), out,
+             x * y * z, STREAM, device=self.device, dtype=d_image)
         return out
 
     def take_rows(self, Xh, perm):
@@ -450,8 +446,7 @@ class HipBackend:
         self._transform_plan(kw)
         n = Xh.shape[0]
         out = torch.empty((n, self.k), dtype=torch_dtype(self.dtype), device=self.device)
-        check(lib.modl_somf_transform(self.tplan, ptr(self.Dt), ptr(G), ptr(Xh), Xh.stride(0), n, ptr(out),
-                                      stream_ptr(self.device)), 'modl_somf_transform')
+        call('modl_somf_transform', self.tplan, self.Dt, G, Xh, Xh.stride(0), n, out, STREAM, device=self.device)
         return out.cpu().numpy() if to_host else out
 
     def masked_gram(self, Xh, obs, rows=None):
@@ -462,15 +457,31 @@ class HipBackend:
         kw = dict(dtype=torch_dtype(self.dtype), device=self.device)
         G, Dx = torch.empty((b, self.k, self.k), **kw), torch.empty((b, self.k), **kw)
         nobs = torch.empty(b, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(getattr(lib, 'modl_masked_gram_' + sfx(self.dtype))(
-                ptr(self.Dt), self.p, self.k, ptr(Xh), Xh.stride(0), ptr(obs), obs.stride(0), ptr(rows), b, ptr(G),
-                ptr(Dx), ptr(nobs), stream_ptr(self.device)), 'modl_masked_gram')
+        call('modl_masked_gram', self.Dt, self.p, self.k, Xh, Xh.stride(0), obs, obs.stride(0), rows, b, G, Dx, nobs, STREAM,
+             device=self.device, dtype=self.dtype)
         return G, Dx, nobs
 
     def masked_chunk_rows(self):
         """rows per masked solve: their Gram matrices stay under 256 MB (a memory bound, not a tuned value)"""
         return max(1, min(4096, (256 << 20) // (self.k * self.k * self.dtype.itemsize)))
+
+    def _masked_split(self, Xh, obs, nobs):
+        """The rows of a masked solve by their observed entries (obs (n, p) uint8, 1 = observed; nobs: its row sums, or
+        None): (nobs, clean, chunks) with `clean` the rows without a hole, which take the shared-Gram route, and `chunks`
+        a generator of (rows, G (b, k, k), Dx (b, k)) over the rows with a hole and an observed entry, masked_chunk_rows()
+        of them at a time with the Gram matrices of their own (`masked_gram`).  Rows without an observed entry are in
+        neither."""
+        if nobs is None:
+            nobs = obs.sum(dim=1, dtype=torch.int32)
+        clean = torch.nonzero(nobs == self.p).flatten()
+
+        def chunks():
+            holed = torch.nonzero((nobs > 0) & (nobs < self.p)).flatten()
+            step = self.masked_chunk_rows()
+            for c0 in range(0, holed.shape[0], step):
+                rows = holed[c0:c0 + step].contiguous()
+                yield (rows,) + self.masked_gram(Xh, obs, rows)[:2]
+        return nobs, clean, chunks()
 
     def transform_masked(self, Xh, obs, kw, G=None, nobs=None):
         """Codes of the rows of Xh (n, p) from their observed entries only (obs (n, p) uint8, 1 = observed; nobs: its row
@@ -479,33 +490,21 @@ class HipBackend:
         of their own: modl_masked_gram_* then modl_enet_regression_multi_gram_* from a warm start of ones, the solver's
         X being the zero-filled rows (its tolerance scales with the observed squared norm)."""
         n = Xh.shape[0]
-        if nobs is None:
-            nobs = obs.sum(dim=1, dtype=torch.int32)
-        clean = torch.nonzero(nobs == self.p).flatten()
+        nobs, clean, chunks = self._masked_split(Xh, obs, nobs)
         if clean.shape[0] == n:
             return self.transform(Xh, kw, G, to_host=False)
         code = torch.zeros((n, self.k), dtype=torch_dtype(self.dtype), device=self.device)
         if clean.shape[0]:
             code[clean] = self.transform(Xh[clean], kw, G, to_host=False)
-        holed = torch.nonzero((nobs > 0) & (nobs < self.p)).flatten()
-        if holed.shape[0] == 0:
-            return code
-        Xz = torch.where(obs != 0, Xh, torch.zeros((), dtype=Xh.dtype, device=Xh.device))
-        solve = getattr(lib, 'modl_enet_regression_multi_gram_' + sfx(self.dtype))
-        step = self.masked_chunk_rows()
-        for c0 in range(0, holed.shape[0], step):
-            rows = holed[c0:c0 + step].contiguous()
+        for rows, Gm, Dx in chunks:
             b = rows.shape[0]
-            Gm, Dx, _ = self.masked_gram(Xh, obs, rows)
-            Xc = Xz[rows]
+            Xc = torch.where(obs[rows] != 0, Xh[rows], torch.zeros((), dtype=Xh.dtype, device=Xh.device))
             out = torch.ones((b, self.k), dtype=code.dtype, device=self.device)
             nbytes = lib.modl_enet_regression_workspace(dtype_id(self.dtype), b, self.k, 1)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
-            with torch.cuda.device(self.device):
-                check(solve(ptr(Gm), ptr(Dx), ptr(Xc), Xc.stride(0), self.p, ptr(out), None, b, self.k,
-                            kw['code_l1_ratio'], kw['code_alpha'], int(bool(kw['code_pos'])), kw['tol'],
-                            int(kw['max_iter']), None, ptr(ws), nbytes, stream_ptr(self.device)),
-                      'modl_enet_regression_multi_gram')
+            ws = scratch(nbytes, self.device)
+            call('modl_enet_regression_multi_gram', Gm, Dx, Xc, Xc.stride(0), self.p, out, None, b, self.k,
+                 kw['code_l1_ratio'], kw['code_alpha'], int(bool(kw['code_pos'])), kw['tol'], int(kw['max_iter']), None, ws,
+                 nbytes, STREAM, device=self.device, dtype=self.dtype)
             code[rows] = out
         return code
 
@@ -526,12 +525,10 @@ class HipBackend:
             code = torch.empty((n, self.k), dtype=td, device=dev)
             support = torch.empty((n, s), dtype=torch.int32, device=dev)
             n_active = torch.empty(n, dtype=torch.int32, device=dev)
-            check(lib.modl_somf_transform_omp(self.tplan, ptr(self.Dt), ptr(G), ptr(Xh), Xh.stride(0), n, s, tolv, ptr(code),
-                                              ptr(support), ptr(n_active), stream_ptr(dev)), 'modl_somf_transform_omp')
+            call('modl_somf_transform_omp', self.tplan, self.Dt, G, Xh, Xh.stride(0), n, s, tolv, code, support, n_active,
+                 STREAM, device=dev)
             return code, support, n_active
-        if nobs is None:
-            nobs = obs.sum(dim=1, dtype=torch.int32)
-        clean = torch.nonzero(nobs == self.p).flatten()
+        nobs, clean, chunks = self._masked_split(Xh, obs, nobs)
         if clean.shape[0] == n:
             return self.omp(Xh, s, tol, G, kw=kw)
         code = torch.zeros((n, self.k), dtype=td, device=dev)
@@ -539,15 +536,8 @@ class HipBackend:
         n_active = torch.zeros(n, dtype=torch.int32, device=dev)
         if clean.shape[0]:
             code[clean], support[clean], n_active[clean] = self.omp(Xh[clean], s, tol, G, kw=kw)
-        holed = torch.nonzero((nobs > 0) & (nobs < self.p)).flatten()
-        if holed.shape[0] == 0:
-            return code, support, n_active
-        solve = getattr(lib, 'modl_omp_gram_' + sfx(self.dtype))
-        step = self.masked_chunk_rows()
-        for c0 in range(0, holed.shape[0], step):
-            rows = holed[c0:c0 + step].contiguous()
+        for rows, Gm, Dx in chunks:
             b = rows.shape[0]
-            Gm, Dx, _ = self.masked_gram(Xh, obs, rows)
             xn = None
             if tol is not None:
                 Xc = torch.where(obs[rows] != 0, Xh[rows], torch.zeros((), dtype=Xh.dtype, device=Xh.device))
@@ -555,9 +545,8 @@ class HipBackend:
             out = torch.empty((b, self.k), dtype=td, device=dev)
             sup = torch.empty((b, s), dtype=torch.int32, device=dev)
             na = torch.empty(b, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):                            # (no scratch: modl_omp_workspace is 0)
-                check(solve(ptr(Gm), self.k * self.k, ptr(Dx), ptr(xn), b, self.k, s, tolv, ptr(out), ptr(sup), ptr(na),
-                            None, 0, stream_ptr(dev)), 'modl_omp_gram')
+            call('modl_omp_gram', Gm, self.k * self.k, Dx, xn, b, self.k, s, tolv, out, sup, na, None, 0, STREAM, device=dev,
+                 dtype=self.dtype)                                  # (no scratch: modl_omp_workspace is 0)
             code[rows], support[rows], n_active[rows] = out, sup, na
         return code, support, n_active
 
@@ -568,10 +557,8 @@ class HipBackend:
         out = torch.empty((n, self.p), dtype=torch_dtype(self.dtype), device=self.device)
         if n == 0:
             return out
-        f = getattr(lib, 'modl_image_decode_' + sfx(self.dtype))
-        with torch.cuda.device(self.device):
-            check(f(ptr(code), n, self.k, ptr(self.Dt), self.p, 1 if mean is None else mean.shape[1], ptr(mean), ptr(den),
-                    ptr(out), self.p, stream_ptr(self.device)), 'modl_image_decode')
+        call('modl_image_decode', code, n, self.k, self.Dt, self.p, 1 if mean is None else mean.shape[1], mean, den, out,
+             self.p, STREAM, device=self.device, dtype=self.dtype)
         return out
 
     def compact(self, code, base=0):
@@ -580,24 +567,21 @@ class HipBackend:
         (nnz,) int32 in ascending order within a row and data (nnz,) of the chunk's dtype, bit for bit.  Kept: value != 0.
         The chunk's total is read back between the two calls to size the outputs: one synchronise per chunk."""
         b, k = code.shape
-        dev, sx = self.device, 'f32' if code.dtype == torch.float32 else 'f64'
+        dev = self.device
         if code.stride(1) != 1 and b:
             code = code.contiguous()
         indptr = torch.full((b + 1,), base, dtype=torch.int64, device=dev)
         total = 0
         if b:
             nbytes = lib.modl_csr_compact_workspace(b)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                check(getattr(lib, 'modl_csr_count_' + sx)(ptr(code), code.stride(0), b, k, base, ptr(indptr), ptr(ws),
-                                                           nbytes, stream_ptr(dev)), 'modl_csr_count')
+            ws = scratch(nbytes, dev)
+            call('modl_csr_count', code, code.stride(0), b, k, base, indptr, ws, nbytes, STREAM, device=dev, dtype=code)
             total = int(indptr[b].item()) - base
         indices = torch.empty(total, dtype=torch.int32, device=dev)
         data = torch.empty(total, dtype=code.dtype, device=dev)
         if total:
-            with torch.cuda.device(dev):
-                check(getattr(lib, 'modl_csr_fill_' + sx)(ptr(code), code.stride(0), b, k, base, ptr(indptr), total,
-                                                          ptr(indices), ptr(data), stream_ptr(dev)), 'modl_csr_fill')
+            call('modl_csr_fill', code, code.stride(0), b, k, base, indptr, total, indices, data, STREAM, device=dev,
+                 dtype=code)
         return indptr, indices, data
 
     def decode_csr(self, indptr, indices, data, n):
@@ -613,12 +597,10 @@ class HipBackend:
         if nnz == 0:                                 # (an empty tensor has no address; the kernel still checks indptr)
             indices, data = indices.new_zeros(1), data.new_zeros(1)
         nbytes = lib.modl_csr_decode_workspace(dtype_id(self.dtype), self.k, self.p)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = scratch(nbytes, dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            check(getattr(lib, 'modl_csr_decode_' + sfx(self.dtype))(
-                ptr(indptr), ptr(indices), ptr(data), nnz, n, self.k, ptr(self.Dt), self.p, ptr(out), self.p,
-                ptr(status), ptr(ws), nbytes, stream_ptr(dev)), 'modl_csr_decode')
+        call('modl_csr_decode', indptr, indices, data, nnz, n, self.k, self.Dt, self.p, out, self.p, status, ws, nbytes,
+             STREAM, device=dev, dtype=self.dtype)
         if int(status.item()):
             raise ValueError('sparse codes are corrupt: an index outside [0, %d) or an indptr pair that is decreasing or '
                              'reaches beyond the %d stored entries' % (self.k, nnz))
@@ -628,12 +610,10 @@ class HipBackend:
         """[sum (X - code D)^2, sum |code|, sum code^2] of device-resident X and codes (dict_fact.py:108-112)."""
         n, p = Xh.shape
         nbytes = lib.modl_objective_workspace(dtype_id(self.dtype), n, p)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = scratch(nbytes, self.device)
         out = torch.empty(3, dtype=torch.float64, device=self.device)
-        f = getattr(lib, 'modl_objective_' + sfx(self.dtype))
-        with torch.cuda.device(self.device):
-            check(f(ptr(Xh), Xh.stride(0), n, p, ptr(self.Dt), self.k, ptr(code), ptr(ws), nbytes, ptr(out),
-                    stream_ptr(self.device)), 'modl_objective')
+        call('modl_objective', Xh, Xh.stride(0), n, p, self.Dt, self.k, code, ws, nbytes, out, STREAM, device=self.device,
+             dtype=self.dtype)
         return out.cpu().numpy()
 
     def masked_objective(self, Xh, sel, code, row_w=None):
@@ -643,22 +623,18 @@ class HipBackend:
         used.  A numpy (8,) f64 array."""
         n, p = Xh.shape
         nbytes = lib.modl_masked_objective_workspace(dtype_id(self.dtype), n, p)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = scratch(nbytes, self.device)
         out = torch.empty(8, dtype=torch.float64, device=self.device)
-        f = getattr(lib, 'modl_masked_objective_' + sfx(self.dtype))
-        with torch.cuda.device(self.device):
-            check(f(ptr(Xh), Xh.stride(0), ptr(sel), sel.stride(0), n, p, ptr(self.Dt), self.k, ptr(code), ptr(row_w),
-                    ptr(ws), nbytes, ptr(out), stream_ptr(self.device)), 'modl_masked_objective')
+        call('modl_masked_objective', Xh, Xh.stride(0), sel, sel.stride(0), n, p, self.Dt, self.k, code, row_w, ws, nbytes,
+             out, STREAM, device=self.device, dtype=self.dtype)
         return out.cpu().numpy()
 
     def impute(self, code, Xh, obs):
         """Xh where obs != 0 (its bits), code D elsewhere (modl_impute_*): a (n, p) device tensor."""
         n = Xh.shape[0]
         out = torch.empty((n, self.p), dtype=torch_dtype(self.dtype), device=self.device)
-        f = getattr(lib, 'modl_impute_' + sfx(self.dtype))
-        with torch.cuda.device(self.device):
-            check(f(ptr(code), n, self.k, ptr(self.Dt), self.p, ptr(Xh), Xh.stride(0), ptr(obs), obs.stride(0), ptr(out),
-                    self.p, stream_ptr(self.device)), 'modl_impute')
+        call('modl_impute', code, n, self.k, self.Dt, self.p, Xh, Xh.stride(0), obs, obs.stride(0), out, self.p, STREAM,
+             device=self.device, dtype=self.dtype)
         return out
 
     def last_sweeps(self):

@@ -2,13 +2,11 @@
 the same four callables with the same arguments and in-place behaviour, running
 on the GPU through libmodl_hip.so.  NumPy arguments are staged to the device and
 the mutated arrays copied back; torch CUDA tensors are used in place."""
-import ctypes as C
-
 import numpy as np
 import torch
 
-from ._lib import lib, check
-from .device import default_device, dtype_id, sfx, ptr, stream_ptr, to_device
+from ._lib import lib
+from .device import STREAM, call, default_device, dtype_id, np_dtype_of, scratch, to_device
 from .randomkit import batch_weight as _batch_weight  # noqa: F401  (dict_fact_fast.pyx:115)
 
 
@@ -16,9 +14,9 @@ def _regression(kind, G, Dx, X, code, indices, l1_ratio, alpha, positive, tol, m
     lib = _lib if _lib is not None else globals()['lib']        # (tests: the diagnostics build, _lib.load_diag())
     dev = default_device()
     np_in = isinstance(code, np.ndarray)
-    dt = code.dtype if np_in else (np.float32 if code.dtype == torch.float32 else np.float64)
+    dt = code.dtype if np_in else np_dtype_of(code)
     for name, a in (('G', G), ('Dx', Dx), ('X', X)):
-        adt = a.dtype if isinstance(a, np.ndarray) else (np.float32 if a.dtype == torch.float32 else np.float64)
+        adt = a.dtype if isinstance(a, np.ndarray) else np_dtype_of(a)
         if np.dtype(adt) != np.dtype(dt):
             raise TypeError('%s has dtype %s, code has %s (the reference dispatches on one fused type)' % (name, adt, dt))
     dG, dDx, dX, dcode = (to_device(a, dev) for a in (G, Dx, X, code))
@@ -27,12 +25,10 @@ def _regression(kind, G, Dx, X, code, indices, l1_ratio, alpha, positive, tol, m
     p = dX.shape[1]
     multi = 1 if kind == 'multi' else 0
     nbytes = lib.modl_enet_regression_workspace(dtype_id(dt), b, k, multi)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ws = scratch(nbytes, dev)
     dsw = torch.zeros(b, dtype=torch.int32, device=dev) if sweeps is not None else None
-    f = getattr(lib, 'modl_enet_regression_%s_gram_%s' % (kind, sfx(dt)))
-    check(f(ptr(dG), ptr(dDx), ptr(dX), dX.stride(0), p, ptr(dcode), ptr(idx), b, k, l1_ratio, alpha,
-            int(bool(positive)), tol, int(max_iter), ptr(dsw), ptr(ws), nbytes, stream_ptr(dev)),
-          'modl_enet_regression_%s_gram' % kind)
+    call('modl_enet_regression_%s_gram' % kind, dG, dDx, dX, dX.stride(0), p, dcode, idx, b, k, l1_ratio, alpha,
+         int(bool(positive)), tol, int(max_iter), dsw, ws, nbytes, STREAM, device=dev, dtype=dt, lib=lib)
     if sweeps is not None:
         sweeps[:] = dsw.cpu().numpy()
     if np_in:
@@ -57,13 +53,12 @@ def _update_G_average(G_average, G, w_sample):
     """dict_fact_fast.pyx:217-228 (in place)"""
     dev = default_device()
     np_in = isinstance(G_average, np.ndarray)
-    dt = G_average.dtype if np_in else (np.float32 if G_average.dtype == torch.float32 else np.float64)
+    dt = G_average.dtype if np_in else np_dtype_of(G_average)
     dGa = to_device(G_average, dev)
     dG = to_device(G, dev, dtype=dt)
     dw = to_device(np.asarray(w_sample) if not isinstance(w_sample, torch.Tensor) else w_sample, dev, dtype=dt)
     b, k = dGa.shape[0], dGa.shape[1]
-    f = getattr(lib, 'modl_update_G_average_' + sfx(dt))
-    check(f(ptr(dGa), ptr(dG), ptr(dw), b, k, stream_ptr(dev)), 'modl_update_G_average')
+    call('modl_update_G_average', dGa, dG, dw, b, k, STREAM, device=dev, dtype=dt)
     if np_in:
         G_average[:] = dGa.cpu().numpy()
         return G_average

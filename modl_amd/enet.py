@@ -3,12 +3,11 @@ enet_scale :150) on the GPU; 1-D vectors or, batched, the rows of a 2-D array.""
 import numpy as np
 import torch
 
-from ._lib import lib, check
-from .device import default_device, sfx, ptr, stream_ptr, to_device
+from .device import STREAM, call, default_device, np_dtype_of, to_device
 
 
 def _dt(a):
-    return a.dtype if isinstance(a, np.ndarray) else (np.float32 if a.dtype == torch.float32 else np.float64)
+    return a.dtype if isinstance(a, np.ndarray) else np_dtype_of(a)
 
 
 def enet_norm(v, l1_ratio):
@@ -17,7 +16,7 @@ def enet_norm(v, l1_ratio):
     rows = 1 if dv.dim() == 1 else dv.shape[0]
     n = dv.shape[-1]
     out = torch.empty(rows, dtype=dv.dtype, device=dev)
-    check(getattr(lib, 'modl_enet_norm_' + sfx(_dt(v)))(ptr(dv), rows, n, n, 1, l1_ratio, ptr(out), stream_ptr(dev)))
+    call('modl_enet_norm', dv, rows, n, n, 1, l1_ratio, out, STREAM, device=dev, dtype=_dt(v))
     res = out.cpu().numpy()
     return float(res[0]) if dv.dim() == 1 else res
 
@@ -29,8 +28,7 @@ def enet_projection(v, out, radius, l1_ratio):
     n = dv.shape[-1]
     dout = torch.empty_like(dv)
     rad = to_device(np.broadcast_to(np.asarray(radius, dtype=_dt(v)), (rows,)).copy(), dev)
-    check(getattr(lib, 'modl_enet_projection_' + sfx(_dt(v)))(ptr(dv), ptr(dout), rows, n, n, 1, ptr(rad), l1_ratio,
-                                                              stream_ptr(dev)))
+    call('modl_enet_projection', dv, dout, rows, n, n, 1, rad, l1_ratio, STREAM, device=dev, dtype=_dt(v))
     if isinstance(out, np.ndarray):
         out[...] = dout.cpu().numpy()
     else:
@@ -44,6 +42,6 @@ def enet_scale(X, l1_ratio, radius=1):
         raise ValueError('enet_scale works in place: pass a contiguous device tensor or a numpy array')
     rows = 1 if dv.dim() == 1 else dv.shape[0]
     n = dv.shape[-1]
-    check(getattr(lib, 'modl_enet_scale_' + sfx(_dt(X)))(ptr(dv), rows, n, n, 1, l1_ratio, radius, stream_ptr(dev)))
+    call('modl_enet_scale', dv, rows, n, n, 1, l1_ratio, radius, STREAM, device=dev, dtype=_dt(X))
     if isinstance(X, np.ndarray):
         X[...] = dv.cpu().numpy()

@@ -40,7 +40,7 @@ import torch
 from sklearn.base import BaseEstimator
 from sklearn.utils import check_random_state
 
-from .device import gather_rows, to_device
+from .device import current_device, gather_rows, have_gpu, to_device
 from .dict_fact import DictFact, Coder
 from .masker import ArrayMasker, unmask, compute_strategy_mask, _check_strategy
 from .regions import connected_regions
@@ -737,9 +737,7 @@ class fMRIParcellation(BaseEstimator):
         self.verbose = verbose
 
     def _staging(self, dtype):
-        from ._lib import lib
-        device = torch.device('cuda', torch.cuda.current_device()) if lib.modl_device_count() > 0 else None
-        return _Staging(device, dtype if dtype in (np.float32, np.float64) else np.float64)
+        return _Staging(current_device() if have_gpu() else None, dtype if dtype in (np.float32, np.float64) else np.float64)
 
     def _make_masker(self):
         if isinstance(self.mask, str):

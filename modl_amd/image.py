@@ -24,8 +24,7 @@ from sklearn.base import BaseEstimator
 from sklearn.utils import check_random_state, gen_batches
 from sklearn.utils.validation import check_is_fitted
 
-from ._lib import lib, check
-from .device import default_device, ptr, stream_ptr, to_device
+from .device import STREAM, call, default_device, to_device
 from .dict_fact import DictFact, _held_out_set
 
 
@@ -53,7 +52,7 @@ def scale_patches(X, with_mean=True, with_std=True, channel_wise=True, copy=True
 def fill(p, q, r):
     """All patch coordinates in C order (image_fast.pyx:59-74)."""
     out = np.empty((p * q * r, 3), dtype=np.int64)
-    check(lib.modl_image_fill(p, q, r, out.ctypes.data_as(C.c_void_p)), 'modl_image_fill')
+    call('modl_image_fill', p, q, r, out, device=None)
     return out
 
 
@@ -64,11 +63,9 @@ def clean_mask(patches, image):
         raise TypeError('clean_mask: float32 or float64 image expected (fused `floating`, image_fast.pyx:12)')
     image = np.ascontiguousarray(image)
     H, W, Cc = image.shape
-    f = getattr(lib, 'modl_image_clean_mask_' + ('f32' if image.dtype == np.float32 else 'f64'))
     out = np.empty(((H - x + 1) * (W - y + 1) * (Cc - z + 1), 3), dtype=np.int64)
     n = C.c_int64()
-    check(f(image.ctypes.data_as(C.c_void_p), H, W, Cc, x, y, z, out.ctypes.data_as(C.c_void_p), C.byref(n)),
-          'modl_image_clean_mask')
+    call('modl_image_clean_mask', image, H, W, Cc, x, y, z, out, C.byref(n), device=None, dtype=image.dtype)
     return out[:n.value].copy()
 
 
@@ -110,14 +107,8 @@ def grid_origins(image_shape, patch_size, stride=1):
 def _grid_shape(g):
     H, W, _, x, y, si, sj = g
     rows, cols = C.c_int64(), C.c_int64()
-    check(lib.modl_image_grid_shape(H, W, x, y, si, sj, C.byref(rows), C.byref(cols)), 'modl_image_grid_shape')
+    call('modl_image_grid_shape', H, W, x, y, si, sj, C.byref(rows), C.byref(cols), device=None)
     return rows.value, cols.value
-
-
-def _sfx(t):
-    if t.dtype not in (torch.float32, torch.float64):
-        raise TypeError('float32 or float64 expected, got %s' % t.dtype)
-    return 'f32' if t.dtype == torch.float32 else 'f64'
 
 
 def _grid_patches_pass(d_image, g, gcols, row0, nrows, with_mean, with_std):
@@ -125,27 +116,21 @@ def _grid_patches_pass(d_image, g, gcols, row0, nrows, with_mean, with_std):
     H, W, Cc, x, y, si, sj = g
     n, kw = nrows * gcols, dict(dtype=d_image.dtype, device=d_image.device)
     out, mean, den = torch.empty((n, x * y * Cc), **kw), torch.empty((n, Cc), **kw), torch.empty((n, Cc), **kw)
-    with torch.cuda.device(d_image.device):
-        check(getattr(lib, 'modl_image_grid_patches_' + _sfx(d_image))(
-            ptr(d_image), H, W, Cc, x, y, si, sj, row0, nrows, int(bool(with_mean)), int(bool(with_std)), ptr(out),
-            x * y * Cc, ptr(mean), ptr(den), stream_ptr(d_image.device)), 'modl_image_grid_patches')
+    call('modl_image_grid_patches', d_image, H, W, Cc, x, y, si, sj, row0, nrows, int(bool(with_mean)), int(bool(with_std)),
+         out, x * y * Cc, mean, den, STREAM, device=d_image.device, dtype=d_image)
     return out, mean, den
 
 
 def _overlap_add(d_patches, g, row0, nrows, acc):
     H, W, Cc, x, y, si, sj = g
-    with torch.cuda.device(acc.device):
-        check(getattr(lib, 'modl_image_overlap_add_' + _sfx(d_patches))(
-            ptr(d_patches), d_patches.stride(0), H, W, Cc, x, y, si, sj, row0, nrows, ptr(acc), stream_ptr(acc.device)),
-            'modl_image_overlap_add')
+    call('modl_image_overlap_add', d_patches, d_patches.stride(0), H, W, Cc, x, y, si, sj, row0, nrows, acc, STREAM,
+         device=acc.device, dtype=d_patches)
 
 
 def _overlap_finish(acc, g, dtype):
     H, W, Cc, x, y, si, sj = g
     out = torch.empty((H, W, Cc), dtype=dtype, device=acc.device)
-    with torch.cuda.device(acc.device):
-        check(getattr(lib, 'modl_image_overlap_finish_' + _sfx(out))(
-            ptr(acc), H, W, Cc, x, y, si, sj, ptr(out), stream_ptr(acc.device)), 'modl_image_overlap_finish')
+    call('modl_image_overlap_finish', acc, H, W, Cc, x, y, si, sj, out, STREAM, device=acc.device, dtype=out)
     return out
 
 
@@ -157,11 +142,8 @@ def _grid_patches_masked_pass(d_image, d_obs, g, gcols, row0, nrows, with_mean, 
     out, mean, den = torch.empty((n, x * y * Cc), **kw), torch.empty((n, Cc), **kw), torch.empty((n, Cc), **kw)
     obs = torch.empty((n, x * y * Cc), dtype=torch.uint8, device=d_image.device)
     nobs = torch.empty(n, dtype=torch.int32, device=d_image.device)
-    with torch.cuda.device(d_image.device):
-        check(getattr(lib, 'modl_image_grid_patches_masked_' + _sfx(d_image))(
-            ptr(d_image), H, W, Cc, x, y, si, sj, row0, nrows, int(bool(with_mean)), int(bool(with_std)), ptr(out),
-            x * y * Cc, ptr(mean), ptr(den), ptr(d_obs), ptr(obs), ptr(nobs), stream_ptr(d_image.device)),
-            'modl_image_grid_patches_masked')
+    call('modl_image_grid_patches_masked', d_image, H, W, Cc, x, y, si, sj, row0, nrows, int(bool(with_mean)),
+         int(bool(with_std)), out, x * y * Cc, mean, den, d_obs, obs, nobs, STREAM, device=d_image.device, dtype=d_image)
     return out, mean, den, obs, nobs
 
 
@@ -175,11 +157,8 @@ def _patches_masked(d_image, d_obs, origins, patch_shape, with_mean, with_std):
     out, mean, den = torch.empty((n, x * y * z), **kw), torch.empty((n, Cc), **kw), torch.empty((n, Cc), **kw)
     obs = torch.empty((n, x * y * z), dtype=torch.uint8, device=d_image.device)
     nobs = torch.empty(n, dtype=torch.int32, device=d_image.device)
-    with torch.cuda.device(d_image.device):
-        check(getattr(lib, 'modl_image_patches_masked_' + _sfx(d_image))(
-            ptr(d_image), H, W, Cc, ptr(idx), n, x, y, z, int(bool(with_mean)), int(bool(with_std)), ptr(out),
-            x * y * z, ptr(mean), ptr(den), ptr(d_obs), ptr(obs), ptr(nobs), stream_ptr(d_image.device)),
-            'modl_image_patches_masked')
+    call('modl_image_patches_masked', d_image, H, W, Cc, idx, n, x, y, z, int(bool(with_mean)), int(bool(with_std)), out,
+         x * y * z, mean, den, d_obs, obs, nobs, STREAM, device=d_image.device, dtype=d_image)
     return out, mean, den, obs, nobs
 
 
@@ -200,19 +179,15 @@ def masked_candidates(mask, patch_size, min_observed):
 
 def _overlap_add_weighted(d_patches, use, g, row0, nrows, acc, cnt):
     H, W, Cc, x, y, si, sj = g
-    with torch.cuda.device(acc.device):
-        check(getattr(lib, 'modl_image_overlap_add_weighted_' + _sfx(d_patches))(
-            ptr(d_patches), d_patches.stride(0), H, W, Cc, x, y, si, sj, row0, nrows, ptr(acc), ptr(use), ptr(cnt),
-            stream_ptr(acc.device)), 'modl_image_overlap_add_weighted')
+    call('modl_image_overlap_add_weighted', d_patches, d_patches.stride(0), H, W, Cc, x, y, si, sj, row0, nrows, acc, use,
+         cnt, STREAM, device=acc.device, dtype=d_patches)
 
 
 def _inpaint_finish(acc, cnt, d_image, d_obs, keep_observed):
     H, W, Cc = d_image.shape
     out = torch.empty_like(d_image)
-    with torch.cuda.device(acc.device):
-        check(getattr(lib, 'modl_image_inpaint_finish_' + _sfx(out))(
-            ptr(acc), ptr(cnt), ptr(d_image), ptr(d_obs), H, W, Cc, int(bool(keep_observed)), ptr(out),
-            stream_ptr(acc.device)), 'modl_image_inpaint_finish')
+    call('modl_image_inpaint_finish', acc, cnt, d_image, d_obs, H, W, Cc, int(bool(keep_observed)), out, STREAM,
+         device=acc.device, dtype=out)
     return out
 
 

@@ -42,7 +42,8 @@ import scipy.ndimage
 import torch
 from sklearn.base import BaseEstimator
 
-from ._lib import lib, check
+from ._lib import lib
+from .device import STREAM, call, current_device, dtype_id, have_gpu, scratch
 from .signal import clean
 
 SMOOTH_MAX_RADIUS = lib.modl_smooth_max_radius()           # 8: fwhm 8 mm at 2 mm voxels, 6 mm at 1.5 mm
@@ -185,24 +186,19 @@ def _check_dst(dst_row, T):
 
 def _smooth_mask_device(frames, maps, weights, dst):
     """frames: contiguous CUDA tensor (T, Z, Y, X); weights [(w, r)] for x, y, z; dst int64 numpy or None -> (T, V)"""
-    from .device import ptr, stream_ptr
     T, n0, n1, n2 = frames.shape
     V = maps.n_voxels
-    sx = 'f32' if frames.dtype == torch.float32 else 'f64'
     (wx, rx), (wy, ry), (wz, rz) = weights
     wx, wy, wz = (np.ascontiguousarray(w, dtype=np.float64) for w in (wx, wy, wz))
-    need = lib.modl_smooth_mask_workspace(0 if sx == 'f32' else 1, T, n0, n1, n2, rz, ry, rx)
+    need = lib.modl_smooth_mask_workspace(dtype_id(frames), T, n0, n1, n2, rz, ry, rx)
     if need == 0:
         raise ValueError('modl_smooth_mask: unsupported shape %s, radii %s' % (tuple(frames.shape), (rz, ry, rx)))
-    with torch.cuda.device(frames.device):
-        d_col, _ = maps.on(frames.device)
-        d_dst = None if dst is None else torch.from_numpy(dst).to(frames.device)
-        out = torch.empty((T, V), dtype=frames.dtype, device=frames.device)
-        ws = torch.empty(need, dtype=torch.uint8, device=frames.device)
-        check(getattr(lib, 'modl_smooth_mask_' + sx)(
-            ptr(frames), n0 * n1 * n2, T, n0, n1, n2, wz.ctypes.data if rz else None, rz, wy.ctypes.data if ry else None,
-            ry, wx.ctypes.data if rx else None, rx, ptr(d_col), V, ptr(d_dst), ptr(out), V, ptr(ws), need,
-            stream_ptr(frames.device)), 'modl_smooth_mask')
+    d_col, _ = maps.on(frames.device)
+    d_dst = None if dst is None else torch.from_numpy(dst).to(frames.device)
+    out = torch.empty((T, V), dtype=frames.dtype, device=frames.device)
+    ws = scratch(need, frames.device)
+    call('modl_smooth_mask', frames, n0 * n1 * n2, T, n0, n1, n2, wz if rz else None, rz, wy if ry else None, ry,
+         wx if rx else None, rx, d_col, V, d_dst, out, V, ws, need, STREAM, device=frames.device, dtype=frames)
     return out
 
 
@@ -256,9 +252,9 @@ def _smooth_mask(volume, maps, weights, sigmas, dst_row):
     dst = _check_dst(dst_row, vol.shape[3])
     if isinstance(vol, torch.Tensor):
         return _smooth_mask_device(_to_frames(vol), maps, weights, dst)
-    if lib.modl_device_count() <= 0:
+    if not have_gpu():
         return _smooth_mask_host(vol, maps, weights, sigmas, dst)
-    device = torch.device('cuda', torch.cuda.current_device())
+    device = current_device()
     if vol.flags.f_contiguous:
         frames = torch.from_numpy(vol.T).to(device)                          # (T, Z, Y, X), the same bytes
     else:
@@ -303,14 +299,11 @@ def _check_rows(rows, maps):
 
 
 def _unmask_device(rows, maps):
-    from .device import ptr, stream_ptr
     n, V = rows.shape
     X, Y, Z = maps.mask.shape
-    with torch.cuda.device(rows.device):
-        _, d_vox = maps.on(rows.device)
-        out = torch.empty((n, X, Y, Z), dtype=rows.dtype, device=rows.device)
-        check(getattr(lib, 'modl_unmask_' + ('f32' if rows.dtype == torch.float32 else 'f64'))(
-            ptr(rows), rows.stride(0), n, V, ptr(d_vox), X, Y, Z, ptr(out), stream_ptr(rows.device)), 'modl_unmask')
+    _, d_vox = maps.on(rows.device)
+    out = torch.empty((n, X, Y, Z), dtype=rows.dtype, device=rows.device)
+    call('modl_unmask', rows, rows.stride(0), n, V, d_vox, X, Y, Z, out, STREAM, device=rows.device, dtype=rows)
     return out.permute(1, 2, 3, 0)
 
 
@@ -323,10 +316,9 @@ def unmask(rows, mask):
     r = _check_rows(rows, maps)
     if isinstance(r, torch.Tensor):
         return _unmask_device(r, maps)
-    if lib.modl_device_count() <= 0:
+    if not have_gpu():
         return unmask_host(r, maps)
-    device = torch.device('cuda', torch.cuda.current_device())
-    return _unmask_device(torch.from_numpy(np.ascontiguousarray(r)).to(device), maps).cpu().numpy()
+    return _unmask_device(torch.from_numpy(np.ascontiguousarray(r)).to(current_device()), maps).cpu().numpy()
 
 
 def _check_affine(affine, name):
@@ -405,11 +397,9 @@ def _rows_host(box, maps, dst):
 def _resample_device(frames, A, b, shape, order, fill, maps=None, dst=None):
     """frames: contiguous CUDA tensor (T, Z, Y, X).  Box mode (maps None): (T, Z', Y', X'); rows mode: (T, V).  At order 3 the
     frames go through in chunks whose workspace stays within RESAMPLE_WORKSPACE_BYTES (one frame at least)."""
-    from .device import ptr, stream_ptr
     T, n0, n1, n2 = frames.shape
     m0, m1, m2 = shape[2], shape[1], shape[0]
-    sx = 'f32' if frames.dtype == torch.float32 else 'f64'
-    dt = 0 if sx == 'f32' else 1
+    dt = dtype_id(frames)
     if _is_shift(A, b):
         order = 0
     Ak = np.ascontiguousarray(A[::-1, ::-1], dtype=np.float64)           # P A P and P b: the kernel's axes are z, y, x
@@ -421,7 +411,6 @@ def _resample_device(frames, A, b, shape, order, fill, maps=None, dst=None):
         if per_frame == 0:
             raise ValueError('modl_resample: unsupported shape %s' % (tuple(frames.shape),))
         chunk = max(1, min(T, RESAMPLE_WORKSPACE_BYTES // per_frame))
-    fn = getattr(lib, 'modl_resample_' + sx)
     with torch.cuda.device(frames.device):
         if maps is None:
             out = torch.empty((T, m0, m1, m2), dtype=frames.dtype, device=frames.device)
@@ -439,10 +428,9 @@ def _resample_device(frames, A, b, shape, order, fill, maps=None, dst=None):
             n = min(chunk, T - t0)
             need = lib.modl_resample_workspace(dt, n, n0, n1, n2, order)
             if need and (ws is None or ws.numel() < need):
-                ws = torch.empty(need, dtype=torch.uint8, device=frames.device)
-            check(fn(ptr(frames[t0:t0 + n]), box, n, n0, n1, n2, Ak.ctypes.data, bk.ctypes.data, order, fill, m0, m1, m2,
-                     ptr(d_vox), V, ptr(d_order), ptr(d_dst) if fold else None, ptr(target[t0:t0 + n]), ldo, ptr(ws), need,
-                     stream_ptr(frames.device)), 'modl_resample')
+                ws = scratch(need, frames.device)
+            call('modl_resample', frames[t0:t0 + n], box, n, n0, n1, n2, Ak, bk, order, fill, m0, m1, m2, d_vox, V, d_order,
+                 d_dst if fold else None, target[t0:t0 + n], ldo, ws, need, STREAM, device=frames.device, dtype=frames)
         if target is not out:
             out[d_dst] = target
     return out
@@ -455,7 +443,7 @@ def _resample(vol, A, b, shape, order, fill, maps=None, dst=None):
 
     if isinstance(vol, torch.Tensor):
         return finish(_resample_device(_to_frames(vol), A, b, shape, order, fill, maps, dst))
-    if lib.modl_device_count() <= 0:
+    if not have_gpu():
         res = _resample_host(vol, A, b, shape, order, fill)
         return res if maps is None else _rows_host(res, maps, dst)
     return finish(_resample_device(_to_frames(_upload(vol)), A, b, shape, order, fill, maps, dst)).cpu().numpy()
@@ -464,7 +452,7 @@ def _resample(vol, A, b, shape, order, fill, maps=None, dst=None):
 def _upload(vol):
     """numpy (X, Y, Z, T) -> CUDA tensor of that shape on the current device; a Fortran-ordered volume keeps its bytes (its
     frames (T, Z, Y, X) are then a view)"""
-    device = torch.device('cuda', torch.cuda.current_device())
+    device = current_device()
     if vol.flags.f_contiguous:
         return torch.from_numpy(vol.T).to(device).permute(3, 2, 1, 0)
     return torch.from_numpy(np.ascontiguousarray(vol)).to(device)
@@ -717,43 +705,32 @@ def compute_multi_background_mask_host(volumes, border_size=2, connected=True, o
 # ---- the device: masks are uint8 tensors (Z, Y, X), the kernels' frame order
 def _frame_mean_device(frames, zero_nonfinite):
     """frames: contiguous CUDA tensor (T, Z, Y, X) -> (Z, Y, X), contract item 1 (csrc/compute_mask.hip)"""
-    from .device import ptr, stream_ptr
     T, n0, n1, n2 = frames.shape
     box = n0 * n1 * n2
-    with torch.cuda.device(frames.device):
-        mean = torch.empty((n0, n1, n2), dtype=frames.dtype, device=frames.device)
-        check(getattr(lib, 'modl_frame_mean_' + ('f32' if frames.dtype == torch.float32 else 'f64'))(
-            ptr(frames), box, T, box, int(bool(zero_nonfinite)), ptr(mean), stream_ptr(frames.device)), 'modl_frame_mean')
+    mean = torch.empty((n0, n1, n2), dtype=frames.dtype, device=frames.device)
+    call('modl_frame_mean', frames, box, T, box, int(bool(zero_nonfinite)), mean, STREAM, device=frames.device, dtype=frames)
     return mean
 
 
 def _morph_device(m, iterations, dilate):
-    from .device import ptr, stream_ptr
     n0, n1, n2 = m.shape
     need = lib.modl_morph_workspace(n0, n1, n2, iterations)
     if need == 0:
         raise ValueError('modl_binary_morph: unsupported box %s, iterations %r' % (tuple(m.shape), iterations))
-    with torch.cuda.device(m.device):
-        out = torch.empty_like(m)
-        ws = torch.empty(need, dtype=torch.uint8, device=m.device)
-        check(lib.modl_binary_morph(ptr(m), n0, n1, n2, iterations, int(dilate), ptr(out), ptr(ws), need, stream_ptr(m.device)),
-              'modl_binary_morph')
+    out, ws = torch.empty_like(m), scratch(need, m.device)
+    call('modl_binary_morph', m, n0, n1, n2, iterations, int(dilate), out, ws, need, STREAM, device=m.device)
     return out
 
 
 def _largest_device(m):
     """(the largest component (Z, Y, X) uint8, [components, size, first voxel]) - the three numbers come to the host"""
-    from .device import ptr, stream_ptr
     n0, n1, n2 = m.shape
     need = lib.modl_label_workspace(n0, n1, n2)
     if need == 0:
         raise ValueError('modl_largest_component: unsupported box %s' % (tuple(m.shape),))
-    with torch.cuda.device(m.device):
-        out = torch.empty_like(m)
-        info = torch.empty(3, dtype=torch.int64, device=m.device)
-        ws = torch.empty(need, dtype=torch.uint8, device=m.device)
-        check(lib.modl_largest_component(ptr(m), n0, n1, n2, ptr(out), ptr(info), ptr(ws), need, stream_ptr(m.device)),
-              'modl_largest_component')
+    out, ws = torch.empty_like(m), scratch(need, m.device)
+    info = torch.empty(3, dtype=torch.int64, device=m.device)
+    call('modl_largest_component', m, n0, n1, n2, out, info, ws, need, STREAM, device=m.device)
     return out, info.cpu().tolist()
 
 
@@ -803,7 +780,7 @@ def _device_frames(volume):
     vol = _check_volume(volume, None)
     if isinstance(vol, torch.Tensor):
         return _to_frames(vol), True
-    if lib.modl_device_count() <= 0:
+    if not have_gpu():
         return vol, None
     return _to_frames(_upload(vol)), False
 
@@ -824,7 +801,7 @@ def _mask_in(mask, name='mask'):
     if mask.ndim != 3 or mask.dtype not in (np.bool_, torch.bool):
         raise ValueError('%s must be a 3-D boolean array, got shape %s, dtype %s' % (name, tuple(mask.shape), mask.dtype))
     if not cuda:
-        mask = torch.from_numpy(np.ascontiguousarray(mask)).to(torch.device('cuda', torch.cuda.current_device()))
+        mask = torch.from_numpy(np.ascontiguousarray(mask)).to(current_device())
     return mask.permute(2, 1, 0).contiguous().to(torch.uint8), cuda
 
 
@@ -833,7 +810,7 @@ def largest_connected_component(mask):
     components of equal size the one whose first voxel comes first in C order.  numpy in, numpy out; a CUDA tensor in, a
     CUDA tensor out.  On the device: union-find labelling, csrc/compute_mask.hip.  Without a GPU:
     `largest_connected_component_host`.  ValueError: a mask that is not 3-D boolean or has no true voxel."""
-    if not isinstance(mask, torch.Tensor) and lib.modl_device_count() <= 0:
+    if not isinstance(mask, torch.Tensor) and not have_gpu():
         return largest_connected_component_host(mask)
     m, cuda = _mask_in(mask)
     out, info = _largest_device(m)
@@ -914,7 +891,7 @@ def intersect_masks(masks, threshold=0.5, connected=True):
     ValueError: a threshold outside [0, 1], an empty list, shapes that differ."""
     threshold = _check_threshold(threshold)
     masks = _check_masks(masks)
-    if lib.modl_device_count() <= 0 and not any(isinstance(m, torch.Tensor) for m in masks):
+    if not have_gpu() and not any(isinstance(m, torch.Tensor) for m in masks):
         return intersect_masks_host(masks, threshold, connected)
     pairs = [_mask_in(m, 'masks[%d]' % i) for i, m in enumerate(masks)]
     return _mask_out(_intersect_device([m for m, _ in pairs], threshold, connected), any(c for _, c in pairs))
@@ -933,7 +910,7 @@ def _multi(volumes, single_device, single_host, threshold, connected, what):
             state['cuda'] = state['cuda'] or bool(cuda)
             yield single_host(frames) if cuda is None else single_device(frames)
 
-    if lib.modl_device_count() <= 0:
+    if not have_gpu():
         found = list(masks())
         if not found:
             raise ValueError('volumes is an empty list')
@@ -1120,7 +1097,7 @@ class ArrayMasker(BaseEstimator):
             return _smooth_mask(volume, maps, self.weights_, self.sigmas_, dst_row)
         vol = _check_volume(volume, None)
         if self._smooths():                                                  # into the mask's box, then the launch of before
-            if not isinstance(vol, torch.Tensor) and lib.modl_device_count() > 0:
+            if not isinstance(vol, torch.Tensor) and have_gpu():
                 return self.mask_volume(_upload(vol), dst_row, affine).cpu().numpy()     # (one upload for both steps)
             return _smooth_mask(_resample(vol, grid[0], grid[1], maps.mask.shape, 3, 0.0), maps, self.weights_, self.sigmas_,
                                 dst_row)

@@ -32,9 +32,9 @@ import numpy as np
 import torch
 from sklearn.utils import check_random_state
 
-from ._lib import lib, check
-from .canica import (_is_cuda, _have_gpu, _to_device, _check_2d, _check_k, _out, reduce_record, group_components,
-                     reduce_record_host, group_components_host)
+from ._lib import lib
+from .canica import _check_2d, _check_records, reduce_record, group_components, reduce_record_host, group_components_host
+from .device import STREAM, as_float_tensor, call, have_gpu, is_cuda, like_input, scratch
 
 __all__ = ['KMeansParcels', 'Parcellation', 'kmeans_init', 'kmeans_parcels', 'label_signals', 'signals_to_rows', 'parcellate',
            'kmeans_init_host', 'kmeans_parcels_host', 'label_signals_host', 'signals_to_rows_host', 'parcellate_host',
@@ -96,7 +96,6 @@ def kmeans_assign(X, C, active, score=None, labels=None, ws=None):
     """One launch of modl_kmeans_assign_f64 on CUDA tensors: X (d, V) float64 with contiguous rows, C (n, K, d) float64
     contiguous, active (R,) int32 -> (score (n, V) float64, labels (n, V) int32, 0-based); only the rows of the listed sets are
     written."""
-    from .device import ptr, stream_ptr
     d, V = X.shape
     n, K = C.shape[:2]
     R = int(active.shape[0])
@@ -106,27 +105,23 @@ def kmeans_assign(X, C, active, score=None, labels=None, ws=None):
         labels = torch.full((n, V), -1, dtype=torch.int32, device=X.device)
     need = lib.modl_kmeans_assign_workspace(V, d, K, R)
     if ws is None:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=X.device)
+        ws = scratch(need, X.device)
     elif ws.numel() < need:
         raise ValueError('kmeans_assign: the workspace holds %d bytes, %d sets need %d' % (ws.numel(), R, need))
-    with torch.cuda.device(X.device):
-        check(lib.modl_kmeans_assign_f64(ptr(X), X.stride(0) if d > 1 else V, V, d, ptr(C), K, n, ptr(active), R, ptr(score),
-                                         ptr(labels), ptr(ws), ws.numel(), stream_ptr(X.device)), 'modl_kmeans_assign')
+    call('modl_kmeans_assign_f64', X, X.stride(0) if d > 1 else V, V, d, C, K, n, active, R, score, labels, ws, ws.numel(),
+         STREAM, device=X.device)
     return score, labels
 
 
 def label_sums(rows, order, offsets, sums=None):
     """One launch of modl_label_sums_*: rows (T, V) float32 / float64 CUDA tensor with contiguous rows, order (n,) int32,
     offsets (K + 1,) int64 -> sums (T, K) float64."""
-    from .device import ptr, stream_ptr
     T, V = rows.shape
     K = int(offsets.shape[0]) - 1
     if sums is None:
         sums = torch.zeros((T, K), dtype=torch.float64, device=rows.device)
-    f = lib.modl_label_sums_f32 if rows.dtype == torch.float32 else lib.modl_label_sums_f64
-    with torch.cuda.device(rows.device):
-        check(f(ptr(rows), rows.stride(0) if T > 1 else V, T, V, ptr(order), int(order.shape[0]), ptr(offsets), K, ptr(sums),
-                sums.stride(0) if T > 1 else K, stream_ptr(rows.device)), 'modl_label_sums')
+    call('modl_label_sums', rows, rows.stride(0) if T > 1 else V, T, V, order, int(order.shape[0]), offsets, K, sums,
+         sums.stride(0) if T > 1 else K, STREAM, device=rows.device, dtype=rows)
     return sums
 
 
@@ -155,10 +150,10 @@ def kmeans_init(components, n_parcels, n_init=1, random_state=None, return_voxel
     rng.random_sample() * total.  One candidate per step: sklearn's greedy variant tries 2 + log(K) and keeps the best.  On
     the device distances, cumulative sum and search are torch and nothing is transferred until the end; host and device can
     pick different voxels only when a draw falls within rounding of a boundary of the cumulative sum."""
-    cuda = _is_cuda(components)
-    if not cuda and not _have_gpu():
+    cuda = is_cuda(components)
+    if not cuda and not have_gpu():
         return kmeans_init_host(components, n_parcels, n_init, random_state, return_voxels)
-    X = _to_device(components).to(torch.float64)
+    X = as_float_tensor(components).to(torch.float64)
     _check_2d(X, 'components')
     d, V = X.shape
     K = _check_parcels(n_parcels, V)
@@ -177,8 +172,8 @@ def kmeans_init(components, n_parcels, n_init=1, random_state=None, return_voxel
                 closest = torch.minimum(closest, ((X - X[:, v]) ** 2).sum(dim=0))
         centers = X[:, vox.reshape(-1)].T.reshape(n_init, K, d).contiguous()
     if return_voxels:
-        return _out(centers, cuda), _out(vox, cuda)
-    return _out(centers, cuda)
+        return like_input(centers, cuda), like_input(vox, cuda)
+    return like_input(centers, cuda)
 
 
 def kmeans_init_host(components, n_parcels, n_init=1, random_state=None, return_voxels=False):
@@ -230,10 +225,10 @@ def kmeans_parcels(components, n_parcels, n_init=3, init=None, tol=1e-4, max_ite
 
     Returns KMeansParcels(labels (V,) int32 in 1 .. K, centers (K, d), inertia, n_iter (n_init,), converged (n_init,), selected,
     inertias (n_init,)): labels, centres and inertia of the selected restart."""
-    cuda = _is_cuda(components)
-    if not cuda and not _have_gpu():
+    cuda = is_cuda(components)
+    if not cuda and not have_gpu():
         return kmeans_parcels_host(components, n_parcels, n_init, init, tol, max_iter, random_state)
-    X = _to_device(components).to(torch.float64).contiguous()
+    X = as_float_tensor(components).to(torch.float64).contiguous()
     _check_2d(X, 'components')
     d, V = X.shape
     K = _check_parcels(n_parcels, V)
@@ -252,7 +247,7 @@ def kmeans_parcels(components, n_parcels, n_init=3, init=None, tol=1e-4, max_ite
         score = torch.zeros((n, V), dtype=torch.float64, device=dev)
         labels = torch.full((n, V), -1, dtype=torch.int32, device=dev)
         prev = torch.full((n, V), -2, dtype=torch.int32, device=dev)
-        ws = torch.empty(max(lib.modl_kmeans_assign_workspace(V, d, K, n), 8), dtype=torch.uint8, device=dev)
+        ws = scratch(lib.modl_kmeans_assign_workspace(V, d, K, n), dev)
         run, strict = np.ones(n, dtype=bool), np.zeros(n, dtype=bool)
         converged, n_iter = np.zeros(n, dtype=bool), np.zeros(n, dtype=np.int64)
         for it in range(1, max_iter + 1):
@@ -412,12 +407,12 @@ def label_signals(rows, labels, n_labels=None, strategy='mean'):
     K = n_labels, or the largest label.  Labels outside 1 .. K are ignored (0 is "no parcel"); an empty label gives a column of
     zeros."""
     _check_strategy(strategy)
-    cuda = _is_cuda(rows)
+    cuda = is_cuda(rows)
     if isinstance(labels, torch.Tensor) and not cuda:
         labels = labels.detach().cpu().numpy()
-    if not cuda and not _have_gpu():
+    if not cuda and not have_gpu():
         return label_signals_host(rows, labels, n_labels, strategy)
-    R = _to_device(rows).contiguous()
+    R = as_float_tensor(rows).contiguous()
     _check_2d(R, 'rows')
     lab = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
     if lab.dtype.is_floating_point or lab.dtype == torch.bool:
@@ -432,7 +427,7 @@ def label_signals(rows, labels, n_labels=None, strategy='mean'):
         if strategy == 'mean':
             sums = torch.where(counts > 0, sums / counts.clamp_min(1).to(torch.float64), torch.zeros_like(sums))
         signals = sums.to(R.dtype)
-    return _out(signals, cuda), _out(counts, cuda)
+    return like_input(signals, cuda), like_input(counts, cuda)
 
 
 def label_signals_host(rows, labels, n_labels=None, strategy='mean'):
@@ -457,7 +452,7 @@ def label_signals_host(rows, labels, n_labels=None, strategy='mean'):
 def signals_to_rows(signals, labels):
     """The inverse of `label_signals`: (T, K) signals and (V,) labels -> rows (T, V) with rows[t, v] = signals[t, labels[v] - 1],
     0 where the label is outside 1 .. K.  Indexing only: torch on a CUDA tensor, numpy otherwise."""
-    if not _is_cuda(signals):
+    if not is_cuda(signals):
         if isinstance(labels, torch.Tensor):
             labels = labels.detach().cpu().numpy()
         return signals_to_rows_host(signals, labels)
@@ -482,20 +477,6 @@ def signals_to_rows_host(signals, labels):
 
 
 # ---- the pipeline
-def _check_records(records, n_components):
-    if isinstance(records, (np.ndarray, torch.Tensor)) and records.ndim == 2:
-        records = [records]
-    records = list(records)
-    if not records:
-        raise ValueError('parcellate needs at least one record')
-    for r in records:
-        _check_2d(r, 'a record')
-        _check_k(n_components, r.shape[0], 'the shortest record')
-        if r.shape[1] != records[0].shape[1]:
-            raise ValueError('the records must have one number of voxels, got %d and %d' % (records[0].shape[1], r.shape[1]))
-    return records
-
-
 def _sizes(labels, K):
     if isinstance(labels, torch.Tensor):
         return torch.bincount(labels.long() - 1, minlength=K)
@@ -507,14 +488,14 @@ def parcellate(records, n_parcels, n_components=20, n_init=3, tol=1e-4, max_iter
     nilearn clusters), kmeans_parcels on the (n_components, V) basis.  Returns Parcellation(labels (V,) int32 in 1 .. K,
     sizes (K,), variance (n_components,), kmeans: the KMeansParcels record).  ValueError: n_components larger than the
     shortest record."""
-    records = _check_records(records, n_components)
-    cuda = any(_is_cuda(r) for r in records)
-    if not cuda and not _have_gpu():
+    records = _check_records(records, n_components, 'parcellate', same_width=True)
+    cuda = any(is_cuda(r) for r in records)
+    if not cuda and not have_gpu():
         return parcellate_host(records, n_parcels, n_components, n_init, tol, max_iter, random_state)
     K = _check_parcels(n_parcels, records[0].shape[1])
     _check_kmeans_scalars(n_components, n_init, tol, max_iter)
     device = next((r.device for r in records if isinstance(r, torch.Tensor)), None)
-    reduced = [reduce_record(_to_device(r, device), n_components) for r in records]
+    reduced = [reduce_record(as_float_tensor(r, device), n_components) for r in records]
     comp, variance = group_components(reduced, n_components)
     del reduced
     km = kmeans_parcels(comp, K, n_init, None, tol, max_iter, random_state)
@@ -527,7 +508,7 @@ def parcellate(records, n_parcels, n_components=20, n_init=3, tol=1e-4, max_iter
 
 def parcellate_host(records, n_parcels, n_components=20, n_init=3, tol=1e-4, max_iter=300, random_state=None):
     """`parcellate` through the host twins"""
-    records = _check_records(records, n_components)
+    records = _check_records(records, n_components, 'parcellate', same_width=True)
     K = _check_parcels(n_parcels, records[0].shape[1])
     _check_kmeans_scalars(n_components, n_init, tol, max_iter)
     comp, variance = group_components_host([reduce_record_host(r, n_components) for r in records], n_components)

@@ -16,7 +16,8 @@ from sklearn.base import BaseEstimator
 from sklearn.utils import check_array, check_random_state, gen_batches
 
 from ._lib import lib, check, RECSYS_MAX_TOPN, RECSYS_MAX_RANK_TARGETS
-from .device import default_device, dtype_id, sfx, torch_dtype, ptr, stream_ptr, to_device, transpose_to
+from .device import (STREAM, call, default_device, dtype_id, scratch, sfx, torch_dtype, ptr, stream_ptr, to_device,
+                     transpose_to)
 from .randomkit import batch_weight
 
 
@@ -136,7 +137,7 @@ class _RecsysDevice:
         self.comp_norm = torch.zeros(k, dtype=td, device=dev)
         self.feature_n_iter = torch.zeros(self.p, dtype=torch.int64, device=dev)
         nbytes = lib.modl_dict_update_workspace(dtype_id(self.dtype), self.p, k)
-        self.ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        self.ws = scratch(nbytes, dev)
         self.ws_bytes = nbytes
 
     def set_dictionary(self, D):
@@ -147,14 +148,9 @@ class _RecsysDevice:
 
     def codes(self, rows, alpha):
         """ridge codes of the CSR rows `rows` (None = all), written to code[rows]"""
-        f = getattr(lib, 'modl_recsys_codes_' + sfx(self.dtype))
-        if rows is None:
-            check(f(ptr(self.Dt), self.p, self.k, ptr(self.indptr), ptr(self.indices), ptr(self.data), None, None,
-                    self.n, float(alpha), ptr(self.code), stream_ptr(self.device)), 'modl_recsys_codes')
-        else:
-            r = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(self.device)
-            check(f(ptr(self.Dt), self.p, self.k, ptr(self.indptr), ptr(self.indices), ptr(self.data), ptr(r), None,
-                    len(rows), float(alpha), ptr(self.code), stream_ptr(self.device)), 'modl_recsys_codes')
+        r = None if rows is None else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(self.device)
+        call('modl_recsys_codes', self.Dt, self.p, self.k, self.indptr, self.indices, self.data, r, None,
+             self.n if rows is None else len(rows), float(alpha), self.code, STREAM, device=self.device, dtype=self.dtype)
 
     def batch_update(self, batch, alpha, w, n_iter, order):
         """One minibatch (recsys.py:147-165) for the CSR rows `batch` (in this order): one asynchronous call
@@ -243,9 +239,7 @@ class _RecsysDevice:
         out = torch.zeros(Xp.nnz, dtype=torch.float64, device=dev)
         ind = torch.from_numpy(Xp.indices.astype(np.int32)).to(dev)
         iptr = torch.from_numpy(Xp.indptr.astype(np.int32)).to(dev)
-        f = getattr(lib, 'modl_recsys_predict_' + sfx(self.dtype))
-        check(f(ptr(out), ptr(ind), ptr(iptr), ptr(code), Xp.shape[0], self.k, ptr(self.Dt), stream_ptr(dev)),
-              'modl_recsys_predict')
+        call('modl_recsys_predict', out, ind, iptr, code, Xp.shape[0], self.k, self.Dt, STREAM, device=dev, dtype=self.dtype)
         return out.cpu().numpy()
 
     def codes_of(self, X, alpha):
@@ -256,9 +250,8 @@ class _RecsysDevice:
         indices = _csr_piece(X.indices, np.int32, dev)
         data = _csr_piece(X.data, self.dtype, dev)
         code = torch.zeros((X.shape[0], self.k), dtype=torch_dtype(self.dtype), device=dev)
-        f = getattr(lib, 'modl_recsys_codes_' + sfx(self.dtype))
-        check(f(ptr(self.Dt), self.p, self.k, ptr(indptr), ptr(indices), ptr(data), None, None, X.shape[0], float(alpha),
-                ptr(code), stream_ptr(dev)), 'modl_recsys_codes')
+        call('modl_recsys_codes', self.Dt, self.p, self.k, indptr, indices, data, None, None, X.shape[0], float(alpha), code,
+             STREAM, device=dev, dtype=self.dtype)
         return code
 
     def topn_rows_per_call(self, b, n_top):
@@ -278,23 +271,22 @@ class _RecsysDevice:
         if rows_per_call is None:
             rows_per_call = self.topn_rows_per_call(b, n_top)
         rows_per_call = max(int(rows_per_call), 1)
-        f = getattr(lib, 'modl_recsys_topn_' + sfx(self.dtype))
         nbytes = lib.modl_recsys_topn_workspace(dtype_id(self.dtype), self.p, self.k, min(rows_per_call, max(b, 1)), n_top)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        ws = scratch(nbytes, dev)
         for s in range(0, b, rows_per_call):
             e = min(s + rows_per_call, b)
             need = lib.modl_recsys_topn_workspace(dtype_id(self.dtype), self.p, self.k, e - s, n_top)
             if need > ws.numel():                           # (a short last chunk is cut into more slabs)
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                ws = scratch(need, dev)
             if ex_indptr is None:
                 ex = (None, None, None)
             elif ex_rows is None:
                 # rows s .. e-1 of the pattern: the row pointers are absolute, so a view of indptr addresses them
-                ex = (ptr(ex_indptr[s:]), ptr(ex_indices), None)
+                ex = (ex_indptr[s:], ex_indices, None)
             else:
-                ex = (ptr(ex_indptr), ptr(ex_indices), ptr(ex_rows[s:e]))
-            check(f(ptr(code[s:e]), None, e - s, self.k, ptr(self.Dt), self.p, ex[0], ex[1], ex[2], ptr(item_bias), n_top,
-                    ptr(items[s:e]), ptr(scores[s:e]), ptr(ws), ws.numel(), stream_ptr(dev)), 'modl_recsys_topn')
+                ex = (ex_indptr, ex_indices, ex_rows[s:e])
+            call('modl_recsys_topn', code[s:e], None, e - s, self.k, self.Dt, self.p, *ex, item_bias, n_top, items[s:e],
+                 scores[s:e], ws, ws.numel(), STREAM, device=dev, dtype=self.dtype)
         return items
 
     def ranks_rows_per_call(self, b, t_max):
@@ -335,16 +327,13 @@ class _RecsysDevice:
         if rows_per_call is None:
             rows_per_call = self.ranks_rows_per_call(nq, t_max)
         rows_per_call = max(int(rows_per_call), 1)
-        f = getattr(lib, 'modl_recsys_ranks_' + sfx(self.dtype))
-        nbytes = lib.modl_recsys_ranks_workspace(dtype_id(self.dtype), self.p, self.k, min(rows_per_call, nq), t_max)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        ws = scratch(lib.modl_recsys_ranks_workspace(dtype_id(self.dtype), self.p, self.k, min(rows_per_call, nq), t_max), dev)
         for s in range(0, nq, rows_per_call):
             e = min(s + rows_per_call, nq)
-            ex = (None, None, None) if ex_indptr is None else (ptr(ex_indptr), ptr(ex_indices), ptr(d_ex_rows[s:e]))
+            ex = (None, None, None) if ex_indptr is None else (ex_indptr, ex_indices, d_ex_rows[s:e])
             # queries s .. e-1: the row pointers are absolute, so a view of them addresses the same t_indices and ranks
-            check(f(ptr(code), ptr(d_user[s:e]), e - s, self.k, ptr(self.Dt), self.p, ex[0], ex[1], ex[2], ptr(item_bias),
-                    ptr(d_ptr[s:]), ptr(d_tidx), t_max, ptr(d_ranks), ptr(d_cand[s:e]), ptr(ws), ws.numel(), stream_ptr(dev)),
-                  'modl_recsys_ranks')
+            call('modl_recsys_ranks', code, d_user[s:e], e - s, self.k, self.Dt, self.p, *ex, item_bias, d_ptr[s:], d_tidx, t_max,
+                 d_ranks, d_cand[s:e], ws, ws.numel(), STREAM, device=dev, dtype=self.dtype)
         ranks[:] = d_ranks.cpu().numpy()[:len(ranks)]
         n_cand[q_user] = d_cand.cpu().numpy()
         return ranks, n_cand

@@ -35,7 +35,8 @@ import numpy as np
 import scipy.ndimage
 import torch
 
-from ._lib import lib, check
+from ._lib import lib
+from .device import STREAM, call, current_device, have_gpu, scratch
 from .masker import _maps, _check_affine
 
 __all__ = ['Regions', 'connected_regions', 'region_labels', 'connected_regions_host', 'region_labels_host']
@@ -224,25 +225,22 @@ def _maps_per_pass(maps_per_pass, k, box3, device):
 def _labels_device(comp, maps, cutoff, size_threshold, maps_per_pass):
     """comp: CUDA tensor (k, V) with contiguous rows -> labels (k, V) int32, counts (k,) int32, sizes (k, cap) int32, all on
     the device; nothing comes to the host"""
-    from .device import ptr, stream_ptr
     k, V = comp.shape
     box3 = tuple(int(n) for n in maps.col.shape)                             # (Z, Y, X): the kernels' axis order
     min_voxels = int(min(max(np.floor(size_threshold), -1), 2 ** 31 - 1))     # n > t  <=>  n > floor(t) for an integer n
     cap = V // (max(min_voxels, 0) + 1)                                      # no map has more regions than this
-    fn = getattr(lib, 'modl_region_labels_' + ('f32' if comp.dtype == torch.float32 else 'f64'))
     with torch.cuda.device(comp.device):
         d_col, _ = maps.on(comp.device)
         labels = torch.empty((k, V), dtype=torch.int32, device=comp.device)
         counts = torch.empty(k, dtype=torch.int32, device=comp.device)
         sizes = torch.zeros((k, max(cap, 1)), dtype=torch.int32, device=comp.device)
         M, need = _maps_per_pass(maps_per_pass, k, box3, comp.device)
-        ws = torch.empty(need, dtype=torch.uint8, device=comp.device)
+        ws = scratch(need, comp.device)
         ldr = comp.stride(0) if k > 1 else V
         for a in range(0, k, M):
             b = min(a + M, k)
-            check(fn(ptr(comp[a:b]), ldr, b - a, V, ptr(d_col), *box3, cutoff, min_voxels, ptr(labels[a:b]), V, ptr(counts[a:b]),
-                     ptr(sizes[a:b]) if cap else None, sizes.shape[1] if cap else 0, ptr(ws), need, stream_ptr(comp.device)),
-                  'modl_region_labels')
+            call('modl_region_labels', comp[a:b], ldr, b - a, V, d_col, *box3, cutoff, min_voxels, labels[a:b], V, counts[a:b],
+                 sizes[a:b] if cap else None, sizes.shape[1] if cap else 0, ws, need, STREAM, device=comp.device, dtype=comp)
     return labels, counts, sizes
 
 
@@ -251,9 +249,9 @@ def _device_components(components, maps):
     comp = _check_components(components, maps)
     if isinstance(comp, torch.Tensor):
         return comp, True
-    if lib.modl_device_count() <= 0:
+    if not have_gpu():
         return comp, None
-    return torch.from_numpy(np.ascontiguousarray(comp)).to(torch.device('cuda', torch.cuda.current_device())), False
+    return torch.from_numpy(np.ascontiguousarray(comp)).to(current_device()), False
 
 
 def region_labels(components, mask, min_region_size=1350, threshold=None, thresholding_strategy=None, voxel_size=(1, 1, 1),
@@ -292,7 +290,6 @@ def connected_regions(components, mask, min_region_size=1350, threshold=None, th
     through `connected_regions_host`.  MemoryError: the regions, or the workspace of one map, do not fit the free device
     memory.  ValueError: a bad mask, components that are not (k, V), an unknown strategy, a threshold out of range, a
     non-positive voxel size, a bad affine.  UserWarning: no region is left (the arrays are empty)."""
-    from .device import ptr, stream_ptr
     maps = _maps(mask)
     comp, cuda = _device_components(components, maps)
     size_threshold = _size_threshold(min_region_size, voxel_size, mask_affine)
@@ -314,9 +311,8 @@ def connected_regions(components, mask, min_region_size=1350, threshold=None, th
         kept = torch.arange(sizes.shape[1], device=comp.device)[None, :] < counts[:, None]
         sizes = sizes[kept].to(torch.int64)                                  # row-major: by map, then by number
         if R:
-            check(getattr(lib, 'modl_region_gather_' + ('f32' if comp.dtype == torch.float32 else 'f64'))(
-                ptr(comp), comp.stride(0) if k > 1 else V, k, V, ptr(labels), V, ptr(offsets), R, ptr(regions), V,
-                stream_ptr(comp.device)), 'modl_region_gather')
+            call('modl_region_gather', comp, comp.stride(0) if k > 1 else V, k, V, labels, V, offsets, R, regions, V, STREAM,
+                 device=comp.device, dtype=comp)
     if R == 0:
         _empty_warning()
     if cuda:

@@ -39,7 +39,8 @@ import scipy.linalg
 import scipy.signal
 import torch
 
-from ._lib import lib, check
+from ._lib import lib
+from .device import STREAM, call, current_device, dtype_id, have_gpu, scratch
 
 _EPS = float(np.finfo(np.float64).eps)
 CLEAN_MAX_REGRESSORS = lib.modl_clean_max_regressors()     # 64: the coefficients a thread of the kernel keeps
@@ -335,42 +336,34 @@ def clean_host(signals, detrend=True, standardize=True, confounds=None, permutat
 
 def _filtfilt_device(X, coef, detrend, dst, out):
     """X: CUDA tensor (T, V) with unit column stride; coef: (b, a, zi) f64 numpy; dst: int64 numpy or None"""
-    from .device import ptr, stream_ptr
     T, V = X.shape
     b, a, zi = (np.ascontiguousarray(c, dtype=np.float64) for c in coef)
-    sx = 'f32' if X.dtype == torch.float32 else 'f64'
     if out is None:
         out = torch.empty((T, V), dtype=X.dtype, device=X.device)
-    need = lib.modl_filtfilt_workspace(0 if X.dtype == torch.float32 else 1, T, V, len(b))
+    need = lib.modl_filtfilt_workspace(dtype_id(X), T, V, len(b))
     if need == 0:
         raise ValueError('modl_filtfilt: unsupported shape T = %d, V = %d, %d taps' % (T, V, len(b)))
-    with torch.cuda.device(X.device):
-        d_dst = None if dst is None else torch.from_numpy(dst).to(X.device)
-        ws = torch.empty(need, dtype=torch.uint8, device=X.device)
-        check(getattr(lib, 'modl_filtfilt_' + sx)(ptr(X), X.stride(0), T, V, b.ctypes.data, a.ctypes.data, zi.ctypes.data,
-                                                  len(b), int(bool(detrend)), ptr(d_dst), ptr(out), out.stride(0), ptr(ws),
-                                                  need, stream_ptr(X.device)), 'modl_filtfilt')
+    d_dst = None if dst is None else torch.from_numpy(dst).to(X.device)
+    ws = scratch(need, X.device)
+    call('modl_filtfilt', X, X.stride(0), T, V, b, a, zi, len(b), int(bool(detrend)), d_dst, out, out.stride(0), ws, need,
+         STREAM, device=X.device, dtype=X)
     return out
 
 
 def _clean_device(X, Q, standardize, dst, out):
     """X: CUDA tensor (T, V) with unit column stride; Q: f64 numpy (T, q), q >= 1; dst: int64 numpy or None"""
-    from .device import ptr, stream_ptr
     T, V = X.shape
     q = Q.shape[1]
-    sx = 'f32' if X.dtype == torch.float32 else 'f64'
-    dtype_id = 0 if X.dtype == torch.float32 else 1
     if out is None:
         out = torch.empty((T, V), dtype=X.dtype, device=X.device)
-    need = lib.modl_clean_workspace(dtype_id, T, V, q)
+    need = lib.modl_clean_workspace(dtype_id(X), T, V, q)
     if need == 0:
         raise ValueError('modl_clean: unsupported shape T = %d, V = %d, q = %d' % (T, V, q))
-    with torch.cuda.device(X.device):
-        d_Q = torch.from_numpy(np.ascontiguousarray(Q)).to(X.device)
-        d_dst = None if dst is None else torch.from_numpy(dst).to(X.device)
-        ws = torch.empty(need, dtype=torch.uint8, device=X.device)
-        check(getattr(lib, 'modl_clean_' + sx)(ptr(X), X.stride(0), T, V, ptr(d_Q), q, int(bool(standardize)), ptr(d_dst),
-                                               ptr(out), out.stride(0), ptr(ws), need, stream_ptr(X.device)), 'modl_clean')
+    d_Q = torch.from_numpy(np.ascontiguousarray(Q)).to(X.device)
+    d_dst = None if dst is None else torch.from_numpy(dst).to(X.device)
+    ws = scratch(need, X.device)
+    call('modl_clean', X, X.stride(0), T, V, d_Q, q, int(bool(standardize)), d_dst, out, out.stride(0), ws, need, STREAM,
+         device=X.device, dtype=X)
     return out
 
 
@@ -421,9 +414,9 @@ def clean(signals, detrend=True, standardize=True, confounds=None, permutation=N
         if not (out.data_ptr() == res.data_ptr() and out.stride(0) == res.stride(0)):
             out.copy_(res)
         return out
-    if (coef is None and Q.shape[1] == 0) or lib.modl_device_count() <= 0:
+    if (coef is None and Q.shape[1] == 0) or not have_gpu():
         return _clean_host(X, Q, coef, detrend, standardize, permutation, out)
-    device = torch.device('cuda', torch.cuda.current_device())
+    device = current_device()
     res = torch.from_numpy(np.ascontiguousarray(X)).to(device)
     if coef is not None:
         res = _filtfilt_device(res, coef, detrend, dst if Q.shape[1] == 0 else None, None)

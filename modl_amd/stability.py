@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import device as dev
-from ._lib import lib, check, require_gpu, MODL_F32, MODL_F64
+from ._lib import lib
 
 __all__ = ['amari_discrepency', 'mean_amari_discrepency']
 
@@ -70,12 +70,10 @@ def amari_pairs(dictionaries, maxima=False):
         raise ValueError('at least two dictionaries are needed')
     shapes = _check(dictionaries)
     np_dtype = np.dtype(np.float32) if all(_is_f32(D) for D in dictionaries) else np.dtype(np.float64)
-    require_gpu()
     device = dev.default_device()
     n, p = len(dictionaries), int(shapes[0][1])
     ks = np.array([s[0] for s in shapes], dtype=np.int64)
-    dt = MODL_F32 if np_dtype == np.float32 else MODL_F64
-    ws_bytes = lib.modl_amari_workspace(dt, n, ks.ctypes.data_as(C.c_void_p), p)
+    ws_bytes = lib.modl_amari_workspace(dev.dtype_id(np_dtype), n, ks.ctypes.data_as(C.c_void_p), p)
     if ws_bytes == 0:
         raise ValueError('modl_amari_workspace rejected n=%d, p=%d, k=%s' % (n, p, ks.tolist()))
     npairs = n * (n - 1) // 2
@@ -92,15 +90,14 @@ def amari_pairs(dictionaries, maxima=False):
                           % (need / 1e9, free / 1e9, total / 1e9))
     tensors = [_stage(D, np_dtype, device) for D in dictionaries]
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    ws = dev.scratch(ws_bytes, device)
     d_pair = torch.empty(npairs, dtype=torch.float64, device=device)
     tdt = dev.torch_dtype(np_dtype)
     rowmax = torch.empty(n_row, dtype=tdt, device=device) if maxima else None
     colmax = torch.empty(n_col, dtype=tdt, device=device) if maxima else None
     launches = C.c_int(0)
-    fn = getattr(lib, 'modl_amari_' + dev.sfx(np_dtype))
-    check(fn(ptrs, ks.ctypes.data_as(C.c_void_p), n, p, dev.ptr(d_pair), dev.ptr(rowmax), dev.ptr(colmax),
-             dev.ptr(ws), ws_bytes, dev.stream_ptr(device), C.byref(launches)), 'modl_amari_' + dev.sfx(np_dtype))
+    dev.call('modl_amari', ptrs, ks, n, p, d_pair, rowmax, colmax, ws, ws_bytes, dev.STREAM, C.byref(launches),
+             device=device, dtype=np_dtype)
     out = {'d': d_pair.cpu().numpy(), 'dtype': np_dtype, 'launches': launches.value}
     if maxima:
         rm, cm = rowmax.cpu().numpy(), colmax.cpu().numpy()
